@@ -4,9 +4,11 @@
 NMS kept indices), the metric and workload BASELINE.json names (configs[1]: 320x320, batch 32, 1 GPU, synthetic
 VOC-shaped input, random-init weights of the real architecture).
 
-    python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]   (N>1: torch.distributed.run, one rank per GPU)
 
-Prints ONE JSON line (rank 0).  Multi-GPU = images sharded by batch, no data-path collective (weak scaling).
+Prints ONE JSON line (rank 0); `ms_per_step` is the time of one of the K timed steps.  --dump-outputs writes what the last
+timed step returned as DIR/<name>.npy (rank 0's shard); the inputs depend only on the arguments, so two builds run with the
+same arguments can be compared output for output.  Multi-GPU = images sharded by batch, no data-path collective (weak scaling).
 `roofline` is for the dominant device kernel (by summed time), measured with hipEvents on the launch stream inside this
 process; `cpu_baseline` is the CPU oracle ("port": torch-CPU conv + numpy NMS, NOT the reference -- SURVEY.md §8c/d)
 on a bounded sample of the same workload.
@@ -29,11 +31,13 @@ PEAK_HBM_GBS = 8000.0
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps (K)")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=5,
+    ap.add_argument("--reps", type=int, default=1,
                     help="the K-step timed loop is repeated this many times (each bracketed by barrier + synchronize); the "
-                         "line reports the MEDIAN repetition")
+                         "line reports the MEDIAN repetition.  The default 1 times exactly K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--size", type=int, default=320)
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default 32 @320, 16 @640)")
     ap.add_argument("--graph", action="store_true", help="replay the network as a hipGraph")
@@ -144,6 +148,45 @@ def timed_reps(step, steps, warmup, reps, world, dev):
     return sorted(out)
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def write_outputs(dirpath, arrays):
+    """name -> float32 / float64 array -> dirpath/<name>.npy.  Arrays whose first axis is the image are cut to the first n
+    images so that the files, .npy headers included, stay within DUMP_LIMIT_BYTES (inference: 5.6 kB per image, so a
+    cut starts above ~11 000 images)."""
+    import pathlib
+    B = len(next(iter(arrays.values())))
+    per_image = sum(v.nbytes for v in arrays.values()) / B
+    n = min(B, int((DUMP_LIMIT_BYTES - 4096 * len(arrays)) // per_image))
+    d = pathlib.Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(d / f"{name}.npy", v[:n])
+
+
+def infer_outputs(od, last):
+    """What a caller of the timed inference path receives for its last step: the kept flat indices (-1 padded) and
+    their count per image (collect() / predict_batch_device()), and the kept detections' confidences and boxes as
+    predict() returns them, gathered from the same step's buffers (zero padded to max_det)."""
+    if od.n_inflight > 1:
+        keep, cnt = od.collect(last)
+        post = od._pipes[last].post
+    else:
+        keep, cnt = last
+        post = od.post
+    torch.cuda.synchronize()
+    post.gather()
+    torch.cuda.synchronize()
+    B, D = post.B, post.max_det
+    conf, boxes = np.zeros((B, D), np.float32), np.zeros((B, D, 4), np.float32)
+    for b, (_k, c, bx) in enumerate(post.detections_host(B)):
+        conf[b, :len(c)], boxes[b, :len(c)] = c, bx
+    return {"keep_flat": keep.cpu().numpy().astype(np.float64), "keep_count": cnt.cpu().numpy().astype(np.float64),
+            "det_conf": conf, "det_boxes": boxes}
+
+
 def _median(xs):
     return xs[len(xs) // 2] if len(xs) % 2 else 0.5 * (xs[len(xs) // 2 - 1] + xs[len(xs) // 2])
 
@@ -200,7 +243,9 @@ def train_bench(a, rank, world, dev):
         assert seen == world and r_.value == rank, f"RCCL reports rank {r_.value} of {seen}, launcher said {rank} of {world}"
     elif world > 1:
         seen = torch.distributed.get_world_size()
-    rec, _tr = run_train(W.random_init(2), size, batch, a.steps, a.warmup, a.reps, rank, world, dev, comm, a.grad_payload)
+    rec, tr = run_train(W.random_init(2), size, batch, a.steps, a.warmup, a.reps, rank, world, dev, comm, a.grad_payload)
+    if rank == 0 and a.dump_outputs:
+        write_outputs(a.dump_outputs, {"losses": tr.losses.cpu().numpy()})  # what Trainer.step returns
     if rank == 0:
         print(json.dumps({
             "metric": "train_images_per_sec", "value": rec["value"], "unit": "images/s",
@@ -227,18 +272,19 @@ def train_bench(a, rank, world, dev):
 def run_infer(params, size, batch, inflight, steps, warmup, reps, rank, world, dev, graph=False, precision=None):
     """One step = one predict pass over a uint8 batch resident in HBM (network + decode + top-K + NMS).  With inflight > 1
     the step is queued on the next pipeline's stream and overlaps the tail of the previous steps; every step of a
-    repetition is complete before its closing synchronize."""
+    repetition is complete before its closing synchronize.  -> (detector, sorted seconds, what the last step returned)."""
     from object_detector_amd.detector import ObjectDetector
     od = ObjectDetector(params, batch, (size, size), device=dev, use_multi_gpu=world > 1, n_inflight=inflight,
                         precision=precision)
     rng = np.random.default_rng(1000 + rank)  # each rank its own shard of synthetic images
     x = torch.from_numpy(rng.integers(0, 256, (batch, size, size, 3), dtype=np.uint8)).to(dev)
-    if od.n_inflight > 1:
-        step = lambda: od.submit(x, conf_threshold=0.01, graph=graph)  # noqa: E731
-    else:
-        step = lambda: od.predict_batch_device(x, conf_threshold=0.01, graph=graph)  # noqa: E731
+    run = od.submit if od.n_inflight > 1 else od.predict_batch_device
+    last = [None]
+
+    def step():
+        last[0] = run(x, conf_threshold=0.01, graph=graph)
     times = timed_reps(step, steps, warmup, reps, world, dev)
-    return od, times
+    return od, times, last[0]
 
 
 def extra_block(params, a, dev):
@@ -249,7 +295,8 @@ def extra_block(params, a, dev):
     net_flops_320 = 29.01e9 + 7.2e9
 
     def infer(key, size, batch, inflight, steps, precision=None):
-        od, times = run_infer(params, size, batch, inflight, steps, max(3, steps // 5), a.reps, 0, 1, dev, precision=precision)
+        od, times, _ = run_infer(params, size, batch, inflight, steps, max(3, steps // 5), a.reps, 0, 1, dev,
+                                 precision=precision)
         el = _median(times)
         fl = net_flops_320 * (size / 320.0) ** 2 * batch
         what = "" if precision is None else (f", precision={precision} (every logit within 1e-3 x scale of the fp32 oracle: f32 "
@@ -386,7 +433,9 @@ def main():
     size = a.size
     batch = a.batch or (32 if size <= 320 else 16)
     params = W.random_init(2)
-    od, times = run_infer(params, size, batch, a.inflight, a.steps, a.warmup, a.reps, rank, world, dev, a.graph)
+    od, times, last = run_infer(params, size, batch, a.inflight, a.steps, a.warmup, a.reps, rank, world, dev, a.graph)
+    if rank == 0 and a.dump_outputs:  # before time_ops() below reruns the network over these buffers
+        write_outputs(a.dump_outputs, infer_outputs(od, last))
     elapsed = _median(times)
     ranks_seen = world
     if world > 1:

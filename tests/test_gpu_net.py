@@ -105,6 +105,40 @@ def test_entry_points_synthetic(cuda, tmp_path):
     assert len(list((tmp_path / "assign").glob("*.jpg"))) == 2
 
 
+def test_bench_dump_outputs(cuda, tmp_path):
+    """bench.py --dump-outputs: the line reports K timed steps and their ms_per_step, and the files hold what a caller of
+    the timed path receives for bench's seeded batch (kept indices and counts, and the kept detections' confidences and
+    boxes as predict() gathers them), bit for bit."""
+    import json
+    import pathlib
+    import subprocess
+    import sys
+    from object_detector_amd import weights as W
+    from object_detector_amd.detector import ObjectDetector
+    root = pathlib.Path(__file__).resolve().parent.parent
+    B, S, K = 4, 96, 3
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "1",
+                        "--size", str(S), "--batch", str(B), "--no-cpu-baseline", "--no-extra",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == K and line["reps"] == 1 and line["ms_per_step"] > 0
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("keep_flat", "keep_count", "det_conf", "det_boxes")}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+
+    od = ObjectDetector(W.random_init(2), B, (S, S), device=cuda, n_inflight=3)  # bench's plan
+    x = torch.from_numpy(np.random.default_rng(1000).integers(0, 256, (B, S, S, 3), dtype=np.uint8)).to(cuda)
+    keep, cnt = (t.cpu().numpy() for t in od.predict_batch_device(x, conf_threshold=0.01))
+    od.post.gather()
+    torch.cuda.synchronize()
+    assert np.array_equal(got["keep_flat"], keep) and np.array_equal(got["keep_count"], cnt)
+    for b, (k, conf, boxes) in enumerate(od.post.detections_host(B)):
+        n = len(k)
+        assert n == cnt[b] and np.array_equal(k, keep[b, :n])
+        assert np.array_equal(got["det_conf"][b, :n], conf) and np.array_equal(got["det_boxes"][b, :n], boxes)
+        assert not got["det_conf"][b, n:].any() and not got["det_boxes"][b, n:].any()
+
+
 def test_keep_aspect_boxes_map_back(cuda):
     from object_detector_amd.detector import ObjectDetector, load_image
     img = np.random.default_rng(0).integers(0, 256, (100, 200, 3), dtype=np.uint8)
