@@ -64,11 +64,6 @@ long od_sizeof(const char* struct_name);
 long od_offsetof(const char* struct_name, const char* field_name);
 int od_struct_fields(const char* struct_name, char* buf, int buf_bytes);
 
-/* A stream whose kernels run on a subset of the compute units only (bit i of cu_bits[i / 32] = CU i enabled).  The training
- * step (Trainer, OD_TRAIN_WSTREAM_CUS) can confine its weight-gradient chain to one; destroy with od_stream_destroy. */
-int od_stream_create_cu_mask(od_ctx* ctx, const uint32_t* cu_bits, int n_words, void** out_stream);
-int od_stream_destroy(od_ctx* ctx, void* stream);
-
 /* ------------------------------------------------------------------------------------------------
  * K1/K2: fused conv2d forward.  Replaces the Keras Conv2D+BatchNormalization+activation(+Add) layers
  * that `ObjectDetector.predict` executes (reference voc_validate.py:27; network per docs/MODEL.md:5-21).

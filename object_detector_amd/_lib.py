@@ -116,8 +116,6 @@ _PROTOS = {
     "od_sizeof": (C.c_long, [C.c_char_p]),
     "od_offsetof": (C.c_long, [C.c_char_p, C.c_char_p]),
     "od_struct_fields": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int]),
-    "od_stream_create_cu_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
-    "od_stream_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
     "od_conv_weight_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "od_conv_num_tile_cfgs": (C.c_int, []),
     "od_conv2d_fwd": (C.c_int, [C.c_void_p, C.POINTER(ConvDesc), C.c_void_p]),

@@ -165,24 +165,6 @@ extern "C" int od_ctx_destroy(od_ctx* ctx) {
   return OD_OK;
 }
 
-// A HIP stream confined to a subset of the CUs (hipExtStreamCreateWithCUMask): the training step runs its weight-gradient
-// chain on one beside the dz -> dx chain, so that the two chains stop evicting each other's tiles from every CU.
-// cu_bits: bit i of word i / 32 = CU i enabled.
-extern "C" int od_stream_create_cu_mask(od_ctx* ctx, const uint32_t* cu_bits, int n_words, void** out) {
-  OD_REQUIRE(ctx && cu_bits && n_words > 0 && out, "od_stream_create_cu_mask: bad argument");
-  OD_CHECK_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = nullptr;
-  OD_CHECK_HIP(hipExtStreamCreateWithCUMask(&s, (uint32_t)n_words, cu_bits));
-  *out = (void*)s;
-  return OD_OK;
-}
-
-extern "C" int od_stream_destroy(od_ctx* ctx, void* stream) {
-  OD_REQUIRE(ctx && stream, "od_stream_destroy: bad argument");
-  OD_CHECK_HIP(hipStreamDestroy((hipStream_t)stream));
-  return OD_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // Forward plan: the layer list of one network, launched from C++ (eager or as a replayed hipGraph).
 // ---------------------------------------------------------------------------------------------------------------

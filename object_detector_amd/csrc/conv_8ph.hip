@@ -34,10 +34,6 @@ constexpr int E_REGION = 128 * 128;       // one staged region: 128 rows x 64 f1
 constexpr int E_BUF = 4 * E_REGION;       // A-lo, A-hi, B-lo, B-hi
 constexpr int E_ALO = 0, E_AHI = E_REGION, E_BLO = 2 * E_REGION, E_BHI = 3 * E_REGION;
 
-// DBG & 32: s_memtime stamps of K tile 10, waves 0 and 4 of workgroup 0 (5 per phase: load part start, loads issued,
-// DMA wait done, MFMA start, MFMA done); read back with od_debug_e8_stamps
-__device__ unsigned long long g_e8_stamps[2][20];
-
 struct TapWalk {  // wave-uniform position of a K tile inside the (tap, cin) axis
   int c0, tap, tapoff, dx;
   int sel_tap;  // tap the cached per-lane offsets (a_sel) were selected for
@@ -156,26 +152,16 @@ static __device__ __forceinline__ void e8_epilogue_direct(const ConvKP& p, f32x4
   }
 }
 
-// DBG (timing ablations only, results are garbage; selected by OD_CONV_DEBUG on the 3x3 / BM = 256 variant):
-//   1 = no LDS-DMA, 2 = no fragment reads and no MFMA, 8 = no MFMA, 16 = no fragment reads
-// BUF = 1: loaders are buffer_load_dwordx4 ... lds (resource in SGPRs, per-lane byte offset cached per filter tap,
-// K position in the scalar offset: no per-DMA address arithmetic, padding = out-of-range offset -> zeros);
-// BUF = 0: global_load_lds_dwordx4 with 64-bit per-lane addresses and the zero page (kept for A/B timing).
+// Loaders are buffer_load_dwordx4 ... lds (resource in SGPRs, per-lane byte offset cached per filter tap, K position in
+// the scalar offset: no per-DMA address arithmetic, padding = out-of-range offset -> zeros).
 // PW: the pointwise (1x1) layer that consumes this tile's 256 output channels runs in the epilogue (see the end of the
 // kernel); the launch then writes both tensors and the 1x1 layer has no launch of its own.
 // SEG: grouped launch -- the m-tile index selects one of up to three input maps (x, out, H, W, M come from the segment
 // table; stride 1, no residual): the prediction module shared by the pyramid levels as ONE launch per layer.
-template <int KS, int MF1, int DBG = 0, int BUF = 1, bool PW = false, bool SEG = false>
+template <int KS, int MF1, bool PW = false, bool SEG = false>
 __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
   constexpr int MF0 = 4, MT = MF0 + MF1, WROWS = MT * 16, BM = 2 * WROWS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  unsigned long long cst[4] = {0, 0, 0, 0};
-#define E8_CSTAMP(k)                                                                               \
-  do {                                                                                             \
-    if (DBG & 32) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(cst[k])::"memory"); \
-  } while (0)
-  E8_CSTAMP(0);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -217,9 +203,9 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
   // ---- per-lane staging state: 64 rows x 8 chunks per DMA instruction of the workgroup --------------------------
   const int rr = tid >> 3;
   const int lc = (tid & 7) ^ (rr & 7);
-  int a_base[2][2];      // BUF: byte offset of the window-centre pixel (>= 0); else element offset of tap (0,0)
+  int a_base[2][2];      // byte offset of the window-centre pixel (>= 0)
   unsigned a_vmask[2][2];
-  unsigned a_sel[2][2];  // BUF: a_base or E_OOB for the tap the walk is at
+  unsigned a_sel[2][2];  // a_base or E_OOB for the tap the walk is at
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -233,8 +219,7 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
         const unsigned ho = pix / (unsigned)p.Wo;
         const unsigned wo = pix - ho * (unsigned)p.Wo;
         const int hi0 = (int)ho * p.stride - p.pad, wi0 = (int)wo * p.stride - p.pad;
-        a_base[s][j] = BUF ? ((((int)b * p.H + hi0 + p.pad) * p.W + wi0 + p.pad) * p.Cin + lc * 8) * 2
-                           : (((int)b * p.H + hi0) * p.W + wi0) * p.Cin + lc * 8;
+        a_base[s][j] = ((((int)b * p.H + hi0 + p.pad) * p.W + wi0 + p.pad) * p.Cin + lc * 8) * 2;
 #pragma unroll
         for (int t = 0; t < KS * KS; ++t) {
           const int hi = hi0 + t / KS, wi = wi0 + t % KS;
@@ -242,13 +227,13 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
         }
       }
     }
-  int w_off[2][2];  // element offsets of this lane's weight rows
+  int w_off[2][2];  // byte offsets of this lane's weight rows
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int n = n0 + (2 * j + (rr >> 5)) * 64 + s * 32 + (rr & 31);
-      w_off[s][j] = (n * p.Kstride + lc * 8 + ks0 * E_BK) * (BUF ? 2 : 1);
+      w_off[s][j] = (n * p.Kstride + lc * 8 + ks0 * E_BK) * 2;
     }
   // buffer resources: x is addressed from (pad rows + pad pixels) before its start so that the tap offset is >= 0
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
@@ -295,39 +280,21 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
 
   char* const piece = smem + wave * 1024;  // this wave's 8 rows inside a 64-row DMA round
   auto stage_a = [&](int s, TapWalk& w, int buf) {
-    if (DBG & 1) return;
-    if ((DBG & 64) && w.tap != 0) {  // ablation: A traffic of an LDS-window kernel (one DMA round per 9 K tiles)
-      walk_next(w);
-      return;
-    }
     const int koff = w.tapoff + w.c0;
     char* dst = piece + buf * E_BUF + (s ? E_AHI : E_ALO);
-    if (BUF) {
-      if (w.sel_tap != w.tap) {  // wave-uniform: once per filter tap
-        w.sel_tap = w.tap;
+    if (w.sel_tap != w.tap) {  // wave-uniform: once per filter tap
+      w.sel_tap = w.tap;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) a_sel[s][j] = ((a_vmask[s][j] >> w.tap) & 1u) ? (unsigned)a_base[s][j] : E_OOB;
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) blds16(rs_x, a_sel[s][j], koff * 2, dst + j * 8192);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const bool ok = (a_vmask[s][j] >> w.tap) & 1u;
-        const f16* src = ok ? p.x + (a_base[s][j] + koff) : p.zero;
-        glds16(src, dst + j * 8192);
-      }
+      for (int j = 0; j < 2; ++j) a_sel[s][j] = ((a_vmask[s][j] >> w.tap) & 1u) ? (unsigned)a_base[s][j] : E_OOB;
     }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) blds16(rs_x, a_sel[s][j], koff * 2, dst + j * 8192);
     walk_next(w);
   };
   auto stage_b = [&](int s, int t, int buf) {
-    if (DBG & 1) return;
     char* dst = piece + buf * E_BUF + (s ? E_BHI : E_BLO);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (BUF) blds16(rs_w, (unsigned)w_off[s][j], t * (E_BK * 2), dst + j * 8192);
-      else glds16(p.w + (w_off[s][j] + t * E_BK), dst + j * 8192);
-    }
+    for (int j = 0; j < 2; ++j) blds16(rs_w, (unsigned)w_off[s][j], t * (E_BK * 2), dst + j * 8192);
   };
 
   // PW: the second layer's weights (64 KiB: 4 k-slabs of [128 output channels][64 k], the ring's row format) stream into
@@ -367,37 +334,14 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
   const int fb = (wc * 32 + l15) * 128 + ((lq ^ (l15 & 7)) * 16);
 
   f16x8 xa[MF0][2], wlo[2][2], whi[2][2];
-  constexpr bool kRead = !(DBG & (2 | 16)), kMma = !(DBG & (2 | 8));
-  if (!kRead) {
-#pragma unroll
-    for (int f = 0; f < MF0; ++f)
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) xa[f][kh] = f16x8{1, 1, 1, 1, 1, 1, 1, 1};
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int kh = 0; kh < 2; ++kh) wlo[f][kh] = whi[f][kh] = f16x8{1, 1, 1, 1, 1, 1, 1, 1};
-  }
-  auto ldf = [&](f16x8& dst, const char* src) {
-    if (kRead) dst = *(const f16x8*)src;
-  };
+  auto ldf = [&](f16x8& dst, const char* src) { dst = *(const f16x8*)src; };
   auto mma = [&](f32x4& c, const f16x8& a, const f16x8& b) {
-    if (kMma) {
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    } else {
-      asm volatile("" ::"v"(a), "v"(b));
-    }
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
   };
-  unsigned long long st[16];
-#define E8_STAMP(k)                                                     \
-  do {                                                                  \
-    if (DBG & 32) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st[k])::"memory"); \
-  } while (0)
 
   // ---- the four load parts (fragment reads of this phase + LDS-DMA of a later tile + counted wait) and MFMA parts
   auto L0 = [&](int t) {
     const char* cur = smem + (t & 1) * E_BUF;
-    E8_STAMP(0);
 #pragma unroll
     for (int f = 0; f < 2; ++f)
 #pragma unroll
@@ -415,11 +359,9 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
     } else {
       wait_vmcnt<0>();
     }
-    E8_STAMP(1);
   };
   auto L1 = [&](int t) {
     const char* cur = smem + (t & 1) * E_BUF;
-    E8_STAMP(4);
 #pragma unroll
     for (int f = 0; f < 2; ++f)
 #pragma unroll
@@ -432,21 +374,17 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
     } else {
       wait_vmcnt<0>();
     }
-    E8_STAMP(5);
   };
   auto L2 = [&](int t) {
     const char* cur = smem + (t & 1) * E_BUF;
-    E8_STAMP(8);
 #pragma unroll
     for (int f = 0; f < MF1; ++f)
 #pragma unroll
       for (int kh = 0; kh < 2; ++kh) ldf(xa[f][kh], cur + E_AHI + ((fa + f * 2048) ^ (kh * 64)));
     if (t + 2 < nk) stage_a(0, walk_lo, t & 1);
     if (PW && t + 1 == nk) stage_w2(2);
-    E8_STAMP(9);
   };
   auto L3 = [&](int t) {
-    E8_STAMP(12);
     if (t + 2 < nk) {
       stage_b(0, t + 2, t & 1);
       wait_vmcnt<8>();  // A-lo and B-lo of tile t+1
@@ -455,11 +393,8 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
     } else {
       wait_vmcnt<0>();
     }
-    E8_STAMP(13);
   };
   auto M = [&](int ph) {  // ph is a literal at every call site
-    if (DBG & 32) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    E8_STAMP(ph * 4 + 2);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh)
@@ -473,18 +408,8 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
           if (ph == 3) mma(acc[MF0 + i][j], wlo[j][kh], xa[i][kh]);
         }
     __builtin_amdgcn_s_setprio(0);
-    E8_STAMP(ph * 4 + 3);
-  };
-  auto dump_stamps = [&](int t) {
-    if ((DBG & 32) && t == 10 && blockIdx.x == 0 && (wave & 3) == 0) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < 16; ++k) g_e8_stamps[wr][k] = st[k];
-    }
   };
 
-  E8_CSTAMP(1);
   // ONE barrier per phase.  Wave row 0 runs { load part, MFMA part } between two barriers, wave row 1 runs { MFMA part
   // of the previous phase, load part }: on every SIMD one wave is in its MFMA cluster while its partner issues reads
   // and DMAs, and neither waits for the other in between.  Both rows read, stage and wait for phase P in the same
@@ -504,7 +429,6 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
       L3(t);
       M(3);
       __builtin_amdgcn_s_barrier();
-      dump_stamps(t);
     }
   } else {
     L0(0);
@@ -524,11 +448,9 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
         L0(t + 1);
         __builtin_amdgcn_s_barrier();
       }
-      dump_stamps(t);
     }
   }
   __syncthreads();
-  E8_CSTAMP(2);
 
   if (PW) {
     // ---- fused pointwise layer: t = act2(scale2 * (y . W2) + bias2) for this tile's BM pixels, y = the f16 rows the
@@ -616,44 +538,27 @@ __global__ __launch_bounds__(512, 2) void od_conv_8ph(ConvKP p_in) {
     od_mfma_results_ready();
     e8_epilogue_direct<MT>(p, acc, m0 + wr * WROWS, n0 + wc * 64, l15, lq);
   }
-  if (DBG & 32) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    E8_CSTAMP(3);
-    if (blockIdx.x == 0 && (wave & 3) == 0 && lane == 0)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) g_e8_stamps[wr][16 + k] = cst[k];
-  }
 }
 
 struct E8Entry {
   int BM;
   const void* k1;
-  const void* k3;
   const char* name1;
-  const char* name3;
   const void* k1pw;  // + the consuming pointwise layer in the epilogue
   const void* k3pw;
   const char* name1pw;
   const char* name3pw;
-  const void* k3seg;  // grouped launch over several maps (3x3)
+  const void* k3seg;  // 3x3: grouped launches over several maps and ordinary ones alike (see od_conv_8ph_select)
   const char* name3seg;
 };
-#define OD_E8(MF1)                                                                                        \
-  {                                                                                                       \
-    32 * (4 + MF1), (const void*)&od_conv_8ph<1, MF1>, (const void*)&od_conv_8ph<3, MF1>,                 \
-        "od_conv_8ph<1, " #MF1 ", 0, 1, false, false>", "od_conv_8ph<3, " #MF1 ", 0, 1, false, false>",                             \
-        (const void*)&od_conv_8ph<1, MF1, 0, 1, true>, (const void*)&od_conv_8ph<3, MF1, 0, 1, true>,     \
-        "od_conv_8ph<1, " #MF1 ", 0, 1, true, false>", "od_conv_8ph<3, " #MF1 ", 0, 1, true, false>",                   \
-        (const void*)&od_conv_8ph<3, MF1, 0, 1, false, true>, "od_conv_8ph<3, " #MF1 ", 0, 1, false, true>" \
+#define OD_E8(MF1)                                                                                                   \
+  {                                                                                                                  \
+    32 * (4 + MF1), (const void*)&od_conv_8ph<1, MF1>, "od_conv_8ph<1, " #MF1 ", false, false>",                     \
+        (const void*)&od_conv_8ph<1, MF1, true>, (const void*)&od_conv_8ph<3, MF1, true>,                            \
+        "od_conv_8ph<1, " #MF1 ", true, false>", "od_conv_8ph<3, " #MF1 ", true, false>",                            \
+        (const void*)&od_conv_8ph<3, MF1, false, true>, "od_conv_8ph<3, " #MF1 ", false, true>"                      \
   }
 const E8Entry g_e8[] = {OD_E8(4), OD_E8(3), OD_E8(2), OD_E8(1)};  // BM = 256, 224, 192, 160
-const void* const g_e8_dbg[][2] = {{(const void*)&od_conv_8ph<3, 4, 1>, "od_conv_8ph<3, 4, dbg1>"},
-                                   {(const void*)&od_conv_8ph<3, 4, 2>, "od_conv_8ph<3, 4, dbg2>"},
-                                   {(const void*)&od_conv_8ph<3, 4, 8>, "od_conv_8ph<3, 4, dbg8>"},
-                                   {(const void*)&od_conv_8ph<3, 4, 16>, "od_conv_8ph<3, 4, dbg16>"},
-                                   {(const void*)&od_conv_8ph<3, 4, 32>, "od_conv_8ph<3, 4, dbg32>"},
-                                   {(const void*)&od_conv_8ph<3, 4, 64>, "od_conv_8ph<3, 4, dbg64>"},
-                                   {(const void*)&od_conv_8ph<3, 4, 0, 0>, "od_conv_8ph<3, 4, glds>"}};
 constexpr int kNumE8 = sizeof(g_e8) / sizeof(g_e8[0]);
 
 }  // namespace
@@ -666,41 +571,15 @@ bool od_conv_8ph_select(int idx, const ConvKP& p, int ksize, ConvKernelInfo* inf
   if (p.x_bytes >= 0x7F000000u || p.w_bytes >= 0x7F000000u || p.x_bytes == 0) return false;  // E_OOB must stay out of range
   const E8Entry& e = g_e8[idx];
   const bool pw = p.w2 != nullptr;  // the caller (od_conv2d_fwd) has checked od_conv_8ph_can_fuse_pointwise
-  info->fn = ksize == 1 ? (pw ? e.k1pw : e.k1) : (pw ? e.k3pw : e.k3);
-  info->name = ksize == 1 ? (pw ? e.name1pw : e.name1) : (pw ? e.name3pw : e.name3);
-  if (p.nseg > 1) {
-    if (ksize != 3 || pw || p.stride != 1 || p.res_mode != OD_RES_NONE) return false;
-    info->fn = e.k3seg;
-    info->name = e.name3seg;
-  } else if (ksize == 3 && !pw) {
-    // ordinary 3x3 launches run the segment-capable instantiation too (its segment table is empty: nseg <= 1), so that the
-    // kernel is ONE symbol whether or not a layer is grouped; OD_E8_ONE_SYMBOL=0 keeps the plain instantiation (A/B timing)
-    static int one = -1;
-    if (one < 0) {
-      const char* ev = getenv("OD_E8_ONE_SYMBOL");
-      one = ev ? atoi(ev) : 1;
-    }
-    if (one) {
-      info->fn = e.k3seg;
-      info->name = e.name3seg;
-    }
-  }
-  if (idx == 0 && ksize == 3 && p.dbg && !pw) {
-    const int di = p.dbg == 1 ? 0 : p.dbg == 2 ? 1 : p.dbg == 8 ? 2 : p.dbg == 16 ? 3 : p.dbg == 32 ? 4 : p.dbg == 64 ? 5 : p.dbg == 128 ? 6 : -1;
-    if (di >= 0) {
-      info->fn = g_e8_dbg[di][0];
-      info->name = (const char*)g_e8_dbg[di][1];
-    }
-  }
+  info->fn = ksize == 1 ? (pw ? e.k1pw : e.k1) : (pw ? e.k3pw : e.k3seg);
+  info->name = ksize == 1 ? (pw ? e.name1pw : e.name1) : (pw ? e.name3pw : e.name3seg);
+  // ordinary 3x3 launches run the segment-capable instantiation too (its segment table is empty: nseg <= 1), so that the
+  // kernel is ONE symbol whether or not a layer is grouped
+  if (p.nseg > 1 && (ksize != 3 || pw || p.stride != 1 || p.res_mode != OD_RES_NONE)) return false;
   info->BM = e.BM;
   info->BN = E_BN;
   info->threads = 512;
   const size_t epi = (size_t)(e.BM / 2) * (E_BN + 4) * 4;
   *lds_bytes = epi > (size_t)2 * E_BUF ? epi : (size_t)2 * E_BUF;
   return true;
-}
-
-// debug only (not part of include/odhip.h): copies the s_memtime stamps of the OD_CONV_DEBUG=32 build to the host
-extern "C" int od_debug_e8_stamps(unsigned long long* dst) {
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_e8_stamps), sizeof(unsigned long long) * 40) == hipSuccess ? 0 : -1;
 }

@@ -101,14 +101,11 @@ struct BneckCfg {
   }
 };
 
-// DBG = 1 (OD_CONV_DEBUG=32): s_memtime stamps of the 6th tile of workgroup 0, waves 0 and 5 (od_debug_bneck_stamps)
-__device__ unsigned long long g_bn_stamps[2][8];
-
 // C = 64 runs 12 waves: waves 0-7 compute, waves 8-11 only issue the NEXT tile's x-window LDS-DMAs (and wait for them).
 // Stamps of the 8-wave version: producer 3.8 k, window DMA issue 4.8 k (the issuing waves stall while the memory pipeline
 // is full: 41 KB per tile at the CU's HBM share), consumer 2.0 k, epilogue 4.5 k cycles per tile, all in series; with
 // loader waves the 4.8 k run beside the other 10.3 k.
-template <int C, int DBG = 0, int ACT = OD_ACT_LEAKY>
+template <int C, int ACT = OD_ACT_LEAKY>
 __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck(BneckKP p, int ntiles) {
   using Cf = BneckCfg<C>;
   constexpr bool LOADERS = (C == 64);
@@ -225,15 +222,8 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
     }
 
   int cur = 0;
-  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int tcount = 0;
-#define BN_STAMP(k)                                                                              \
-  do {                                                                                           \
-    if (DBG) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st[k])::"memory");      \
-  } while (0)
 #pragma unroll 1
   for (; tile < ntiles; tile += (int)gridDim.x) {
-    BN_STAMP(0);
     const int b = tile / tpi;
     const int trem = tile - b * tpi;
     const int tyi = trem / p.tiles_x, txi = trem - tyi * p.tiles_x;
@@ -305,9 +295,7 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
         }
       }
     }
-    BN_STAMP(1);
     __syncthreads();  // t window complete; w1 region and (streamed) x window free
-    BN_STAMP(2);
 
     if (Cf::RESIDENT) {
       if (!LOADERS && tile + (int)gridDim.x < ntiles) issue_xwin(tile + (int)gridDim.x, cur ^ 1);  // next tile's window
@@ -316,7 +304,6 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
       for (int k = 1; k <= 6; ++k) load_tap((k % 3) * 3 + k / 3, Cf::slot_off(k));  // consumption order, see below
     }
 
-    BN_STAMP(3);
     // ---- consumer: 3x3 from the t window -----------------------------------------------------------------------
     f32x4 acc[4][NFW];
 #pragma unroll
@@ -393,7 +380,6 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
       do_tap(2, Cf::slot_off(1));            // k = 8
     }
 
-    BN_STAMP(4);
     od_mfma_results_ready();
     // ---- epilogue: 8 consecutive channels per lane (permlane16 swap of a fragment pair) + residual ----------------
 #pragma unroll
@@ -435,19 +421,12 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
         *(f16x8*)(p.out + ((long long)(b * p.H + y0 + ty) * p.W + x0 + l15) * C + ch) = h;
       }
     }
-    BN_STAMP(5);
     if (Cf::RESIDENT) {
       // the next tile's window was issued BEFORE this tile's (NFW/2)*4 output stores: a counted wait retires the DMA
       // and leaves the stores in flight (vmcnt retires in issue order)
       if (!LOADERS) wait_vmcnt<(NFW / 2) * 4>();  // (with loader waves the compute waves have no DMA of their own in flight)
-      BN_STAMP(6);
       __syncthreads();   // everyone is done with the t window and with this tile's x window
       cur ^= 1;
-    }
-    BN_STAMP(7);
-    if (DBG && blockIdx.x == (Cf::RESIDENT ? 0 : 300) && (wave == 0 || wave == 5) && (++tcount == 6 || !Cf::RESIDENT) && lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) g_bn_stamps[wave ? 1 : 0][k] = st[k];
     }
   }
 }
@@ -458,7 +437,7 @@ extern "C" int od_bottleneck_supported(int H, int W, int C) {
   return (C == 64 || C == 128) && H > 0 && W > 0 && (H % 16) == 0 && (W % 16) == 0;
 }
 
-const char* od_bottleneck_kernel_name(int C) { return C == 64 ? "od_bneck<64, 0, 1>" : "od_bneck<128, 0, 1>"; }
+const char* od_bottleneck_kernel_name(int C) { return C == 64 ? "od_bneck<64, 1>" : "od_bneck<128, 1>"; }
 
 extern "C" int od_bottleneck_fwd(od_ctx* ctx, const od_bneck_desc* d, void* stream) {
   OD_REQUIRE(ctx && d, "od_bottleneck_fwd: null ctx/desc");
@@ -488,22 +467,15 @@ extern "C" int od_bottleneck_fwd(od_ctx* ctx, const od_bneck_desc* d, void* stre
   p.alpha = d->alpha;
   p.tiles_x = d->W / 16;
   p.tiles_y = d->H / 16;
-  static int dbg = -1;
-  if (dbg < 0) {
-    const char* e = getenv("OD_CONV_DEBUG");
-    dbg = e ? atoi(e) : 0;
-  }
   const void* fn;
   if (d->C == 64) {
-    fn = dbg == 32 && d->act == OD_ACT_LEAKY ? (const void*)&od_bneck<64, 1, OD_ACT_LEAKY>
-         : d->act == OD_ACT_LEAKY            ? (const void*)&od_bneck<64, 0, OD_ACT_LEAKY>
-         : d->act == OD_ACT_ELU              ? (const void*)&od_bneck<64, 0, OD_ACT_ELU>
-                                             : (const void*)&od_bneck<64, 0, OD_ACT_LINEAR>;
+    fn = d->act == OD_ACT_LEAKY ? (const void*)&od_bneck<64, OD_ACT_LEAKY>
+         : d->act == OD_ACT_ELU ? (const void*)&od_bneck<64, OD_ACT_ELU>
+                                : (const void*)&od_bneck<64, OD_ACT_LINEAR>;
   } else {
-    fn = dbg == 33 && d->act == OD_ACT_LEAKY ? (const void*)&od_bneck<128, 1, OD_ACT_LEAKY>
-         : d->act == OD_ACT_LEAKY ? (const void*)&od_bneck<128, 0, OD_ACT_LEAKY>
-         : d->act == OD_ACT_ELU ? (const void*)&od_bneck<128, 0, OD_ACT_ELU>
-                                : (const void*)&od_bneck<128, 0, OD_ACT_LINEAR>;
+    fn = d->act == OD_ACT_LEAKY ? (const void*)&od_bneck<128, OD_ACT_LEAKY>
+         : d->act == OD_ACT_ELU ? (const void*)&od_bneck<128, OD_ACT_ELU>
+                                : (const void*)&od_bneck<128, OD_ACT_LINEAR>;
   }
   const int lds = d->C == 64 ? BneckCfg<64>::LDS_BYTES : BneckCfg<128>::LDS_BYTES;
   if (int rc = od_ensure_lds(ctx, fn, (size_t)lds)) return rc;
@@ -514,9 +486,4 @@ extern "C" int od_bottleneck_fwd(od_ctx* ctx, const od_bneck_desc* d, void* stre
   void* args[] = {&p, &ntiles};
   OD_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(d->C == 64 ? 768 : 512), args, (size_t)lds, (hipStream_t)stream));
   return OD_OK;
-}
-
-// debug only (not part of include/odhip.h)
-extern "C" int od_debug_bneck_stamps(unsigned long long* dst) {
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_bn_stamps), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -1;
 }

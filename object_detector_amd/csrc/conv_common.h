@@ -23,7 +23,6 @@ struct ConvKP {
   int Mq;             // transposed mode: B*Hs*Ws source positions (rows per parity class)
   int tconv, Hs, Ws;  // transposed (backward-data of a stride-2 conv): x is [B,Hs,Ws,Cin], gathered through a 2x zero-upsampled view
   unsigned x_bytes, w_bytes;  // extents of x / packed w (buffer-addressed loaders: out-of-range lanes read zeros)
-  int dbg;  // tuning ablations (OD_CONV_DEBUG): bit0 = skip the DMA, bit1 = skip fragment reads + MFMA
   // training forward (od_conv_desc.bn_partials): per-channel partial sums of the STORED f16 outputs of this tile, row
   // mtile of [mtiles][2][Cout] f32 = (sum z, sum z^2): the BatchNorm statistics pass over z disappears
   float* stats;

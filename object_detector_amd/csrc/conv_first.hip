@@ -268,13 +268,9 @@ __global__ __launch_bounds__(256) void od_conv_first_wgrad_finish2(const float* 
 }
 }  // namespace
 
+// otherwise (W % 32 != 0) the widened-copy + generic-kernel path
 static bool first_wgrad_use_stream(int B, int H, int W) {
-  static int stream_ok = -1;
-  if (stream_ok < 0) {
-    const char* e = getenv("OD_FIRST_WGRAD_STREAM");  // 0 = the widened-copy + generic-kernel path (A/B timing)
-    stream_ok = e ? atoi(e) : 1;
-  }
-  return stream_ok && W % 32 == 0 && (long long)B * H * W < (1LL << 31);
+  return W % 32 == 0 && (long long)B * H * W < (1LL << 31);
 }
 
 static int first_wgrad_stream_wgs(const od_ctx* ctx, int B, int H, int W) {

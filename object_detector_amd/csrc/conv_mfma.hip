@@ -180,7 +180,6 @@ __global__ __launch_bounds__(WM* WN * 64 * (SPEC ? 2 : 1), MINW) void od_conv_ig
     }
   };
   auto stage = [&](int buf) {
-    if (p.dbg & 1) return;
     rn = 0;
     char* abuf = smem + buf * Cf::STAGE_BYTES + piece_off;
     char* bbuf = abuf + Cf::A_BYTES;
@@ -263,13 +262,12 @@ __global__ __launch_bounds__(WM* WN * 64 * (SPEC ? 2 : 1), MINW) void od_conv_ig
   const int swz = l15 & 7;
   int buf = 0;
   for (int ks = 0; ks < nk; ++ks) {
-    // retire this step's DMA (issued STAGES-1 steps ago); later steps stay in flight
-    if ((p.dbg & 4) || !is_loader) {
-      // consumers have no DMA of their own; dbg bit 2: never wait for the DMA (garbage results, timing ablation)
-    } else if (STAGES > 2 && ks + (STAGES - 2) < nk) {
-      wait_vmcnt<Cf::LOADS*(STAGES > 2 ? STAGES - 2 : 0)>();
-    } else {
-      wait_vmcnt<0>();
+    // retire this step's DMA (issued STAGES-1 steps ago); later steps stay in flight.  Consumers have no DMA of their own.
+    if (is_loader) {
+      if (STAGES > 2 && ks + (STAGES - 2) < nk)
+        wait_vmcnt<Cf::LOADS*(STAGES > 2 ? STAGES - 2 : 0)>();
+      else
+        wait_vmcnt<0>();
     }
     if (SPEC == 2) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every wave's piece of step ks landed; everyone finished reading step ks-1
@@ -282,7 +280,7 @@ __global__ __launch_bounds__(WM* WN * 64 * (SPEC ? 2 : 1), MINW) void od_conv_ig
     const char* abuf = smem + buf * Cf::STAGE_BYTES;
     const char* bbuf = abuf + Cf::A_BYTES;
     __builtin_amdgcn_s_setprio(1);
-    if (is_consumer && !(p.dbg & 2))
+    if (is_consumer)
 #pragma unroll
     for (int kh = 0; kh < BK / 32; ++kh) {
       f16x8 xa[MT], wb[NTL];
@@ -508,12 +506,6 @@ int pick_cfg(const od_ctx* ctx, int M, int Cin, int Cout, int ksize, bool e8_ok,
   // few tiles, long K.  Up to half a round of 128 x 128 tiles (backward-data of stage 5: M = 3200, Cout = 512, K = 9216) the
   // 64-row specialised tile doubles the workgroups: 55.6 vs 78.8 us (profiles/r02/dgrad_cfg_sweep.txt); above that one
   // deep-ring workgroup per CU
-  static int last = -2;
-  if (last == -2) {
-    const char* e = getenv("OD_PICK_FEW_TILES");  // tuning: force the config of this branch
-    last = e ? atoi(e) : -1;
-  }
-  if (last >= 0) return last;
   return (M >= 2048 && 2 * t128 <= cus) ? 7 : 5;  // (batch-1 maps keep their split-K plan on 5)
 }
 
@@ -647,30 +639,12 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
                    (d->out_pix_stride == 0 || d->out_pix_stride == d->Cout),
                "od_conv2d_fwd: w2 (the consuming pointwise layer) needs a dense f16 output of the first layer");
   }
-  if (tconv && d->tile_cfg < 0 && od_tconv_small_supported(d)) {
-    static int allow = -1;
-    if (allow < 0) {
-      const char* e = getenv("OD_TCONV_SMALL");  // 0 = the generic transposed path (A/B timing)
-      allow = e ? atoi(e) : 1;
-    }
-    if (allow) return od_tconv_small_launch(ctx, d, stream, kernel_name, dry_run);
-  }
-  if (d->tile_cfg < 0 && od_conv_rdirect_supported(d)) {  // (also the transposed form of b.down2's backward-data)
-    static int allow = -1;
-    if (allow < 0) {
-      const char* e = getenv("OD_CONV_RDIRECT");  // 0 = the table kernels (A/B timing)
-      allow = e ? atoi(e) : 1;
-    }
-    if (allow) return od_conv_rdirect_launch(ctx, d, stream, kernel_name, dry_run);
-  }
-  if (!tconv && d->tile_cfg < 0 && od_conv_stream3_supported(d)) {
-    static int allow = -1;
-    if (allow < 0) {
-      const char* e = getenv("OD_CONV_STREAM3");  // 0 = the table kernels (A/B timing)
-      allow = e ? atoi(e) : 1;
-    }
-    if (allow) return od_conv_stream3_launch(ctx, d, stream, kernel_name, dry_run);
-  }
+  if (tconv && d->tile_cfg < 0 && od_tconv_small_supported(d))
+    return od_tconv_small_launch(ctx, d, stream, kernel_name, dry_run);
+  if (d->tile_cfg < 0 && od_conv_rdirect_supported(d))  // (also the transposed form of b.down2's backward-data)
+    return od_conv_rdirect_launch(ctx, d, stream, kernel_name, dry_run);
+  if (!tconv && d->tile_cfg < 0 && od_conv_stream3_supported(d))
+    return od_conv_stream3_launch(ctx, d, stream, kernel_name, dry_run);
   int cfg = d->tile_cfg;
   if (cfg < 0)  // (the 8-wave kernel has its own epilogue without the statistics path: not offered when they are asked for)
     cfg = pick_cfg(ctx, M, d->Cin, d->Cout, d->ksize,
@@ -735,14 +709,6 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
   p.w_bytes = (unsigned)((long long)od_round_up(d->Cout, 256) * p.Kstride * 2);
   p.obs = d->out_batch_stride ? d->out_batch_stride : (long long)p.HoWo * d->Cout;
   p.ops = d->out_pix_stride ? d->out_pix_stride : d->Cout;
-  {
-    static int dbg = -1;
-    if (dbg < 0) {
-      const char* e = getenv("OD_CONV_DEBUG");
-      dbg = e ? atoi(e) : 0;
-    }
-    p.dbg = dbg;
-  }
   ConvKernelInfo e8;
   if (use_e8) {
     // 8-wave / 256-wide schedule (conv_8ph.hip): same launch path (split-K slabs, finish kernel) as the table kernels
@@ -804,13 +770,8 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
     const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
     const int tiles = p.mtiles * p.ntiles;
     const int nk = od_ceil_div(p.Ktot, tc.BK);
-    static int thr_mul = -1, tgt_mul = -1;  // tuning knobs (OD_SPLITK="thr,tgt"): split when tiles*thr <= CUs, aim at tgt*CUs/2 workgroups
-    if (thr_mul < 0) {
-      thr_mul = 8;  // measured on MI355X (profiles/r01/splitk_sweep.txt): split only when <= CUs/8 tiles,
-      tgt_mul = 1;  // aiming at ~CUs/2 workgroups
-      const char* e = getenv("OD_SPLITK");
-      if (e) sscanf(e, "%d,%d", &thr_mul, &tgt_mul);
-    }
+    constexpr int thr_mul = 8;  // measured on MI355X (profiles/r01/splitk_sweep.txt): split only when <= CUs/8 tiles,
+    constexpr int tgt_mul = 1;  // aiming at ~CUs/2 workgroups
     int sk = d->splitk > 1 ? d->splitk : ((tiles * thr_mul <= cus && nk >= 8) ? od_ceil_div(tgt_mul * cus / 2, tiles) : 1);
     if (sk > nk / 4) sk = nk / 4;  // >= 4 K steps per workgroup
     const long long slab_bytes = (long long)M * d->Cout * 4;
@@ -823,16 +784,9 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
   // the consuming pointwise layer inside the epilogue: 8-wave kernel, one n tile holding all 256 channels of a pixel, 128
   // output channels (W2 = 64 KiB of LDS), no split-K slabs
   if (d->w2 && use_e8 && p.splitk == 1 && d->Cout == 256 && d->Cout2 == 128) {
-    static int allow = -1;
-    if (allow < 0) {
-      const char* e = getenv("OD_FUSE_POINTWISE");  // 0 = always two launches (A/B timing)
-      allow = e ? atoi(e) : 1;
-    }
-    if (allow) {
-      p.w2 = (const f16*)d->w2;
-      size_t lds = 0;
-      if (!od_conv_8ph_select(cfg - cfg_e8, p, d->ksize, &e8, &lds)) return OD_ERR_INVALID;
-    }
+    p.w2 = (const f16*)d->w2;
+    size_t lds = 0;
+    if (!od_conv_8ph_select(cfg - cfg_e8, p, d->ksize, &e8, &lds)) return OD_ERR_INVALID;
   }
   if (fused_out) *fused_out = grouped || p.w2 != nullptr;
   // weights/scale/bias are padded to a multiple of 256 output channels, so any BN <= 256 tile stays in bounds.

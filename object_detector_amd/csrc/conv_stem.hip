@@ -75,14 +75,7 @@ static __device__ __forceinline__ void s_buffer_dma(__amdgpu_buffer_rsrc_t rs, i
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
 }
 
-// DBG = 1 (OD_CONV_DEBUG=64): s_memtime stamps of the 6th tile of workgroup 0, waves 0 and 5 (od_debug_stem_stamps)
-__device__ unsigned long long g_stem_stamps[2][8];
-#define ST_STAMP(k)                                                                         \
-  do {                                                                                      \
-    if (DBG) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st[k])::"memory"); \
-  } while (0)
-
-template <int DBG, int ACT = OD_ACT_LEAKY>
+template <int ACT = OD_ACT_LEAKY>
 __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -179,11 +172,8 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
   __syncthreads();
 
   int cur = 0;
-  unsigned long long st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int tcount = 0;
 #pragma unroll 1
   for (; tile < ntiles; tile += (int)gridDim.x) {
-    ST_STAMP(0);
     const int b = tile / tpi;
     const int trem = tile - b * tpi;
     const int tyi = trem / p.tiles_x, txi = trem - tyi * p.tiles_x;
@@ -244,13 +234,10 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
       p_store(wpA, wyA, wxA, a0A, a1A);
       if (hasB) p_store(wpB, wyB, wxB, a0B, a1B);
     }
-    ST_STAMP(1);
     __syncthreads();  // window complete; this tile's uint8 window is free
-    ST_STAMP(2);
 
     const int tnext = tile + (int)gridDim.x;
     if (tnext < ntiles) fetch_u(tnext);  // global byte loads in flight during the consumer
-    ST_STAMP(3);
 
     // ---- consumer: 3x3 stride 2 from the window ------------------------------------------------------------------
     f32x4 acc[4][2];
@@ -280,7 +267,6 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
     }
 
     // ---- epilogue ---------------------------------------------------------------------------------------------
-    ST_STAMP(4);
     od_mfma_results_ready();
     {
       const int ch = (wn * 2 + (lq & 1)) * 16 + (lq >> 1) * 8;
@@ -312,16 +298,9 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
         *(f16x8*)(p.out + ((long long)(b * Ho + y0 + ty) * Wo + x0 + l15) * 64 + ch) = h;
       }
     }
-    ST_STAMP(5);
     if (tnext < ntiles) store_u(cur ^ 1);  // waits for the byte loads issued before the consumer
-    ST_STAMP(6);
     __syncthreads();                        // next window visible; everyone is done with the first-layer window
-    ST_STAMP(7);
     cur ^= 1;
-    if (DBG && blockIdx.x == 0 && (wave == 0 || wave == 5) && ++tcount == 6 && lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) g_stem_stamps[wave ? 1 : 0][k] = st[k];
-    }
   }
 }
 
@@ -329,7 +308,7 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
 
 extern "C" int od_stem_supported(int H, int W) { return H > 0 && W > 0 && (H % 32) == 0 && (W % 32) == 0; }  // net input rule
 
-const char* od_stem_kernel_name() { return "od_stem_k<0, 1>"; }
+const char* od_stem_kernel_name() { return "od_stem_k<1>"; }
 
 extern "C" int od_stem_fwd(od_ctx* ctx, const od_stem_desc* d, void* stream) {
   OD_REQUIRE(ctx && d, "od_stem_fwd: null ctx/desc");
@@ -358,22 +337,11 @@ extern "C" int od_stem_fwd(od_ctx* ctx, const od_stem_desc* d, void* stream) {
   int ntiles = d->B * p.tiles_x * p.tiles_y;
   const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
   const int grid = ntiles < cus ? ntiles : cus;
-  static int dbg = -1;
-  if (dbg < 0) {
-    const char* e = getenv("OD_CONV_DEBUG");
-    dbg = e ? atoi(e) : 0;
-  }
-  const void* fn = dbg == 64 && d->act == OD_ACT_LEAKY ? (const void*)&od_stem_k<1, OD_ACT_LEAKY>
-                   : d->act == OD_ACT_LEAKY            ? (const void*)&od_stem_k<0, OD_ACT_LEAKY>
-                   : d->act == OD_ACT_ELU              ? (const void*)&od_stem_k<0, OD_ACT_ELU>
-                                                       : (const void*)&od_stem_k<0, OD_ACT_LINEAR>;
+  const void* fn = d->act == OD_ACT_LEAKY ? (const void*)&od_stem_k<OD_ACT_LEAKY>
+                   : d->act == OD_ACT_ELU ? (const void*)&od_stem_k<OD_ACT_ELU>
+                                          : (const void*)&od_stem_k<OD_ACT_LINEAR>;
   if (int rc = od_ensure_lds(ctx, fn, (size_t)S_LDS)) return rc;
   void* args[] = {&p, &ntiles};
   OD_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(512), args, (size_t)S_LDS, (hipStream_t)stream));
   return OD_OK;
-}
-
-// debug only (not part of include/odhip.h)
-extern "C" int od_debug_stem_stamps(unsigned long long* dst) {
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stem_stamps), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -1;
 }

@@ -495,12 +495,6 @@ __global__ __launch_bounds__(256, 2) void od_conv_wgrad_thin(WgradKP p, int chun
 // chunks per workgroup so that the pipeline fill and the 256-KiB partial-tile store stay a small part of it
 static int wgrad_w8_split(int cus, int nchunks, int Cout, int Ktot, int* chunks_per_split) {
   const int tiles = od_ceil_div(Cout, W8_TILE) * od_ceil_div(Ktot, W8_TILE);
-  static int target = -1;  // workgroups one launch aims at (OD_WGRAD_W8_WGS; default = every CU)
-  if (target < 0) {
-    const char* e = getenv("OD_WGRAD_W8_WGS");
-    target = e ? atoi(e) : 0;
-  }
-  if (target > 0) cus = target;
   int split = cus / tiles;
   if (split < 1) split = 1;
   if (split > nchunks / 12) split = nchunks / 12 > 0 ? nchunks / 12 : 1;
@@ -513,39 +507,22 @@ static int wgrad_w8_split(int cus, int nchunks, int Cout, int Ktot, int* chunks_
 // round of workgroups fills most of the chip (measured per shape, profiles/r02/wgrad_bench.txt: the 1x1 layers and the
 // 10x10 maps with few tiles run 62-72 workgroups of it and are faster on the 128-wide kernel's 480+)
 static bool wgrad_use_w8(int cus, int M, int Cout, int Ktot) {
-  static int force = -2;
-  if (force == -2) {
-    const char* e = getenv("OD_WGRAD_W8");  // 0 = never, 1 = whenever possible (tuning)
-    force = e ? atoi(e) : -1;
-  }
-  if (force == 0) return false;
-  if (force == 1) return true;
+  constexpr int min_wgs = 160;
+  // pixel chunks per workgroup below which the 128 x 128 kernel is taken.  Standalone the 256-wide kernel wins from ~24
+  // chunks; INSIDE the two-stream step it holds a whole CU (128 KiB of LDS, 256 VGPRs x 8 waves) while the other stream's
+  // kernels wait for a slot, and only pays with long pixel runs: 32 x 320^2 (31 chunks per workgroup on stage 3) 10.80 ->
+  // 10.65 ms without it, 16 x 640^2 (63) 17.5 -> 18.0 ms without it; 60 keeps both (sweep: profiles/r02/wgrad_w8_cps_sweep.txt)
+  constexpr int min_cps = 60;
   const long long tiles = (long long)od_ceil_div(Cout, W8_TILE) * od_ceil_div(Ktot, W8_TILE);
   const double eff = (double)Cout * Ktot / (double)(tiles * W8_TILE * W8_TILE);
   int cps = 0;
   const int split = wgrad_w8_split(cus, od_ceil_div(M, KC), Cout, Ktot, &cps);
-  static int min_wgs = -1, min_cps = -1;
-  if (min_wgs < 0) {
-    const char* e = getenv("OD_WGRAD_W8_MIN");
-    min_wgs = e ? atoi(e) : 160;
-    // pixel chunks per workgroup below which the 128 x 128 kernel is taken.  Standalone the 256-wide kernel wins from ~24
-    // chunks; INSIDE the two-stream step it holds a whole CU (128 KiB of LDS, 256 VGPRs x 8 waves) while the other stream's
-    // kernels wait for a slot, and only pays with long pixel runs: 32 x 320^2 (31 chunks per workgroup on stage 3) 10.80 ->
-    // 10.65 ms without it, 16 x 640^2 (63) 17.5 -> 18.0 ms without it; 60 keeps both (sweep: profiles/r02/wgrad_w8_cps_sweep.txt)
-    const char* c = getenv("OD_WGRAD_W8_CPS");
-    min_cps = c ? atoi(c) : 60;
-  }
   return eff >= 0.74 && tiles * split >= min_wgs && cps >= min_cps;
 }
 
 // the thin kernel's shapes (slab output only): 3x3, 32 -> 64 channels, output rows that are whole 32-pixel chunks
 static bool wgrad_thin_ok(int Cin, int Cout, int ksize, int stride, int H, int W, int Ho, int Wo) {
-  static int allow = -1;
-  if (allow < 0) {
-    const char* e = getenv("OD_WGRAD_THIN");  // 0 = the 128 x 128 kernel (A/B timing)
-    allow = e ? atoi(e) : 1;
-  }
-  return allow && Cin == 32 && Cout == 64 && ksize == 3 && Wo % 32 == 0 && H == Ho * stride && W == Wo * stride;
+  return Cin == 32 && Cout == 64 && ksize == 3 && Wo % 32 == 0 && H == Ho * stride && W == Wo * stride;
 }
 static int wgrad_thin_grid(const od_ctx* ctx, long long nchunks) {
   long long g = 2LL * (ctx->num_cu > 0 ? ctx->num_cu : 256);
@@ -557,11 +534,9 @@ static int wgrad_split(const od_ctx* ctx, int M, int Cout, int Ktot, int* chunks
   const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
   if (wgrad_use_w8(cus, M, Cout, Ktot)) return wgrad_w8_split(cus, nchunks, Cout, Ktot, chunks_per_split);
   const int rtiles = od_ceil_div(Cout, TILE), ctiles = od_ceil_div(Ktot, TILE);
-  static int split_mul = -1;  // workgroups per CU the pixel split aims at (OD_WGRAD_SPLIT; every workgroup emits a full
-  if (split_mul < 0) {        // 64 KiB f32 tile, so more splits = more partial-sum traffic)
-    const char* e = getenv("OD_WGRAD_SPLIT");
-    split_mul = e ? atoi(e) : 2;  // measured on the batch-32 step: 4 -> 18.2 ms, 2 -> 17.5 ms, 1 -> 18.7 ms
-  }
+  // workgroups per CU the pixel split aims at (every workgroup emits a full 64 KiB f32 tile, so more splits = more
+  // partial-sum traffic); measured on the batch-32 step: 4 -> 18.2 ms, 2 -> 17.5 ms, 1 -> 18.7 ms
+  constexpr int split_mul = 2;
   int split = od_ceil_div(split_mul * cus, rtiles * ctiles);
   if (split > nchunks) split = nchunks;
   if (split < 1) split = 1;

@@ -86,15 +86,12 @@ class Net:
     def __init__(self, params, batch_size, input_size=(320, 320), device="cuda:0", backbone_act=("leaky", 0.1),
                  head_act=("elu", 1.0), tile_cfg=None, overlapped=False, share_weights_with=None, precision=None,
                  stream_stages=None, split=None, wide_fpn=None):
-        self.wide_fpn = (os.environ.get("OD_MIXED_WIDE_FPN", "1") != "0") if wide_fpn is None else bool(wide_fpn)
+        self.wide_fpn = True if wide_fpn is None else bool(wide_fpn)
         self.precision = precision or os.environ.get("OD_PRECISION", "f16")
         if self.precision not in ("f16", "mixed"):
             raise ValueError(f"precision must be 'f16' or 'mixed', got {self.precision!r}")
-        env_st, env_sp = os.environ.get("OD_MIXED_STREAM"), os.environ.get("OD_MIXED_SPLIT")
-        self.stream_stages = tuple(stream_stages if stream_stages is not None else
-                                   ([int(v) for v in env_st.split(",") if v] if env_st is not None else MIXED_STREAM_STAGES))
-        self.split = tuple(split if split is not None else
-                           ([v for v in env_sp.split(",") if v] if env_sp is not None else MIXED_SPLIT))
+        self.stream_stages = tuple(stream_stages if stream_stages is not None else MIXED_STREAM_STAGES)
+        self.split = tuple(split if split is not None else MIXED_SPLIT)
         if self.precision == "f16":
             self.stream_stages, self.split, self.wide_fpn = (), (), False
         if any(k not in (3, 4, 5) for k in self.stream_stages):
@@ -117,9 +114,6 @@ class Net:
         self.P = sum(h * w for h, w in self.level_hw) * W.NUM_PRIORS
         self.tile_cfg = dict(tile_cfg or {})
         self.auto_cfg = -2 if overlapped else -1  # od_conv_desc.tile_cfg: -2 = this plan runs beside other batches in flight
-        for item in filter(None, os.environ.get("OD_TILE_CFG", "").split(",")):  # tuning: "b.s3=24,n.lat=25" (name prefixes)
-            pat, cfg = item.split("=")
-            self.tile_cfg[pat] = int(cfg)
         self.fuse_blocks = os.environ.get("OD_FUSE_BLOCKS", "1") != "0"  # fused residual blocks of the early stages
         self.splitk = True  # small-M layers (batch-1) may use split-K through a shared f32 slab workspace
         self._splitk_elems = 0
@@ -366,8 +360,7 @@ class Net:
 
     def _build(self, bact, hact):
         B, H, Wd = self.B, self.H, self.W
-        fuse_stem = (self.fuse_blocks and os.environ.get("OD_FUSE_STEM", "1") != "0"
-                     and self.lib.od_stem_supported(H, Wd))
+        fuse_stem = self.fuse_blocks and self.lib.od_stem_supported(H, Wd)
         if fuse_stem:
             # first two layers in one launch (od_stem_fwd): uint8 in, f16 [B,H/2,W/2,64] out
             w0, sc0, bi0 = self._dev["b.conv0"]
@@ -407,11 +400,10 @@ class Net:
         h, w, cin = H, Wd, 32
         taps = []
         for si, (n, ch) in enumerate(W.STAGES, start=1):
-            fused_block = (self.fuse_blocks and os.environ.get(f"OD_FUSE_BNECK{ch}", "1") != "0"
-                           and self.lib.od_bottleneck_supported(h // 2, w // 2, ch))
+            fused_block = self.fuse_blocks and self.lib.od_bottleneck_supported(h // 2, w // 2, ch)
             # 256-channel stage: a block's 1x1 (256 -> 128) rides in the launch that PRODUCES its input (the stride-2 conv
             # or the previous block's 3x3 -- all 256 channels of a pixel are in one workgroup of the 8-wave kernel)
-            ride = self.fuse_blocks and ch == 256 and not fused_block and os.environ.get("OD_FUSE_POINTWISE", "1") != "0"
+            ride = self.fuse_blocks and ch == 256 and not fused_block
             wide = si in self.stream_stages  # f32 residual stream (precision="mixed")
             if wide:
                 ride = False  # a block's 1x1 reads the f16 copy that od_wide_add rounds from the f32 sum
@@ -469,8 +461,7 @@ class Net:
         # shared prediction module; the last conv writes f32 logits into pred[:, off:off+h*w*8, :]
         off = 0
         cout = W.NUM_PRIORS * self.C
-        group = (self.precision == "f16" and self.tower == 1 and nc % 64 == 0
-                 and os.environ.get("OD_GROUP_HEAD", "1") != "0")
+        group = self.precision == "f16" and self.tower == 1 and nc % 64 == 0
         if group:
             # the prediction module's weights are shared by the three levels (docs/MODEL.md:8): ONE launch per layer over
             # all 67 200 x B / 8 rows instead of three (the 20^2 and 10^2 launches filled 50 and 13 of 256 CUs)

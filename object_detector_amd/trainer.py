@@ -75,10 +75,6 @@ class Trainer:
                              **({} if prior_wh is None else {"prior_wh": prior_wh}))
         self.P = len(self.pb)
         dev = self.device
-        # od_conv_desc.tile_cfg of the forward / backward-data convolutions: -1 = fastest launch on an idle chip, -2 = least
-        # CU x time (the backward-data chain shares the chip with the weight-gradient stream)
-        self.fwd_tile_cfg = int(os.environ.get("OD_TRAIN_FWD_CFG", "-1"))
-        self.bwd_tile_cfg = int(os.environ.get("OD_TRAIN_BWD_CFG", "-1"))
 
         # ---- flat f32 parameter / gradient / momentum buffers -------------------------------------------------
         self.specs = {s[0]: s for s in W.layer_specs(self.num_classes, self.neck_ch, self.tower)}
@@ -139,9 +135,8 @@ class Trainer:
         self.loss_ws = torch.empty(self.lib.od_loss_workspace_bytes(self.B, self.P), dtype=torch.uint8, device=dev)
         mx = max(self.B * (n.H // n.stride) * (n.W // n.stride) * n.Cout for n in self.nodes)
         # dz of the node being processed: three rotating buffers, because the weight gradient of node k runs on a second
-        # stream while the main stream already computes node k-1's dz (backward()); OD_TRAIN_WSTREAM=0 -> one buffer, one stream
-        self.use_wstream = os.environ.get("OD_TRAIN_WSTREAM", "1") != "0"
-        self.dzs = [torch.empty(mx, dtype=torch.float16, device=dev) for _ in range(3 if self.use_wstream else 1)]
+        # stream while the main stream already computes node k-1's dz (backward())
+        self.dzs = [torch.empty(mx, dtype=torch.float16, device=dev) for _ in range(3)]
         self.dz = self.dzs[0]
         # the side streams (weight gradients, collectives) must sit on other hardware queues than the main stream, or nothing
         # overlaps: which queue a fresh stream lands on depends on how many streams the process created before, so they are
@@ -149,25 +144,9 @@ class Trainer:
         # the trainer was built after a few detectors in one process)
         from .detector import stream_queue_sets
         with torch.cuda.device(dev):
-            side = stream_queue_sets(dev, 2, beside=torch.cuda.current_stream(dev)) if self.use_wstream else [None, None]
+            side = stream_queue_sets(dev, 2, beside=torch.cuda.current_stream(dev))
         self._side_streams = side
-        self.wstream = side[0] if self.use_wstream else None
-        # OD_TRAIN_WSTREAM_CUS="first:count[:stride]": the weight-gradient stream confined to `count` CUs starting at `first`
-        # (every `stride`-th CU; an experiment knob -- profiles/r03/train_cu_mask.txt)
-        spec = os.environ.get("OD_TRAIN_WSTREAM_CUS", "")
-        if self.use_wstream and spec:
-            parts = [int(v) for v in spec.split(":")]
-            first, count, stride = parts[0], parts[1], (parts[2] if len(parts) > 2 else 1)
-            ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-            bits = [0] * ((ncu + 31) // 32)
-            for i in range(count):
-                cu = (first + i * stride) % ncu
-                bits[cu // 32] |= 1 << (cu % 32)
-            arr = (C.c_uint32 * len(bits))(*bits)
-            hnd = C.c_void_p()
-            _lib.check(self.lib.od_stream_create_cu_mask(self.ctx.handle, arr, len(bits), C.byref(hnd)), "od_stream_create_cu_mask")
-            self._masked_stream = hnd
-            self.wstream = torch.cuda.ExternalStream(hnd.value, device=dev)
+        self.wstream = side[0]
         self._wg_done = [None] * len(self.dzs)
         # gradient exchange: buckets of whole layers from the END of the flat buffer (the order backward finishes them),
         # each all-reduced on its own stream as soon as its last layer is final -> the RCCL traffic overlaps the rest of
@@ -212,8 +191,7 @@ class Trainer:
             if not names <= done_layers:
                 return
             self.cstream.wait_stream(main)  # BatchNorm / bias gradients of these layers
-            if self.wstream is not None:
-                self.cstream.wait_stream(self.wstream)  # their weight gradients (slab reduce)
+            self.cstream.wait_stream(self.wstream)  # their weight gradients (slab reduce)
             with torch.cuda.stream(self.cstream):
                 self._reduce_range(lo, hi)
             self._next_bucket += 1
@@ -328,7 +306,7 @@ class Trainer:
         d.scale, d.bias = self.ones.data_ptr(), (bias if bias is not None else self.zeros).data_ptr()
         d.out = out if isinstance(out, int) else out.data_ptr()
         d.B, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = self.B, n.H, n.W, n.Cin, n.Cout, n.k, n.stride
-        d.act, d.res_mode, d.tile_cfg = _lib.OD_ACT_LINEAR, _lib.OD_RES_NONE, self.fwd_tile_cfg
+        d.act, d.res_mode, d.tile_cfg = _lib.OD_ACT_LINEAR, _lib.OD_RES_NONE, -1
         d.out_dtype = _lib.OD_DT_F32 if out_f32 else _lib.OD_DT_F16
         d.out_batch_stride, d.out_pix_stride = obs, ops
         if bn_partials is not None:  # BatchNorm partial sums from the conv epilogue (no separate pass over z)
@@ -496,12 +474,10 @@ class Trainer:
             dw = self.view(self.grads, n.name, "w")
             x = self.tensors[n.x]
             # weight gradient: needs only dz and the saved input -> second stream, beside the dz -> dx -> ... chain
-            ws = s
-            if self.wstream is not None:
-                ev = torch.cuda.Event()
-                ev.record(main)
-                self.wstream.wait_event(ev)
-                ws = C.c_void_p(self.wstream.cuda_stream)
+            ev = torch.cuda.Event()
+            ev.record(main)
+            self.wstream.wait_event(ev)
+            ws = C.c_void_p(self.wstream.cuda_stream)
             if n.first:
                 if getattr(self, "_first_ws", None) is None:
                     nb = lib.od_conv_first_bwd_weight_workspace_bytes(h, self.B, n.H, n.W)
@@ -516,10 +492,9 @@ class Trainer:
                 if pending[n.name] == 0:  # every node of the (possibly shared) layer has written its slabs: fixed-order sum
                     _lib.check(lib.od_wgrad_reduce_multi(h, self._wgrad_table.data_ptr() + esz * self._wgrad_entry[n.name],
                                                          1, self.grads.data_ptr(), ws), f"wgrad reduce {n.name}")
-            if self.wstream is not None:
-                done = torch.cuda.Event()
-                done.record(self.wstream)
-                self._wg_done[slot] = done
+            done = torch.cuda.Event()
+            done.record(self.wstream)
+            self._wg_done[slot] = done
             if n.first or pending[n.name] == 0:
                 done_layers.add(n.name)
                 if self.cstream is not None:
@@ -531,7 +506,7 @@ class Trainer:
             d.x, d.w, d.scale, d.bias = dz.data_ptr(), self.wb[n.name].data_ptr(), self.ones.data_ptr(), self.zeros.data_ptr()
             d.out = g.data_ptr()
             d.B, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = self.B, Ho, Wo, n.Cout, n.Cin, n.k, n.stride
-            d.act, d.out_dtype, d.tile_cfg = _lib.OD_ACT_LINEAR, _lib.OD_DT_F16, self.bwd_tile_cfg
+            d.act, d.out_dtype, d.tile_cfg = _lib.OD_ACT_LINEAR, _lib.OD_DT_F16, -1
             d.transposed = int(n.stride == 2)
             if n.x in have:
                 d.res, d.res_mode = g.data_ptr(), _lib.OD_RES_SAME  # accumulate in place
@@ -539,9 +514,8 @@ class Trainer:
                 d.res, d.res_mode = None, _lib.OD_RES_NONE
             _lib.check(lib.od_conv2d_fwd(h, C.byref(d), s), f"dgrad {n.name}")
             have.add(n.x)
-        if self.wstream is not None:
-            main.wait_stream(self.wstream)
-            self._wg_done = [None] * len(self.dzs)
+        main.wait_stream(self.wstream)
+        self._wg_done = [None] * len(self.dzs)
         # (conv weight gradients: each layer's per-split slabs were summed in a fixed order right behind its last
         # weight-gradient launch -- no atomics, and the slabs are still cache-resident when they are read back)
         # shared-layer BN gradients were accumulated over the three levels inside od_bn_bwd

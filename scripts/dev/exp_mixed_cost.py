@@ -1,4 +1,5 @@
-"""Throughput cost of precision="mixed" at the BASELINE sizes, for several (stream_stages, split) choices.
+"""Throughput cost of precision="mixed" at the BASELINE sizes, for several (stream_stages, split) choices: the network alone
+(no post-processing), 3 or 1 batches in flight, one stream per in-flight plan.
 usage: python scripts/dev/exp_mixed_cost.py [B] [S]"""
 import pathlib
 import sys
@@ -9,7 +10,6 @@ sys.path.insert(0, str(ROOT))
 import torch  # noqa: E402
 
 from object_detector_amd import weights as W  # noqa: E402
-from object_detector_amd.detector import ObjectDetector  # noqa: E402
 from object_detector_amd.net import Net  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -19,16 +19,15 @@ x = torch.randint(0, 256, (B, S, S, 3), dtype=torch.uint8, device=dev)
 params = W.random_init(2)
 
 
-def bench(od, steps=60, warm=15):
-    for _ in range(warm):
-        od.submit(x)
-    od.synchronize()
-    torch.cuda.synchronize()
+def bench(nets, streams, steps=60, warm=15):
+    def run(n):
+        for i in range(n):
+            with torch.cuda.stream(streams[i % len(nets)]):
+                nets[i % len(nets)].forward(x)
+        torch.cuda.synchronize()
+    run(warm)
     t0 = time.perf_counter()
-    for _ in range(steps):
-        od.submit(x)
-    od.synchronize()
-    torch.cuda.synchronize()
+    run(steps)
     return (time.perf_counter() - t0) / steps * 1e3
 
 
@@ -37,13 +36,12 @@ plans = [("f16", None, None), ("mixed", (4, 5), ("n.lat4", "n.lat5", "n.out3", "
          ("mixed", (3, 4, 5), ()), ("mixed", (4, 5), ("n.out3", "n.out4", "h.t0", "h.out")), ("mixed", (), ("n.out3", "n.out4", "h.t0", "h.out")),
          ("mixed", (3, 4, 5), ("n.lat3", "n.lat4", "n.lat5", "n.out3", "n.out4", "h.t0", "h.out"))]
 for prec, st, sp in plans:
-    import os
-    if st is not None:
-        os.environ["OD_MIXED_STREAM"] = ",".join(map(str, st))
-        os.environ["OD_MIXED_SPLIT"] = ",".join(sp)
     for nin in (3, 1):
-        od = ObjectDetector(params, B, (S, S), device=dev, use_multi_gpu=False, precision=prec, n_inflight=nin)
-        ms = bench(od)
+        nets = []
+        for _ in range(nin):
+            nets.append(Net(params, B, (S, S), device=dev, overlapped=nin > 1, precision=prec, stream_stages=st, split=sp,
+                            share_weights_with=nets[0] if nets else None))
+        ms = bench(nets, [torch.cuda.Stream(device=dev) for _ in nets])
         print(f"{prec:6s} stream {st} split {sp}: {nin} in flight {ms:.3f} ms/batch = {B / ms * 1e3:.0f} img/s", flush=True)
-        del od
+        del nets
         torch.cuda.empty_cache()

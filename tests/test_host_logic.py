@@ -32,6 +32,42 @@ def test_library_exports_every_header_symbol():
     assert _lib.conv_weight_dims(64, 32, 3) == (256, 320)  # K tail padded to the 64-deep step
 
 
+# Every environment variable the package reads.  Tuning, A/B and debug switches do not belong here: a plan chosen by a
+# variable set in the shell is not the plan the tests checked.
+ENV_ALLOW_LIST = {
+    "OD_PRECISION", "OD_INFLIGHT", "OD_INFLIGHT_CALIBRATE", "OD_DECODE_PROCS", "OD_DECODE_THREADS", "OD_GEN_WORKERS",
+    "OD_VOC_WEIGHTS",                                 # user configuration
+    "OD_TRAIN_GRAD_PAYLOAD", "OD_TRAIN_BUCKET_MB", "OD_TRAIN_FUSE_BN_STATS",
+    "OD_DIST_BACKEND", "OD_BENCH_BACKEND", "RANK", "LOCAL_RANK", "WORLD_SIZE", "HSA_ENABLE_IPC_MODE_LEGACY",
+    "OD_FUSE_BLOCKS",                                 # the layer-by-layer reference plan of the fused-block tests
+    "OD_ABLATE_OPS", "OD_ALLOW_ABLATION",             # bench.py's timing ablation
+    "OD_CONV_RDIRECT_MIN_PIXELS",                     # test hook of the register-direct kernel
+}
+
+
+def test_environment_variables_are_allow_listed():
+    pkg = ROOT / "object_detector_amd"
+    files = list(pkg.rglob("*.py")) + list((pkg / "csrc").glob("*.hip")) + list((pkg / "csrc").glob("*.h"))
+    found = set()
+    for f in files:
+        txt = f.read_text()
+        reads = list(re.finditer(r"(?:getenv|os\.environ(?:\.get|\.setdefault|\.pop)?)\s*[(\[]\s*(?:f?[\"']([^\"']+)[\"']|(\w+))",
+                                 txt))
+        # any other access ("X" in os.environ, os.environ.copy(), an alias of os.environ, ...) would hide a name
+        spans = [m.span() for m in reads]
+        for k in re.finditer(r"\b(?:getenv|environ)\b", txt):
+            assert any(lo <= k.start() < hi for lo, hi in spans), \
+                f"{f.name}:{txt.count(chr(10), 0, k.start()) + 1}: environment access the allow-list cannot read"
+        for m in reads:
+            name = m.group(1)
+            if name is None:  # a module-level constant holding the name
+                c = re.search(r"^%s\s*=\s*[\"']([^\"']+)[\"']" % m.group(2), txt, flags=re.M)
+                assert c, f"{f.name}: environment variable name {m.group(2)} is not a string constant of the module"
+                name = c.group(1)
+            found.add(name)
+    assert found == ENV_ALLOW_LIST, f"not allow-listed: {sorted(found - ENV_ALLOW_LIST)}; unused: {sorted(ENV_ALLOW_LIST - found)}"
+
+
 def test_ctypes_structs_match_library_layout():
     """Every ctypes Structure of _lib.py against the library's own description of the struct it mirrors (od_sizeof /
     od_offsetof / od_struct_fields): same size, same field names in the same order, same byte offsets -- and every struct
