@@ -198,7 +198,7 @@ int od_upsample2x_add(od_ctx* ctx, const void* a, const void* up, void* out, int
  * last 4 = corner-form box offsets: reference check_assign.py:25-27 layout).
  *   conf[b,p,c]  = softmax2(pred[b,p,0:2])[1] * softmax(pred[b,p,2:2+NC])[c]      (docs/MODEL.md:54-58)
  *   boxes[b,p,:] = clip01(priors[p] + loc * loc_scale * [pw,ph,pw,ph])              (od.pb.decode_locs)
- * priors f32 [P,4] corner form, normalised image coordinates.
+ * priors f32 [P,4] corner form, normalised image coordinates.  1 <= NC <= 1024.
  * ---------------------------------------------------------------------------------------------- */
 int od_head_postprocess(od_ctx* ctx, const float* pred, const float* priors, float* conf, float* boxes,
                         int B, int P, int NC, float loc_scale, int clip, void* stream);
@@ -239,7 +239,8 @@ int od_gather_detections(od_ctx* ctx, const float* conf, const float* boxes, con
  * od_topk_scores -> od_nms on the same pred (keys come back SORTED descending here, unused slots 0).
  *   conf: optional dense f32 [B,P,NC] output (NULL in the product path);  workspace: od_detect_workspace_bytes, zeroed once
  *   with od_detect_workspace_init (every call leaves it ready for the next);  nms_workspace: od_nms_workspace_bytes(B, K).
- *   P even, NC <= 76 (the limit of od_head_postprocess, whose dense form stays available for the same pred), K <= 1024. */
+ *   P even, 1 <= NC <= 1024, K <= 1024.  NC <= 76 holds 256 whole rows in LDS; larger class counts stream the class columns
+ *   (same results) and use a workspace of O(B*P) bytes instead of O(B*P*NC). */
 size_t od_detect_workspace_bytes(int B, int P, int NC, int K);
 int od_detect_workspace_init(od_ctx* ctx, void* workspace, size_t workspace_bytes, int B, int P, int NC, void* stream);
 int od_detect(od_ctx* ctx, const float* pred, const float* priors, int B, int P, int NC, float loc_scale, int clip,
@@ -268,7 +269,7 @@ int od_assign_anchors(od_ctx* ctx, const float* priors, const float* gt_boxes, c
 
 /* K10: loss forward + gradient (reference docs/MODEL.md:33-52): focal(objectness, 2-class softmax) +
  * softmax-CE(classes, assigned priors) + box loss (box_mode 0 smooth-L1 / 1 MSE, assigned priors), each weighted and
- * divided by max(1, #assigned).  pred, y, grad f32 [B,P,2+NC+4]; losses f32 [4] = obj, cls, box, total. */
+ * divided by max(1, #assigned).  pred, y, grad f32 [B,P,2+NC+4]; losses f32 [4] = obj, cls, box, total.  1 <= NC <= 1024. */
 size_t od_loss_workspace_bytes(int B, int P);
 int od_loss_fwd_bwd(od_ctx* ctx, const float* pred, const float* y, float* grad, float* losses, int B, int P, int NC,
                     float focal_alpha, float focal_gamma, int box_mode, float w_obj, float w_cls, float w_box,

@@ -12,7 +12,8 @@
 //           bitonic sort of the K winners in LDS, gather of their boxes / classes for the NMS, counts; re-zeroes the histogram
 //   od_nms_mask, od_nms_scan  as in od_nms (nms.hip)
 // Same total order, same exact selection, same kept indices as the three-call path (tests compare them bit for bit).
-// Compiled with -ffp-contract=off like post.hip / topk.hip / nms.hip.
+// Compiled with -ffp-contract=off like post.hip / topk.hip / nms.hip.  NC <= 76 (256 whole rows in LDS); larger class counts
+// take the streamed kernels of detect_wide.hip through the same entry points.
 #include <string.h>
 
 #include "post_common.h"
@@ -23,12 +24,6 @@ typedef unsigned long long u64;
 constexpr int NB = OD_TOPK_NB;
 constexpr int DT_ROWS = 256;      // priors per workgroup (one thread each)
 constexpr int DT_CAND_CAP = 1024; // d0-bin candidates a workgroup compacts in LDS before falling back to global atomics
-
-// First radix digit.  Confidences are products of two probabilities, so a candidate's bit pattern lies in (bits(thr),
-// bits(1.0)]: the 4096 bins are spread over THAT range (dbase = bits(thr), dshift = the smallest shift that fits it) instead of
-// over all exponents -- at thr = 0.01 a bin is 2^14 ulps (0.2 % of the value) wide instead of 2^19 (4.4 %): the threshold bin
-// holds 22x fewer scores, and far fewer priors have to be looked at again in pass 2.
-__device__ __forceinline__ int od_digit0(unsigned sb, unsigned dbase, int dshift) { return (int)((sb - dbase) >> dshift); }
 
 // grid (ceil(P / 256), B).  LDS: rows [256][C] f32 (confidences are computed in place over the class logits) + hist[4096].
 __global__ __launch_bounds__(256) void od_detect_pass1(const float* __restrict__ pred, const float* __restrict__ priors,
@@ -84,53 +79,6 @@ __global__ __launch_bounds__(256) void od_detect_pass1(const float* __restrict__
       dst[i] = rows[r * C + 2 + c];
     }
   }
-}
-
-// Block-wide (256 threads) search of a 4096-bin GLOBAL histogram for the bin where the count of elements in higher bins first
-// reaches >= krem: every thread owns 16 consecutive bins in registers (one round of loads), a suffix scan over the 256
-// partial sums (wave shuffles + four partials through LDS) finds the owner, the owner walks its 16 bins.
-__device__ __forceinline__ void od_find_digit_256(const int* __restrict__ gh, int krem, int* sh /* [8] LDS */, int* d_out,
-                                                  int* above_out) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int v[16];
-  int tot = 0;
-  const int4* g4 = (const int4*)(gh + tid * 16);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int4 t = g4[q];
-    v[4 * q] = t.x, v[4 * q + 1] = t.y, v[4 * q + 2] = t.z, v[4 * q + 3] = t.w;
-    tot += t.x + t.y + t.z + t.w;
-  }
-  int suf = tot;  // inclusive suffix sum over the lanes of this wave
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_down(suf, off);
-    if (lane + off < 64) suf += o;
-  }
-  if (lane == 0) sh[wv] = suf;  // the wave's total
-  if (tid == 0) {
-    sh[4] = -1;
-    sh[5] = 0;
-  }
-  __syncthreads();
-  int higher_waves = 0;
-  for (int w = wv + 1; w < 4; ++w) higher_waves += sh[w];
-  const int incl = suf + higher_waves, higher = incl - tot;  // elements in the bins of this thread and above / strictly above
-  if (higher < krem && incl >= krem) {  // exactly one thread
-    int run = higher;
-#pragma unroll
-    for (int q = 15; q >= 0; --q) {
-      if (run + v[q] >= krem) {
-        sh[4] = tid * 16 + q;
-        sh[5] = run;
-        break;
-      }
-      run += v[q];
-    }
-  }
-  __syncthreads();
-  *d_out = sh[4];
-  *above_out = sh[5];
 }
 
 constexpr int DT2_RPT = 4;  // priors per thread in pass 2 (1024 per workgroup)
@@ -346,6 +294,7 @@ __global__ __launch_bounds__(256) void od_gather_det_pred(const float* __restric
 struct DetLayout {
   size_t hist, state, rowmax, cand, total;
   long long cand_stride;
+  size_t nhot, hot;  // NC > 76 only (then cand / cand_stride are unused)
 };
 DetLayout det_layout(int B, int P, int NC) {
   DetLayout l;
@@ -356,6 +305,17 @@ DetLayout det_layout(int B, int P, int NC) {
   o += ((size_t)B * sizeof(TopkState) + 255) & ~(size_t)255;
   l.rowmax = o;
   o += (((size_t)B * P * sizeof(float)) + 255) & ~(size_t)255;
+  if (NC > OD_MAX_LDS_NC) {
+    l.cand = 0;
+    l.cand_stride = 0;
+    l.nhot = o;
+    o += ((size_t)B * sizeof(int) + 255) & ~(size_t)255;
+    l.hot = o;
+    o += (size_t)B * P * sizeof(HotRow);
+    l.total = o;
+    return l;
+  }
+  l.nhot = l.hot = 0;
   l.cand = o;
   l.cand_stride = (long long)P * NC;  // worst case: every score of an image sits in the d0 bin
   o += (size_t)B * (size_t)l.cand_stride * sizeof(u64);
@@ -388,8 +348,9 @@ extern "C" int od_detect(od_ctx* ctx, const float* pred, const float* priors, in
                          size_t workspace_bytes, void* nms_workspace, size_t nms_workspace_bytes, void* stream) {
   OD_REQUIRE(ctx && pred && priors && boxes && keys && counts && keep_flat && keep_count && workspace && nms_workspace,
              "od_detect: null argument");
-  OD_REQUIRE(B > 0 && B <= 65535 && P > 0 && P % 2 == 0 && NC > 0 && NC <= 76 && K > 0 && K <= 1024 && max_det > 0,
-             "od_detect: bad dims (P even, NC <= 76, K <= 1024)");
+  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "od_detect: NC = %d outside the supported class counts 1..%d", NC, OD_MAX_NC);
+  OD_REQUIRE(B > 0 && B <= 65535 && P > 0 && P % 2 == 0 && K > 0 && K <= 1024 && max_det > 0,
+             "od_detect: bad dims (P even, K <= 1024)");
   OD_REQUIRE((long long)P * NC < (1LL << 31), "od_detect: P * NC must fit 31 bits");
   OD_REQUIRE(conf_threshold >= 0.f, "od_detect: conf_threshold must be >= 0 (scores are probabilities)");
   const DetLayout l = det_layout(B, P, NC);
@@ -414,6 +375,19 @@ extern "C" int od_detect(od_ctx* ctx, const float* pred, const float* priors, in
   int dshift = 0;
   while (((0x3F800000u - dbase) >> dshift) >= (unsigned)NB) ++dshift;
   const dim3 grid((unsigned)od_ceil_div(P, DT_ROWS), (unsigned)B);
+  const dim3 grid2((unsigned)od_ceil_div(P, DT_ROWS * DT2_RPT), (unsigned)B);
+  u64* skeys;
+  f32x4* sbox;
+  int* scls;
+  int KP;
+  od_nms_sorted_buffers(nms_workspace, B, K, &skeys, &sbox, &scls, &KP);
+  if (NC > OD_MAX_LDS_NC) {
+    if (int rc = od_detect_wide_launch(pred, priors, B, P, NC, loc_scale, clip, conf_threshold, dbase, dshift, K, KP, boxes,
+                                       conf, (u64*)keys, counts, hist, st, rowmax, (int*)(ws + l.nhot),
+                                       (HotRow*)(ws + l.hot), skeys, sbox, scls, s))
+      return rc;
+    return od_nms_mask_scan_launch(ctx, nms_workspace, counts, B, K, iou_threshold, strict, max_det, keep_flat, keep_count, s);
+  }
   const size_t lds1 = (size_t)DT_ROWS * C * 4 + (size_t)NB * 4;
   if (int rc = od_ensure_lds(ctx, (const void*)&od_detect_pass1, lds1)) return rc;
   hipLaunchKernelGGL(od_detect_pass1, grid, dim3(256), lds1, s, pred, priors, boxes, rowmax, conf, hist, st, P, NC, loc_scale,
@@ -421,15 +395,9 @@ extern "C" int od_detect(od_ctx* ctx, const float* pred, const float* priors, in
   OD_CHECK_LAUNCH();
   const size_t lds2 = (size_t)DT_ROWS * C * 4 + ((size_t)K + DT_CAND_CAP) * 8;
   if (int rc = od_ensure_lds(ctx, (const void*)&od_detect_pass2, lds2)) return rc;
-  const dim3 grid2((unsigned)od_ceil_div(P, DT_ROWS * DT2_RPT), (unsigned)B);
   hipLaunchKernelGGL(od_detect_pass2, grid2, dim3(256), lds2, s, pred, rowmax, hist, st, (u64*)keys, cand, P, NC, K,
                      conf_threshold, l.cand_stride, dbase, dshift);
   OD_CHECK_LAUNCH();
-  u64* skeys;
-  f32x4* sbox;
-  int* scls;
-  int KP;
-  od_nms_sorted_buffers(nms_workspace, B, K, &skeys, &sbox, &scls, &KP);
   hipLaunchKernelGGL(od_detect_refine_sort, dim3(B), dim3(1024), 0, s, boxes, st, (u64*)keys, cand, hist, counts, P, NC, K, KP,
                      l.cand_stride, skeys, sbox, scls, dbase, dshift);
   OD_CHECK_LAUNCH();
@@ -439,7 +407,12 @@ extern "C" int od_detect(od_ctx* ctx, const float* pred, const float* priors, in
 extern "C" int od_gather_detections_pred(od_ctx* ctx, const float* pred, const float* boxes, const int32_t* keep_flat,
                                          const int32_t* keep_count, int B, int P, int NC, int max_det, float* out, void* stream) {
   OD_REQUIRE(ctx && pred && boxes && keep_flat && keep_count && out, "od_gather_detections_pred: null argument");
-  OD_REQUIRE(B > 0 && P > 0 && NC > 0 && NC <= 76 && max_det > 0, "od_gather_detections_pred: bad dims");
+  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "od_gather_detections_pred: NC = %d outside the supported class counts 1..%d", NC,
+             OD_MAX_NC);
+  OD_REQUIRE(B > 0 && P > 0 && max_det > 0, "od_gather_detections_pred: bad dims");
+  if (NC > OD_MAX_LDS_NC) {
+    return od_gather_det_pred_wide_launch(pred, boxes, keep_flat, keep_count, B, P, NC, max_det, out, (hipStream_t)stream);
+  }
   hipLaunchKernelGGL(od_gather_det_pred, dim3(B), dim3(256), (size_t)256 * (NC + 6) * 4, (hipStream_t)stream, pred, boxes,
                      keep_flat, keep_count, P, NC, max_det, out);
   OD_CHECK_LAUNCH();

@@ -52,6 +52,42 @@ __global__ __launch_bounds__(256) void od_head_post(const float* __restrict__ pr
   }
 }
 
+// od_head_post for NC > 76: the class columns of the workgroup's rows streamed through an LDS tile (od_wide_stats, then a
+// third sweep that writes the confidences over the tile and out as rows of NC)
+__global__ __launch_bounds__(256) void od_head_post_wide(const float* __restrict__ pred, const float* __restrict__ priors,
+                                                         float* __restrict__ conf, float* __restrict__ boxes, long long rows,
+                                                         int P, int NC, float loc_scale, int clip) {
+  __shared__ float tile[PP_ROWS * OD_WIDE_LD];
+  const int C = NC + 6, tid = threadIdx.x;
+  const long long r0 = (long long)blockIdx.x * PP_ROWS;
+  const int nrows = (int)((rows - r0) < PP_ROWS ? (rows - r0) : PP_ROWS);
+  const float* src = pred + r0 * C;
+  const OdRowStats rs = od_wide_stats(src, C, NC, nrows, tile);
+  for (int c0 = 0; c0 < NC; c0 += OD_WIDE_CW) {
+    const int w = min(OD_WIDE_CW, NC - c0);
+    od_wide_stage(src, C, nrows, 2 + c0, w, tile);
+    __syncthreads();
+    if (tid < nrows) {
+      float* t = tile + tid * OD_WIDE_LD;
+      for (int c = 0; c < w; ++c) t[c] = od_wide_conf(t[c], rs);
+    }
+    __syncthreads();
+    for (int i = tid; i < nrows * OD_WIDE_CW; i += 256) {
+      const int r = i / OD_WIDE_CW, c = i % OD_WIDE_CW;
+      if (c < w) conf[(r0 + r) * NC + c0 + c] = tile[r * OD_WIDE_LD + c];
+    }
+    __syncthreads();
+  }
+  if (tid < nrows) {
+    const float* row = src + (long long)tid * C;
+    const long long r = r0 + tid;
+    const int p = (int)(r % P);
+    const f32x4 loc = {row[2 + NC], row[3 + NC], row[4 + NC], row[5 + NC]};
+    const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
+    *(f32x4*)(boxes + r * 4) = decode_one(loc, pr, loc_scale, clip);
+  }
+}
+
 __global__ __launch_bounds__(256) void od_decode(const float* __restrict__ locs, const float* __restrict__ priors,
                                                  float* __restrict__ boxes, long long rows, int P, float loc_scale,
                                                  int clip) {
@@ -126,8 +162,16 @@ extern "C" int od_gather_detections(od_ctx* ctx, const float* conf, const float*
 extern "C" int od_head_postprocess(od_ctx* ctx, const float* pred, const float* priors, float* conf, float* boxes,
                                    int B, int P, int NC, float loc_scale, int clip, void* stream) {
   OD_REQUIRE(ctx && pred && priors && conf && boxes, "od_head_postprocess: null argument");
-  OD_REQUIRE(B > 0 && P > 0 && NC > 0 && NC <= 76, "od_head_postprocess: bad dims (NC <= 76: 256 rows x (2 NC + 6) floats of LDS)");
+  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "od_head_postprocess: NC = %d outside the supported class counts 1..%d", NC,
+             OD_MAX_NC);
+  OD_REQUIRE(B > 0 && P > 0, "od_head_postprocess: bad dims");
   const long long rows = (long long)B * P;
+  if (NC > OD_MAX_LDS_NC) {  // 256 rows x (2 NC + 6) floats no longer fit the LDS: stream the class columns
+    hipLaunchKernelGGL(od_head_post_wide, dim3((unsigned)((rows + PP_ROWS - 1) / PP_ROWS)), dim3(256), 0, (hipStream_t)stream,
+                       pred, priors, conf, boxes, rows, P, NC, loc_scale, clip);
+    OD_CHECK_LAUNCH();
+    return OD_OK;
+  }
   const size_t lds = (size_t)PP_ROWS * (NC + 6 + NC) * sizeof(float);
   if (int rc = od_ensure_lds(ctx, (const void*)&od_head_post, lds)) return rc;
   const unsigned grid = (unsigned)((rows + PP_ROWS - 1) / PP_ROWS);

@@ -1,4 +1,4 @@
-// Shared by post.hip (K5/K6), topk.hip (K7) and detect.hip (the fused product path): the confidence arithmetic and the
+// Shared by post.hip (K5/K6), topk.hip (K7), detect.hip and detect_wide.hip (the fused product path): the confidence arithmetic and the
 // radix-select helpers.  Every TU that includes this is compiled with -ffp-contract=off, so the same source is the same
 // f32 op sequence everywhere (and the one of oracle/postprocess.py): confidences are bit-identical across kernels.
 #pragma once
@@ -28,6 +28,70 @@ __device__ __forceinline__ void od_row_conf(const float* row, int NC, float* out
   for (int c = 0; c < NC; ++c) out[c] = obj * (out[c] / s);
 }
 
+// ---- class counts beyond a [256][NC+6] LDS row block (NC > 76, up to OD_MAX_NC) ----
+// The same confidence as od_row_conf, taken apart into its three sweeps over a row (max; sum of expf in ascending c;
+// obj * (e / s)) so that the class columns can be streamed instead of held: every op happens in the same order on the
+// same inputs, and expf(l - mx) recomputed in the third sweep is the same instruction on the same operands, so the
+// confidences are bit-identical to od_row_conf's (and to oracle/postprocess.confidence).
+constexpr int OD_MAX_LDS_NC = 76;  // the largest NC whose [256][NC+6] rows (+ histogram / output) fit the LDS kernels
+constexpr int OD_MAX_NC = 1024;
+constexpr int OD_WIDE_CW = 32;              // class columns per LDS chunk
+constexpr int OD_WIDE_LD = OD_WIDE_CW + 1;  // tile row pitch: a thread walking its own row hits a different bank per lane
+
+struct OdRowStats {
+  float obj, mx, s;  // objectness probability, max class logit, sum of expf(l - mx)
+};
+
+__device__ __forceinline__ float od_wide_conf(float l, const OdRowStats& r) { return r.obj * (expf(l - r.mx) / r.s); }
+
+// sweeps 1-2 of one row read straight from memory (the few rows pass 2 / the gather look at again)
+__device__ __forceinline__ OdRowStats od_row_stats(const float* row, int NC) {
+  OdRowStats r;
+  r.obj = 1.f / (1.f + expf(row[0] - row[1]));
+  r.mx = row[2];
+  for (int c = 1; c < NC; ++c) r.mx = fmaxf(r.mx, row[2 + c]);
+  r.s = 0.f;
+  for (int c = 0; c < NC; ++c) r.s += expf(row[2 + c] - r.mx);
+  return r;
+}
+
+// tile[r][0..ncols) = src[r * C + col0 + 0..ncols) for r < nrows; 256 threads, 4-byte loads (for odd NC a row start is only
+// 4-byte aligned), 32 consecutive lanes on 32 consecutive floats of one row
+__device__ __forceinline__ void od_wide_stage(const float* __restrict__ src, int C, int nrows, int col0, int ncols,
+                                              float* tile) {
+  for (int i = threadIdx.x; i < nrows * OD_WIDE_CW; i += 256) {
+    const int r = i / OD_WIDE_CW, c = i % OD_WIDE_CW;
+    if (c < ncols) tile[r * OD_WIDE_LD + c] = src[(long long)r * C + col0 + c];
+  }
+}
+
+// sweeps 1-2 for the rows [0, nrows) of src (row stride C, <= 256 rows, one thread each), the class columns streamed
+// through `tile` [256][OD_WIDE_LD].  Thread tid < nrows gets its row's stats.  All 256 threads call it (barriers); it
+// ends on a barrier, so the caller may reuse the tile at once.
+__device__ __forceinline__ OdRowStats od_wide_stats(const float* __restrict__ src, int C, int NC, int nrows, float* tile) {
+  const int tid = threadIdx.x;
+  OdRowStats r = {0.f, 0.f, 0.f};
+  const float* row = src + (long long)tid * C;
+  if (tid < nrows) r.obj = 1.f / (1.f + expf(row[0] - row[1]));
+  for (int sweep = 0; sweep < 2; ++sweep) {
+    for (int c0 = 0; c0 < NC; c0 += OD_WIDE_CW) {
+      const int w = min(OD_WIDE_CW, NC - c0);
+      od_wide_stage(src, C, nrows, 2 + c0, w, tile);
+      __syncthreads();
+      if (tid < nrows) {
+        const float* t = tile + tid * OD_WIDE_LD;
+        if (sweep == 0) {
+          for (int c = 0; c < w; ++c) r.mx = (c0 + c == 0) ? t[c] : fmaxf(r.mx, t[c]);
+        } else {
+          for (int c = 0; c < w; ++c) r.s += expf(t[c] - r.mx);
+        }
+      }
+      __syncthreads();
+    }
+  }
+  return r;
+}
+
 __device__ __forceinline__ unsigned od_score_bits(float v, float thr) {
   return v > thr ? __float_as_uint(v) : 0u;  // positive floats: bit pattern is monotone in value
 }
@@ -46,6 +110,59 @@ __device__ __forceinline__ f32x4 od_decode_one(f32x4 loc, f32x4 pr, float loc_sc
     for (int e = 0; e < 4; ++e) o[e] = fminf(fmaxf(o[e], 0.f), 1.f);
   }
   return o;
+}
+
+// First radix digit.  Confidences are products of two probabilities, so a candidate's bit pattern lies in (bits(thr),
+// bits(1.0)]: the 4096 bins are spread over THAT range (dbase = bits(thr), dshift = the smallest shift that fits it) instead of
+// over all exponents -- at thr = 0.01 a bin is 2^14 ulps (0.2 % of the value) wide instead of 2^19 (4.4 %): the threshold bin
+// holds 22x fewer scores, and far fewer priors have to be looked at again in pass 2.
+__device__ __forceinline__ int od_digit0(unsigned sb, unsigned dbase, int dshift) { return (int)((sb - dbase) >> dshift); }
+
+// Block-wide (256 threads) search of a 4096-bin GLOBAL histogram for the bin where the count of elements in higher bins first
+// reaches >= krem: every thread owns 16 consecutive bins in registers (one round of loads), a suffix scan over the 256
+// partial sums (wave shuffles + four partials through LDS) finds the owner, the owner walks its 16 bins.
+__device__ __forceinline__ void od_find_digit_256(const int* __restrict__ gh, int krem, int* sh /* [8] LDS */, int* d_out,
+                                                  int* above_out) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int v[16];
+  int tot = 0;
+  const int4* g4 = (const int4*)(gh + tid * 16);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int4 t = g4[q];
+    v[4 * q] = t.x, v[4 * q + 1] = t.y, v[4 * q + 2] = t.z, v[4 * q + 3] = t.w;
+    tot += t.x + t.y + t.z + t.w;
+  }
+  int suf = tot;  // inclusive suffix sum over the lanes of this wave
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int o = __shfl_down(suf, off);
+    if (lane + off < 64) suf += o;
+  }
+  if (lane == 0) sh[wv] = suf;  // the wave's total
+  if (tid == 0) {
+    sh[4] = -1;
+    sh[5] = 0;
+  }
+  __syncthreads();
+  int higher_waves = 0;
+  for (int w = wv + 1; w < 4; ++w) higher_waves += sh[w];
+  const int incl = suf + higher_waves, higher = incl - tot;  // elements in the bins of this thread and above / strictly above
+  if (higher < krem && incl >= krem) {  // exactly one thread
+    int run = higher;
+#pragma unroll
+    for (int q = 15; q >= 0; --q) {
+      if (run + v[q] >= krem) {
+        sh[4] = tid * 16 + q;
+        sh[5] = run;
+        break;
+      }
+      run += v[q];
+    }
+  }
+  __syncthreads();
+  *d_out = sh[4];
+  *above_out = sh[5];
 }
 
 // Wave-level search of an nbins-bin histogram (in LDS or global) for the bin where the count of elements in HIGHER
@@ -90,6 +207,19 @@ __device__ __forceinline__ int od_find_digit(const int* hist, int nbins, int kre
   return digit;
 }
 
+// a prior that may hold a d0-bin candidate, as pass 2 of the NC > 76 pipeline records it (detect_wide.hip)
+struct HotRow {
+  int p;
+  OdRowStats r;
+};
+// detect_wide.hip: od_detect's pass 1 / pass 2 / refine launches for NC > 76 (the caller launches the NMS)
+int od_detect_wide_launch(const float* pred, const float* priors, int B, int P, int NC, float loc_scale, int clip, float thr,
+                          unsigned dbase, int dshift, int K, int KP, float* boxes, float* conf, unsigned long long* keys,
+                          int* counts, int* hist, TopkState* st, float* rowmax, int* nhot, HotRow* hot,
+                          unsigned long long* skeys, f32x4* sbox, int* scls, hipStream_t s);
+// detect_wide.hip: od_gather_detections_pred's launch for NC > 76
+int od_gather_det_pred_wide_launch(const float* pred, const float* boxes, const int32_t* keep_flat, const int32_t* keep_count,
+                                   int B, int P, int NC, int max_det, float* out, hipStream_t s);
 // nms.hip: the suppression-mask and greedy-scan launches of od_nms on already sorted / gathered candidates
 int od_nms_mask_scan_launch(od_ctx* ctx, void* nms_workspace, const int32_t* counts, int B, int K, float iou_threshold,
                             int strict, int max_det, int32_t* keep_flat, int32_t* keep_count, hipStream_t stream);

@@ -123,6 +123,67 @@ __global__ __launch_bounds__(256) void od_topk_partition(const float* __restrict
   for (int j = threadIdx.x; j < n_cand; j += 256) oc[j] = l_cand[j];
 }
 
+// hist0 / partition for N % 4 != 0 (odd NC with P = 2 mod 4): an image's scores start only 4-byte aligned, so one scalar load
+// per element; the same digits, lists and order otherwise
+__global__ __launch_bounds__(256) void od_topk_hist0_any(const float* __restrict__ conf, int N, float thr,
+                                                         int* __restrict__ hist, int chunk) {
+  __shared__ int lh[NB];
+  const int b = blockIdx.y;
+  for (int i = threadIdx.x; i < NB; i += 256) lh[i] = 0;
+  __syncthreads();
+  const float* src = conf + (long long)b * N;
+  const int end = min((blockIdx.x + 1) * chunk, N);
+  for (int i = blockIdx.x * chunk + threadIdx.x; i < end; i += 256) {
+    const unsigned sb = score_bits(src[i], thr);
+    if (sb) atomicAdd(&lh[(sb >> 19) & (NB - 1)], 1);
+  }
+  __syncthreads();
+  int* gh = hist + (long long)b * NB;
+  for (int i = threadIdx.x; i < NB; i += 256)
+    if (lh[i]) atomicAdd(&gh[i], lh[i]);
+}
+
+__global__ __launch_bounds__(256) void od_topk_partition_any(const float* __restrict__ conf, int N, float thr,
+                                                             TopkState* __restrict__ st, unsigned long long* __restrict__ keys,
+                                                             unsigned* __restrict__ cand, int K, int chunk) {
+  extern __shared__ __attribute__((aligned(16))) unsigned sm_u[];
+  unsigned* l_out = sm_u;       // [K]
+  unsigned* l_cand = sm_u + K;  // [chunk]
+  __shared__ int n_out, n_cand, base_out, base_cand;
+  const int b = blockIdx.y;
+  const int d0 = st[b].d0;
+  const float* src = conf + (long long)b * N;
+  if (threadIdx.x == 0) {
+    n_out = 0;
+    n_cand = 0;
+  }
+  __syncthreads();
+  const int end = min((blockIdx.x + 1) * chunk, N);
+  for (int i = blockIdx.x * chunk + threadIdx.x; i < end; i += 256) {
+    const unsigned sb = score_bits(src[i], thr);
+    if (!sb) continue;
+    const int dg = (int)((sb >> 19) & (NB - 1));
+    if (dg > d0) {
+      l_out[atomicAdd(&n_out, 1)] = (unsigned)i;
+    } else if (dg == d0) {
+      l_cand[atomicAdd(&n_cand, 1)] = (unsigned)i;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    base_out = n_out ? atomicAdd(&st[b].nout, n_out) : 0;
+    base_cand = n_cand ? atomicAdd(&st[b].ncand, n_cand) : 0;
+  }
+  __syncthreads();
+  unsigned long long* ok = keys + (long long)b * K + base_out;
+  for (int j = threadIdx.x; j < n_out; j += 256) {
+    const unsigned f = l_out[j];
+    ok[j] = ((unsigned long long)__float_as_uint(src[f]) << 32) | (unsigned long long)(0xFFFFFFFFu - f);
+  }
+  unsigned* oc = cand + (long long)b * N + base_cand;
+  for (int j = threadIdx.x; j < n_cand; j += 256) oc[j] = l_cand[j];
+}
+
 // Refine inside the d0 bin.  Remaining key bits, most significant first: score[18:8], score[7:0], ~flat[31:21],
 // ~flat[20:10], ~flat[9:0].
 __global__ __launch_bounds__(1024) void od_topk_refine(const float* __restrict__ conf, int N, TopkState* __restrict__ st,
@@ -215,7 +276,6 @@ extern "C" int od_topk_scores(od_ctx* ctx, const float* conf, int B, int N, int 
   OD_REQUIRE(ctx && conf && keys && counts && workspace, "od_topk_scores: null argument");
   OD_REQUIRE(B > 0 && B <= 65535 && N > 0 && K > 0, "od_topk_scores: bad dims");
   OD_REQUIRE(conf_threshold >= 0.f, "od_topk_scores: conf_threshold must be >= 0 (scores are probabilities)");
-  OD_REQUIRE(N % 4 == 0, "od_topk_scores: N must be a multiple of 4");
   const Layout l = ws_layout(B, N);
   if (workspace_bytes < l.total) {
     od_set_error("od_topk_scores: workspace %zu < %zu bytes", workspace_bytes, l.total);
@@ -233,7 +293,12 @@ extern "C" int od_topk_scores(od_ctx* ctx, const float* conf, int B, int N, int 
   int chunk = od_round_up(od_ceil_div(N, chunks), 1024);
   if (chunk > 8192) chunk = 8192;  // partition stages 2 x chunk u32 in LDS (<= 64 KiB)
   chunks = od_ceil_div(N, chunk);
-  hipLaunchKernelGGL(od_topk_hist0, dim3(chunks, B), dim3(256), 0, s, conf, N, conf_threshold, hist, chunk);
+  const bool vec = N % 4 == 0;  // 16-byte loads need every image's scores 16-byte aligned
+  if (vec) {
+    hipLaunchKernelGGL(od_topk_hist0, dim3(chunks, B), dim3(256), 0, s, conf, N, conf_threshold, hist, chunk);
+  } else {
+    hipLaunchKernelGGL(od_topk_hist0_any, dim3(chunks, B), dim3(256), 0, s, conf, N, conf_threshold, hist, chunk);
+  }
   OD_CHECK_LAUNCH();
   hipLaunchKernelGGL(od_topk_select0, dim3(B), dim3(64), 0, s, hist, st, K);
   OD_CHECK_LAUNCH();
@@ -242,9 +307,15 @@ extern "C" int od_topk_scores(od_ctx* ctx, const float* conf, int B, int N, int 
   const int pchunks = od_ceil_div(N, pchunk);
   const size_t plds = ((size_t)K + pchunk) * sizeof(unsigned);
   OD_REQUIRE(plds <= 160 * 1024, "od_topk_scores: K too large for the partition pass (K + 4096 u32 of LDS)");
-  if (int rc = od_ensure_lds(ctx, (const void*)&od_topk_partition, plds)) return rc;
-  hipLaunchKernelGGL(od_topk_partition, dim3(pchunks, B), dim3(256), plds, s, conf, N, conf_threshold, st,
-                     (unsigned long long*)keys, cand, K, pchunk);
+  if (vec) {
+    if (int rc = od_ensure_lds(ctx, (const void*)&od_topk_partition, plds)) return rc;
+    hipLaunchKernelGGL(od_topk_partition, dim3(pchunks, B), dim3(256), plds, s, conf, N, conf_threshold, st,
+                       (unsigned long long*)keys, cand, K, pchunk);
+  } else {
+    if (int rc = od_ensure_lds(ctx, (const void*)&od_topk_partition_any, plds)) return rc;
+    hipLaunchKernelGGL(od_topk_partition_any, dim3(pchunks, B), dim3(256), plds, s, conf, N, conf_threshold, st,
+                       (unsigned long long*)keys, cand, K, pchunk);
+  }
   OD_CHECK_LAUNCH();
   hipLaunchKernelGGL(od_topk_refine, dim3(B), dim3(1024), 0, s, conf, N, st, (unsigned long long*)keys, cand, K);
   OD_CHECK_LAUNCH();

@@ -637,7 +637,11 @@ extern "C" int od_bn_bwd(od_ctx* ctx, const void* z, const void* dy, const float
                          float* dgamma, float* dbeta, void* dz, void* workspace, size_t workspace_bytes, void* stream) {
   OD_REQUIRE(ctx && z && dy && scale && shift && dz && dgamma && dbeta && workspace, "od_bn_bwd: null argument");
   OD_REQUIRE(!bn || (mean && rstd), "od_bn_bwd: bn needs mean/rstd");
-  OD_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= 2048, "od_bn_bwd: C must be a multiple of 8, <= 2048");
+  OD_REQUIRE(M > 0 && C > 0 && C % 8 == 0, "od_bn_bwd: C must be a multiple of 8");
+  // od_bn_bwd_apply_k covers 2048 channels.  Wider layers are taken only without BatchNorm and activation -- the prediction
+  // conv of a many-class head (Cout = 8 * (NC + 6)), whose dz is dy itself: the reductions loop over any C, the apply is a copy
+  const bool wide = C > 2048;
+  OD_REQUIRE(!wide || (!bn && act == OD_ACT_LINEAR), "od_bn_bwd: C > 2048 only without BatchNorm and activation");
   const int rw = rows_per_wg_reduce(M, C), rw_apply = rows_per_wg(M, C);
   const int nblocks = (int)((M + rw - 1) / rw);
   const size_t need = od_bn_workspace_bytes(M, C) + 2 * (size_t)C * sizeof(float);
@@ -657,6 +661,10 @@ extern "C" int od_bn_bwd(od_ctx* ctx, const void* z, const void* dy, const float
                      (const float*)nullptr, (const float*)nullptr, dgamma, dbeta, sums, sums + C, (float*)nullptr,
                      (float*)nullptr, 0.f);
   OD_CHECK_LAUNCH();
+  if (wide) {  // linear, no BatchNorm: dz = (f16)(dy * 1) = dy
+    if (dz != dy) OD_CHECK_HIP(hipMemcpyAsync(dz, dy, (size_t)M * C * sizeof(f16), hipMemcpyDeviceToDevice, s));
+    return OD_OK;
+  }
   OD_ACT_SWITCH(act, hipLaunchKernelGGL(od_bn_bwd_apply_k<A>, dim3((unsigned)((M + rw_apply - 1) / rw_apply)), dim3(256), 0, s,
                                         (const f16*)z, (const f16*)dy, scale, shift, bn ? mean : shift, bn ? rstd : scale,
                                         sums, sums + C, (f16*)dz, M, C, 1.f / (float)M, act, alpha, bn, rw_apply));

@@ -17,6 +17,7 @@ IOU_THRESHOLD = 0.45
 PRE_NMS_TOPK = 1024
 MAX_DETECTIONS = 200
 LOC_SCALE = 0.1
+MAX_CLASSES = 1024  # od_detect / od_head_postprocess / od_loss_fwd_bwd: 1 <= NC <= 1024
 
 
 class Postprocessor:
@@ -26,6 +27,8 @@ class Postprocessor:
         self.lib = self.ctx.lib
         dev = torch.device(device)
         self.B, self.P, self.NC = int(batch_size), int(num_priors), int(num_classes)
+        if not 1 <= self.NC <= MAX_CLASSES:
+            raise _lib.OdError(f"Postprocessor: num_classes = {self.NC} outside the supported class counts 1..{MAX_CLASSES}")
         self.K, self.max_det = int(topk), int(max_det)
         self.iou_threshold, self.strict, self.loc_scale = float(iou_threshold), int(bool(strict_nms)), float(loc_scale)
         self.priors = torch.as_tensor(priors, dtype=torch.float32).contiguous().to(dev)
@@ -36,7 +39,7 @@ class Postprocessor:
         self._conf = None
         self._pred = None
         self._conf_valid = False
-        self.fused = P % 2 == 0 and NC <= 76
+        self.fused = P % 2 == 0  # NC > 76 runs od_detect's streamed kernels (same entry point, same results)
         self.boxes = torch.empty((B, P, 4), dtype=torch.float32, device=dev)
         self.keys = torch.empty((B, K), dtype=torch.int64, device=dev)  # u64 payload
         self.counts = torch.empty((B,), dtype=torch.int32, device=dev)

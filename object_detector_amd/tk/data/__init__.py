@@ -1,1 +1,1 @@
-from . import voc  # noqa: F401
+from . import coco, voc  # noqa: F401

@@ -108,7 +108,9 @@ class Trainer:
         self.run_stats_saved = torch.empty_like(self.run_stats)
         self.run_mean = {n: self.run_stats[o:o + self.specs[n][2]] for n, o in rviews.items()}
         self.run_var = {n: self.run_stats[o + (self.specs[n][2] + 3) // 4 * 4:][:self.specs[n][2]] for n, o in rviews.items()}
-        maxpad = 2048
+        # per-channel stand-ins (scale / shift / bias / sink) cover every layer's Cout, read in whole 256-channel pads: the
+        # prediction conv of a many-class head has Cout = 8 * (NC + 6), beyond the backbone's widths from NC = 251
+        maxpad = max(2048, max((s[2] + 255) // 256 * 256 for s in self.specs.values()))
         self.ones = torch.ones(maxpad, dtype=torch.float32, device=dev)
         self.zeros = torch.zeros(maxpad, dtype=torch.float32, device=dev)
         self.in_scale = torch.full((32,), 1.0 / 255.0, dtype=torch.float32, device=dev)
@@ -333,10 +335,11 @@ class Trainer:
                                                  _lib.OD_ACT_LINEAR, 0.0, s), "conv_first")
             elif n.pred_off is not None:
                 bias = self.view(self.params, n.name, "bias")
-                if bias.numel() < 256:  # scale/bias vectors are read in whole 256-channel pads
+                if bias.numel() % 256:  # scale/bias vectors are read in whole 256-channel pads
                     bp = getattr(self, "_bias_pad", None)
                     if bp is None:
-                        bp = self._bias_pad = torch.zeros(256, dtype=torch.float32, device=self.device)
+                        bp = self._bias_pad = torch.zeros((bias.numel() + 255) // 256 * 256, dtype=torch.float32,
+                                                          device=self.device)
                     bp[:bias.numel()].copy_(bias)
                     bias = bp
                 self._conv_raw(n, x, self.pred.data_ptr() + n.pred_off * self.C * 4, out_f32=True, obs=self.P * self.C,

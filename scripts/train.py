@@ -6,8 +6,9 @@ check_assign.py:21-22, docs/MODEL.md:33-52, per-layer learning rates docs/MODEL.
 voc_validate.py then logs (README.md:17,22).  This is that loop on MI355X: od_gen generator (pixels augmented on the
 device) -> Trainer.step (every tensor op a libodhip.so kernel) -> weights.save.
 
-Data: a VOCdevkit directory (--vocdevkit-dir, image set --image-set of VOC<year>), or --shapes N generated images
-(_common.shapes_dataset; VOC07+12 cannot be fetched offline).  Under torch.distributed.run every rank trains on its shard of
+Data: a VOCdevkit directory (--vocdevkit-dir, image set --image-set of VOC<year>), a COCO-format dataset (--coco-json +
+--coco-image-dir: the network gets one class per category, and the class names travel in the weights' __meta__), or
+--shapes N generated images (_common.shapes_dataset; VOC07+12 cannot be fetched offline).  Under torch.distributed.run every rank trains on its shard of
 the images and the gradients are all-reduced through RCCL (od_allreduce)."""
 import argparse
 import pathlib
@@ -26,6 +27,9 @@ def _main():
     p.add_argument("--image-set", default="trainval")
     p.add_argument("--year", default=2007, type=int)
     p.add_argument("--shapes", default=0, type=int, help="N generated images instead of a VOC directory")
+    p.add_argument("--coco-json", default=None, type=pathlib.Path,
+                   help="COCO-format instances JSON instead of a VOC directory (with --coco-image-dir)")
+    p.add_argument("--coco-image-dir", default=None, type=pathlib.Path, help="the images --coco-json names")
     p.add_argument("--result-dir", default=pathlib.Path("results"), type=pathlib.Path)
     p.add_argument("--out", default=None, type=pathlib.Path, help="weights file to write (default <result-dir>/trained.npz)")
     p.add_argument("--init", default=None, type=pathlib.Path, help="start from this weights file (e.g. an imported Darknet53)")
@@ -91,8 +95,13 @@ def _run(args):
         args.lr = 0.02 * args.batch_size * world / 32.0
     if args.warmup is None:
         args.warmup = 50 if args.batch_size * world >= 32 else 200
+    class_names = None
     if args.shapes:
         X, y = _common.shapes_dataset(args.shapes, seed=args.seed)
+    elif args.coco_json is not None:
+        if args.coco_image_dir is None:
+            raise SystemExit("--coco-json needs --coco-image-dir")
+        X, y, class_names = tk.data.coco.load_od(args.coco_json, args.coco_image_dir)
     else:
         X, y = tk.data.voc.load_set(args.vocdevkit_dir, args.year, args.image_set)
     y_all = y
@@ -105,7 +114,8 @@ def _run(args):
     if args.init is not None:
         params, _meta = W.load(args.init)
     else:
-        params = init_for_training(W.random_init(seed=2 + args.seed))
+        nc = 20 if class_names is None else len(class_names)
+        params = init_for_training(W.random_init(seed=2 + args.seed, num_classes=nc))
     comm = None
     if world > 1 and torch.distributed.get_backend() == "nccl":
         comm, _ = init_comm(Context.get(dev))
@@ -136,7 +146,10 @@ def _run(args):
     if tk.dl.is_main_process():
         out = args.out or (args.result_dir / "trained.npz")
         out.parent.mkdir(parents=True, exist_ok=True)
-        W.save(out, tr.export_params(), meta={"prior_wh": np.asarray(tr.pb.prior_wh), "loss_history": hist[:, 3]})
+        meta = {"prior_wh": np.asarray(tr.pb.prior_wh), "loss_history": hist[:, 3]}
+        if class_names is not None:
+            meta["class_names"] = np.asarray(class_names)
+        W.save(out, tr.export_params(), meta=meta)
         log.info(f"weights written to {out}")
 
 
