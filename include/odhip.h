@@ -420,6 +420,46 @@ int od_aug_params_bytes(void);
 int od_augment_batch(od_ctx* ctx, const uint8_t* src, const void* params, uint8_t* out, int B, int H, int W,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K15: image decode + resize into the network input for ObjectDetector(image_decode="device") (reference
+ * voc_validate.py:27: predict() on image files).  The output equals the host path (PIL decode + BILINEAR resize) byte
+ * for byte.  One od_img_desc per image; the host packs every image's data into one `blob` (device copy) at the *_off
+ * byte offsets (16-byte aligned); od_img_workspace_plan lays the per-image workspace out (the *_ws offsets) and returns
+ * its size.  out = uint8 [B,H,W,3]: image b's resized out_w x out_h rectangle at the top-left, zeros elsewhere.
+ *   OD_IMG_JPEG  baseline Huffman JPEG: stream = unstuffed entropy-coded bytes; sub = OD_JPEG_SUB_INTS int32 per
+ *                subsequence of the parallel Huffman decode (start bit, end bit, restart-interval end bit, interval's
+ *                first block, end block, first-of-interval flag, 0, 0); huff = 6 decode tables of OD_JPEG_HUFF_INTS
+ *                int32 (DC, AC of components 0..2; layout in object_detector_amd/jpeg.py); quant = 3 x 64 int32,
+ *                natural order.  ncomp 1 (grey) or 3 (YCbCr, luma sampling samp_h x samp_v, chroma 1x1).
+ *   OD_IMG_RGB   packed uint8 [height,width,3] at src_off.
+ * hcoef / vcoef: int32 [out_w][2 + hk] / [out_h][2 + vk] rows of (first source index, taps, weights << 22), Pillow's
+ * BILINEAR tables (object_detector_amd/resample.py); a pass whose size does not change is skipped.
+ * od_jpeg_decode_resize handles the OD_IMG_JPEG entries of the batch, od_rgb_resize the OD_IMG_RGB ones: both may run
+ * on the same batch and output.  descs_host is the host copy of descs (validated against blob_bytes / ws_bytes).
+ * ---------------------------------------------------------------------------------------------- */
+#define OD_IMG_JPEG 1
+#define OD_IMG_RGB 2
+#define OD_JPEG_HUFF_INTS 804
+#define OD_JPEG_SUB_INTS 8
+typedef struct od_img_desc {
+  int32_t kind;
+  int32_t width, height;
+  int32_t out_w, out_h;
+  int32_t ncomp, samp_h, samp_v;
+  int32_t mcux, mcuy, n_sub;
+  int32_t hk, vk;
+  int32_t pad_;
+  int64_t stream_off, stream_bytes;
+  int64_t sub_off, huff_off, quant_off, src_off, hcoef_off, vcoef_off;
+  int64_t coef_ws, plane_ws, rgb_ws, tmp_ws, state_ws;
+} od_img_desc;
+int od_img_workspace_plan(od_img_desc* descs_host, int B, long long* workspace_bytes);
+int od_jpeg_decode_resize(od_ctx* ctx, const od_img_desc* descs_host, const od_img_desc* descs, int B,
+                          const uint8_t* blob, long long blob_bytes, void* workspace, long long ws_bytes, uint8_t* out,
+                          int H, int W, void* stream);
+int od_rgb_resize(od_ctx* ctx, const od_img_desc* descs_host, const od_img_desc* descs, int B, const uint8_t* blob,
+                  long long blob_bytes, void* workspace, long long ws_bytes, uint8_t* out, int H, int W, void* stream);
+
 /* Wide (f32) add paths of the mixed-precision inference plan (ObjectDetector(precision="mixed"); replaces the Keras `Add`
  * layers of the residual blocks, reference docs/MODEL.md:15-17, where the reference's fp32 path keeps the sum in fp32):
  *   v = y (+ res);  out32 = v;  out16 = f16(v);  out_hilo[r] = [f16(v) | f16(v - f16(v))]  (row of 2*C halves)

@@ -98,7 +98,18 @@ class PlanOp(C.Structure):
                 ("wide", WideDesc)]
 
 
-STRUCTS = (ConvDesc, AugParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp)
+OD_IMG_JPEG, OD_IMG_RGB = 1, 2
+
+
+class ImgDesc(C.Structure):
+    C_NAME = "od_img_desc"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
+    _fields_ = [(n, C.c_int32) for n in ("kind", "width", "height", "out_w", "out_h", "ncomp", "samp_h", "samp_v",
+                                         "mcux", "mcuy", "n_sub", "hk", "vk", "pad_")] + \
+               [(n, C.c_int64) for n in ("stream_off", "stream_bytes", "sub_off", "huff_off", "quant_off", "src_off",
+                                         "hcoef_off", "vcoef_off", "coef_ws", "plane_ws", "rgb_ws", "tmp_ws", "state_ws")]
+
+
+STRUCTS = (ConvDesc, AugParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
 
 
 class OdError(RuntimeError):
@@ -206,6 +217,11 @@ _PROTOS = {
     "od_aug_params_bytes": (C.c_int, []),
     "od_augment_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p]),
+    "od_img_workspace_plan": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),
+    "od_jpeg_decode_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong,
+                                        C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "od_rgb_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p,
+                                C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "od_plan_create": (C.c_int, [C.c_void_p, C.POINTER(PlanOp), C.c_int, C.POINTER(C.c_void_p)]),
     "od_plan_run": (C.c_int, [C.c_void_p, C.c_void_p]),
     "od_plan_capture": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -100,6 +100,14 @@ const std::vector<StructInfo>& od_struct_table() {
         OD_F(od_aug_params, crop_y2), OD_F(od_aug_params, flip), OD_F(od_aug_params, brightness),
         OD_F(od_aug_params, contrast), OD_F(od_aug_params, saturation), OD_F(od_aug_params, n_erase),
         OD_F(od_aug_params, erase), OD_F(od_aug_params, erase_rgb)}},
+      {"od_img_desc", sizeof(od_img_desc),
+       {OD_F(od_img_desc, kind), OD_F(od_img_desc, width), OD_F(od_img_desc, height), OD_F(od_img_desc, out_w),
+        OD_F(od_img_desc, out_h), OD_F(od_img_desc, ncomp), OD_F(od_img_desc, samp_h), OD_F(od_img_desc, samp_v),
+        OD_F(od_img_desc, mcux), OD_F(od_img_desc, mcuy), OD_F(od_img_desc, n_sub), OD_F(od_img_desc, hk),
+        OD_F(od_img_desc, vk), OD_F(od_img_desc, pad_), OD_F(od_img_desc, stream_off), OD_F(od_img_desc, stream_bytes),
+        OD_F(od_img_desc, sub_off), OD_F(od_img_desc, huff_off), OD_F(od_img_desc, quant_off), OD_F(od_img_desc, src_off),
+        OD_F(od_img_desc, hcoef_off), OD_F(od_img_desc, vcoef_off), OD_F(od_img_desc, coef_ws),
+        OD_F(od_img_desc, plane_ws), OD_F(od_img_desc, rgb_ws), OD_F(od_img_desc, tmp_ws), OD_F(od_img_desc, state_ws)}},
       {"od_plan_op", sizeof(od_plan_op),
        {OD_F(od_plan_op, kind), OD_F(od_plan_op, pad_), OD_F(od_plan_op, conv), OD_F(od_plan_op, bneck),
         OD_F(od_plan_op, stem), OD_F(od_plan_op, wide)}},

@@ -140,11 +140,12 @@ class _Pipeline:
     def __init__(self, net, post, stream):
         self.net, self.post, self.stream = net, post, stream
         self.done = torch.cuda.Event()
+        self.decoder = None  # devdecode.BatchDecoder of image_decode="device", made on first use
 
 
 class ObjectDetector:
     def __init__(self, params, batch_size=16, input_size=(320, 320), keep_aspect=False, strict_nms=False,
-                 use_multi_gpu=True, device=None, prior_wh=None, n_inflight=None, precision=None):
+                 use_multi_gpu=True, device=None, prior_wh=None, n_inflight=None, precision=None, image_decode="host"):
         if device is None:  # one process per GPU; the modulo only matters when several ranks rehearse on one GPU
             device = f"cuda:{int(os.environ.get('LOCAL_RANK', 0)) % max(1, torch.cuda.device_count())}"
         if not torch.cuda.is_available():
@@ -155,6 +156,12 @@ class ObjectDetector:
         self.batch_size = int(batch_size)
         self.input_size = tuple(int(v) for v in input_size)
         self.keep_aspect, self.strict_nms, self.use_multi_gpu = bool(keep_aspect), bool(strict_nms), bool(use_multi_gpu)
+        # predict()'s image route: "host" = PIL decode + resize on the host; "device" = JPEG decode and every resize on
+        # the GPU (devdecode.py), byte-identical network input.  decode_stats counts the device route's inputs per route.
+        if image_decode not in ("host", "device"):
+            raise ValueError(f"image_decode must be 'host' or 'device', got {image_decode!r}")
+        self.image_decode = image_decode
+        self.decode_stats = {"jpeg": 0, "fallback": 0, "array": 0}
         self.params = params
         self.num_classes, _, _ = W.infer_arch(params)
         kw = {} if prior_wh is None else {"prior_wh": prior_wh}
@@ -235,6 +242,28 @@ class ObjectDetector:
         x_u8.record_stream(p.stream)
         return i
 
+    def _submit_images(self, items, conf_threshold=DEFAULT_CONF_THRESHOLD) -> int:
+        """submit() for image_decode="device": the upload and the decode / resize kernels of `items` (devdecode.prepare
+        results) write the next pipeline's Net.input on its stream, and the network runs on that input without a copy."""
+        if not self._calibrated:
+            self._pick_streams()
+        i = self._next
+        self._next = (i + 1) % len(self._pipes)
+        p = self._pipes[i]
+        if p.decoder is None:
+            from .devdecode import BatchDecoder
+            p.decoder = BatchDecoder(self.device)
+        p.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(p.stream):
+            p.decoder.run(items, p.net.input)
+            pred = p.net.forward(None)
+            p.post.run(pred, conf_threshold)
+            p.post.gather()
+            p.done.record()
+        for it in items:
+            self.decode_stats[it[0]] += 1
+        return i
+
     def _pick_streams(self):
         """One stream per pipeline, on DIFFERENT hardware queues.  HIP deals streams onto a few hardware queues (4 by
         default) in creation order, and kernels of two streams that share a queue never overlap: with 1-2 foreign streams
@@ -298,9 +327,13 @@ class ObjectDetector:
             except FileNotFoundError:
                 pass
 
-    def predict(self, X, conf_threshold=DEFAULT_CONF_THRESHOLD, verbose=0):
-        """X: sequence of image paths or uint8 arrays -> list[ObjectsPrediction] in input order."""
+    def predict(self, X, conf_threshold=DEFAULT_CONF_THRESHOLD, verbose=0, image_decode=None):
+        """X: sequence of image paths or uint8 arrays -> list[ObjectsPrediction] in input order.
+        image_decode: "host" / "device" for this call (None = the detector's setting)."""
         X = list(X)
+        route = self.image_decode if image_decode is None else image_decode
+        if route not in ("host", "device"):
+            raise ValueError(f"image_decode must be 'host' or 'device', got {route!r}")
         rank, world = dist_info(self.use_multi_gpu)
         mine = shard_indices(len(X), rank, world)
         results = {}
@@ -324,7 +357,19 @@ class ObjectDetector:
         nb = ahead + 2  # a staging buffer is busy from the start of its decode until its upload has completed
         nprocs = int(os.environ.get("OD_DECODE_PROCS", "0"))
         img_bytes = self.input_size[0] * self.input_size[1] * 3
-        if nprocs > 0:
+        if route == "device":  # pool threads read files and parse headers; the device decodes and resizes
+            from concurrent.futures import ThreadPoolExecutor
+
+            from .devdecode import prepare
+            nthreads = int(os.environ.get("OD_DECODE_THREADS", "0")) or min(8, os.cpu_count() or 1)
+            own_pool = pool = ThreadPoolExecutor(max_workers=max(1, nthreads))
+
+            def start(bi):
+                return [pool.submit(prepare, X[i], tuple(self.input_size), self.keep_aspect) for i in batches[bi]]
+
+            def finish(bi, items):
+                return self._submit_images(items, conf_threshold), [it[3] for it in items]
+        elif nprocs > 0:
             pool, shm = self._decode_procs(nprocs, nb * B * img_bytes)
             stage = np.ndarray((nb, B) + tuple(self.input_size) + (3,), np.uint8, buffer=shm.buf)
 
@@ -349,6 +394,9 @@ class ObjectDetector:
             def upload(bi):
                 return torch.from_numpy(stage[bi % nb]).to(self.device)
             own_pool = None
+
+            def finish(bi, scales):
+                return self.submit(upload(bi), conf_threshold, gather=True), scales
         else:
             from concurrent.futures import ThreadPoolExecutor
             nthreads = int(os.environ.get("OD_DECODE_THREADS", "0")) or min(8, os.cpu_count() or 1)
@@ -376,16 +424,19 @@ class ObjectDetector:
                 hb[1] = torch.cuda.Event()
                 hb[1].record(torch.cuda.current_stream(self.device))
                 return x
+
+            def finish(bi, scales):
+                return self.submit(upload(bi), conf_threshold, gather=True), scales
         try:
             futs = {bi: start(bi) for bi in range(min(ahead + 1, len(batches)))}
             for bi, idx in enumerate(batches):
                 if bi + ahead + 1 < len(batches):
                     futs[bi + ahead + 1] = start(bi + ahead + 1)
-                scales = [f.result() for f in futs.pop(bi)]
-                x = upload(bi)
+                res = [f.result() for f in futs.pop(bi)]
                 if len(pending) == len(self._pipes):  # the pipeline about to be reused still holds unread results
                     drain(pending.pop(0))
-                pending.append((self.submit(x, conf_threshold, gather=True), idx, scales))
+                ticket, scales = finish(bi, res)
+                pending.append((ticket, idx, scales))
         finally:
             if own_pool is not None:
                 own_pool.shutdown(wait=True)

@@ -24,8 +24,10 @@ def synthetic_dataset(n, size=(375, 500), seed=1):
     return np.array(X, dtype=object), np.array(y, dtype=object)
 
 
-def make_detector(tk, args, batch_size, input_size=(320, 320), **kw):
+def make_detector(tk, args, batch_size, input_size=(320, 320), device_decode=False, **kw):
+    """device_decode: JPEG decode and resize of predict()'s inputs on the GPU (image_decode="device")."""
     OD = tk.dl.od.ObjectDetector
+    kw["image_decode"] = "device" if device_decode else "host"
     if args.synthetic:
         return OD.synthetic(batch_size, input_size, **kw)
     return OD.load_voc(batch_size=batch_size, input_size=input_size, weights=args.weights, **kw)

@@ -19,6 +19,8 @@ def _main():
     p.add_argument("--weights", default=None, type=pathlib.Path)
     p.add_argument("--precision", default=None, choices=("f16", "mixed"),
                    help="mixed = every logit within 1e-3 x scale of an fp32 run (ObjectDetector(precision=...)); default f16")
+    p.add_argument("--device-decode", action="store_true",
+                   help="decode JPEGs and resize every input on the GPU (ObjectDetector(image_decode='device'))")
     p.add_argument("--synthetic", default=0, type=int)
     args = p.parse_args()
     with tk.dl.session():
@@ -33,7 +35,8 @@ def _run(args):
     else:
         X_test, y_test = tk.data.voc.load_07_test(args.vocdevkit_dir)
     od = _common.make_detector(tk, args, args.batch_size, tuple(args.input_size), keep_aspect=False, strict_nms=False,
-                               use_multi_gpu=True, precision=args.precision)
+                               use_multi_gpu=True, precision=args.precision,
+                               device_decode=args.device_decode)
     pred = od.predict(X_test, conf_threshold=0.6)
     precisions, recalls, fscores, supports = tk.ml.compute_scores(y_test, pred, iou_threshold=0.5,
                                                                   num_classes=len(tk.data.voc.CLASS_NAMES))
