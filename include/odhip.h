@@ -460,6 +460,36 @@ int od_jpeg_decode_resize(od_ctx* ctx, const od_img_desc* descs_host, const od_i
 int od_rgb_resize(od_ctx* ctx, const od_img_desc* descs_host, const od_img_desc* descs, int B, const uint8_t* blob,
                   long long blob_bytes, void* workspace, long long ws_bytes, uint8_t* out, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * K16: COCO bbox evaluation (tk.data.coco.evaluate; object_detector_amd/cocoeval.py states the protocol and packs the
+ * inputs).  pycocotools COCOeval parameters, fixed: T IoU thresholds, A area ranges, R recall thresholds, M maxDets.
+ * All f64 arithmetic is the exact op sequence of the protocol (no contraction), so results are bit-identical to numpy.
+ *
+ * od_coco_match: one wave per group g (an (image, category) pair).  GTs of g are gt[gt_off[g] .. gt_off[g+1]) in file
+ * order, detections det[det_off[g] .. det_off[g+1]) in rank order (descending score, at most 100).
+ *   gt_box f64 [n_gt][4] pixel xywh, gt_area f64 [n_gt] (the annotation's area), gt_crowd i32 [n_gt]
+ *   det_box f64 [.][4] pixel xywh; det_out i32 [.]: the slot of the detection in matched / ignored
+ *   iou_thrs f64 [T], area_rng f64 [A][2] (inclusive)
+ *   matched / ignored u64 [.]: bit t*A + a = the detection is matched / ignored under (iou_thrs[t], area_rng[a])
+ *   workspace: od_coco_match_workspace_bytes(n_gt) bytes (match state of groups too large for LDS)
+ * od_coco_accumulate: one wave per (t, k, a, m).  Category k's detections are slots cat_off[k] .. cat_off[k+1) of
+ * rank / score / matched / ignored, in accumulation order (descending score, then image, then rank).
+ *   npig i32 [K][A] (GTs not ignored), rec_thrs f64 [R], max_dets i32 [M]
+ *   precision f64 [T][R][K][A][M], recall f64 [T][K][A][M], scores f64 [T][R][K][A][M]; -1 where npig == 0
+ * ---------------------------------------------------------------------------------------------- */
+#define OD_COCO_T 10
+#define OD_COCO_A 4
+#define OD_COCO_R 101
+#define OD_COCO_M 3
+size_t od_coco_match_workspace_bytes(long long n_gt);
+int od_coco_match(od_ctx* ctx, const int32_t* gt_off, const int32_t* det_off, int n_groups, const double* gt_box,
+                  const double* gt_area, const int32_t* gt_crowd, long long n_gt, const double* det_box,
+                  const int32_t* det_out, const double* iou_thrs, const double* area_rng, uint64_t* matched,
+                  uint64_t* ignored, void* workspace, size_t workspace_bytes, void* stream);
+int od_coco_accumulate(od_ctx* ctx, const int32_t* cat_off, int K, const int32_t* rank, const double* score,
+                       const uint64_t* matched, const uint64_t* ignored, const int32_t* npig, const double* rec_thrs,
+                       const int32_t* max_dets, double* precision, double* recall, double* scores, void* stream);
+
 /* Wide (f32) add paths of the mixed-precision inference plan (ObjectDetector(precision="mixed"); replaces the Keras `Add`
  * layers of the residual blocks, reference docs/MODEL.md:15-17, where the reference's fp32 path keeps the sum in fp32):
  *   v = y (+ res);  out32 = v;  out16 = f16(v);  out_hilo[r] = [f16(v) | f16(v - f16(v))]  (row of 2*C halves)

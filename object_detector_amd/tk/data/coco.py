@@ -8,7 +8,13 @@ load_od(annotation_json, image_dir) -> (X, y, class_names):
   class_names  the category names, in ascending category id (class i = the i-th smallest id)
 Crowd regions (iscrowd = 1) are kept as `difficults`, which tk.data.voc.evaluate neither counts nor penalises.  Images
 without annotations are kept with zero objects.  An image with more than pb.GMAX objects raises ValueError naming it (the
-anchor assignment takes at most GMAX ground-truth boxes per image; nothing is truncated)."""
+anchor assignment takes at most GMAX ground-truth boxes per image; nothing is truncated).
+
+COCO bbox evaluation (object_detector_amd/cocoeval.py; the matching and accumulation run on the GPU):
+  load_gt(annotation_json) -> CocoGroundTruth         the raw boxes, areas, crowd flags and ids load_od normalises away
+  to_results(gt, y_pred, image_ids=None) -> [dict]    ObjectsPrediction lists as COCO result dicts; save_results(path, r)
+  evaluate(gt, predictions, image_ids=None) -> CocoEvaluation   stats (12,), precision / recall / scores, summary(),
+                                                      ap_per_class()"""
 from __future__ import annotations
 
 import json
@@ -16,6 +22,7 @@ import pathlib
 
 import numpy as np
 
+from ...cocoeval import CocoEvaluation, CocoGroundTruth, evaluate, load_gt, save_results, to_results  # noqa: F401
 from ...pb import GMAX, ObjectsAnnotation
 
 
