@@ -532,14 +532,16 @@ typedef struct od_plan_op {
 } od_plan_op;
 
 typedef struct od_plan od_plan;
+/* resolves every op once, here: validation and kernel selection (what od_conv2d_fwd & co. do on each call) happen at
+ * creation, and the plan keeps the ready-to-issue launches of each op; an op that is invalid fails the creation */
 int od_plan_create(od_ctx* ctx, const od_plan_op* ops, int n_ops, od_plan** out);
-int od_plan_run(od_plan* plan, void* stream);   /* eager launches */
+int od_plan_run(od_plan* plan, void* stream);   /* eager launches: issues the launches resolved at creation */
 int od_plan_capture(od_plan* plan, void* stream); /* capture into a hipGraph (stream must be capturable) */
 int od_plan_replay(od_plan* plan, void* stream);
 int od_plan_destroy(od_plan* plan);
 /* per-op timing for bench.py: runs the plan once with hipEvents around every op; ms[n_ops] */
 int od_plan_time_ops(od_plan* plan, void* stream, float* ms, int n_ops);
-/* name of the device kernel an op launches (for matching rocprofv3 rows) */
+/* name of the device kernel an op launches (its first launch, as resolved at creation; for matching rocprofv3 rows) */
 const char* od_plan_op_kernel_name(od_plan* plan, int op_index);
 
 #ifdef __cplusplus

@@ -5,6 +5,7 @@
 #include <string>
 #include <vector>
 
+#include <memory>
 #include <mutex>
 
 #include "common.h"
@@ -174,81 +175,52 @@ extern "C" int od_ctx_destroy(od_ctx* ctx) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Forward plan: the layer list of one network, launched from C++ (eager or as a replayed hipGraph).
+// Forward plan: the layer list of one network, launched from C++ (eager or as a replayed hipGraph); every op is prepared
+// once, at creation, and the plan then only issues the launch records.
 // ---------------------------------------------------------------------------------------------------------------
 struct od_plan {
-  od_ctx* ctx;
-  std::vector<od_plan_op> ops;
-  std::vector<const char*> names;
+  std::vector<od_launches> ops;
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
 };
 
-static int run_op(od_plan* pl, int i, hipStream_t s) {
-  const od_plan_op& op = pl->ops[i];
-  if (op.kind == OD_OP_CONV) return od_conv2d_fwd_impl(pl->ctx, &op.conv, s, nullptr, false);
-  if (op.kind == OD_OP_CONV_FIRST) {
-    const od_conv_desc& c = op.conv;
-    return od_conv_first_fwd(pl->ctx, (const uint8_t*)c.x, c.w, c.scale, c.bias, c.out, c.B, c.H, c.W, c.Cout, c.act,
-                             c.alpha, s);
+static int prepare_op(od_ctx* ctx, const od_plan_op& op, int i, od_launches* L) {
+  const od_conv_desc& c = op.conv;
+  switch (op.kind) {
+    case OD_OP_CONV:
+      return od_conv_prepare(ctx, &c, L);
+    case OD_OP_CONV_FIRST:
+      return od_conv_first_prepare(ctx, (const uint8_t*)c.x, c.w, c.scale, c.bias, c.out, c.B, c.H, c.W, c.Cout, c.act,
+                                   c.alpha, L);
+    case OD_OP_STEM:
+      OD_REQUIRE(od_stem_supported(op.stem.H, op.stem.W), "od_plan_create: op %d: fused stem needs H, W multiples of 32 (got %dx%d)",
+                 i, op.stem.H, op.stem.W);
+      return od_stem_prepare(ctx, &op.stem, L);
+    case OD_OP_BNECK:
+      OD_REQUIRE(od_bottleneck_supported(op.bneck.H, op.bneck.W, op.bneck.C),
+                 "od_plan_create: op %d: fused block unsupported for C=%d, %dx%d", i, op.bneck.C, op.bneck.H, op.bneck.W);
+      return od_bottleneck_prepare(ctx, &op.bneck, L);
+    case OD_OP_WIDE:
+      return od_wide_prepare(ctx, &op.wide, L);
   }
-  if (op.kind == OD_OP_BNECK) return od_bottleneck_fwd(pl->ctx, &op.bneck, s);
-  if (op.kind == OD_OP_STEM) return od_stem_fwd(pl->ctx, &op.stem, s);
-  if (op.kind == OD_OP_WIDE) return od_wide_add(pl->ctx, &op.wide, s);
-  od_set_error("od_plan: unknown op kind %d at %d", op.kind, i);
+  od_set_error("od_plan_create: unknown op kind %d at %d", op.kind, i);
   return OD_ERR_INVALID;
 }
 
 extern "C" int od_plan_create(od_ctx* ctx, const od_plan_op* ops, int n_ops, od_plan** out) {
   OD_REQUIRE(ctx && ops && n_ops > 0 && out, "od_plan_create: bad args");
-  od_plan* pl = new od_plan();
-  pl->ctx = ctx;
-  pl->ops.assign(ops, ops + n_ops);
-  pl->names.resize(n_ops, "");
-  for (int i = 0; i < n_ops; ++i) {
-    if (ops[i].kind == OD_OP_CONV) {
-      const char* nm = nullptr;
-      int rc = od_conv2d_fwd_impl(ctx, &ops[i].conv, nullptr, &nm, true);  // validates the descriptor
-      if (rc != OD_OK) {
-        delete pl;
-        return rc;
-      }
-      pl->names[i] = nm;
-    } else if (ops[i].kind == OD_OP_CONV_FIRST) {
-      pl->names[i] = od_conv_first_kernel_name();
-    } else if (ops[i].kind == OD_OP_STEM) {
-      if (!od_stem_supported(ops[i].stem.H, ops[i].stem.W)) {
-        od_set_error("od_plan_create: op %d: fused stem needs H, W multiples of 32 (got %dx%d)", i, ops[i].stem.H, ops[i].stem.W);
-        delete pl;
-        return OD_ERR_INVALID;
-      }
-      pl->names[i] = od_stem_kernel_name();
-    } else if (ops[i].kind == OD_OP_BNECK) {
-      if (!od_bottleneck_supported(ops[i].bneck.H, ops[i].bneck.W, ops[i].bneck.C)) {
-        od_set_error("od_plan_create: op %d: fused block unsupported for C=%d, %dx%d", i, ops[i].bneck.C, ops[i].bneck.H,
-                     ops[i].bneck.W);
-        delete pl;
-        return OD_ERR_INVALID;
-      }
-      pl->names[i] = od_bottleneck_kernel_name(ops[i].bneck.C);
-    } else if (ops[i].kind == OD_OP_WIDE) {
-      pl->names[i] = "od_wide_add_k";
-    } else {
-      od_set_error("od_plan_create: unknown op kind %d at %d", ops[i].kind, i);
-      delete pl;
-      return OD_ERR_INVALID;
-    }
-  }
-  *out = pl;
+  std::unique_ptr<od_plan> pl(new od_plan());
+  pl->ops.resize(n_ops);
+  for (int i = 0; i < n_ops; ++i)
+    if (int rc = prepare_op(ctx, ops[i], i, &pl->ops[i])) return rc;
+  *out = pl.release();
   return OD_OK;
 }
 
 extern "C" int od_plan_run(od_plan* pl, void* stream) {
   OD_REQUIRE(pl, "od_plan_run: null plan");
-  for (size_t i = 0; i < pl->ops.size(); ++i) {
-    int rc = run_op(pl, (int)i, (hipStream_t)stream);
-    if (rc != OD_OK) return rc;
-  }
+  for (const od_launches& L : pl->ops)
+    if (int rc = od_issue(L, (hipStream_t)stream)) return rc;
   return OD_OK;
 }
 
@@ -256,7 +228,7 @@ extern "C" int od_plan_capture(od_plan* pl, void* stream) {
   OD_REQUIRE(pl, "od_plan_capture: null plan");
   hipStream_t s = (hipStream_t)stream;
   OD_REQUIRE(s != nullptr, "od_plan_capture: needs a non-default stream");
-  // warm every kernel once outside capture (function attributes are set lazily on first launch)
+  // warm every kernel once outside capture
   int rc = od_plan_run(pl, stream);
   if (rc != OD_OK) return rc;
   OD_CHECK_HIP(hipStreamSynchronize(s));
@@ -302,7 +274,7 @@ extern "C" int od_plan_time_ops(od_plan* pl, void* stream, float* ms, int n_ops)
   OD_CHECK_HIP(hipEventRecord(ev[0], s));
   int rc = OD_OK;
   for (int i = 0; i < n_ops && rc == OD_OK; ++i) {
-    rc = run_op(pl, i, s);
+    rc = od_issue(pl->ops[i], s);
     if (rc == OD_OK) OD_CHECK_HIP(hipEventRecord(ev[i + 1], s));
   }
   if (rc == OD_OK) {
@@ -314,6 +286,6 @@ extern "C" int od_plan_time_ops(od_plan* pl, void* stream, float* ms, int n_ops)
 }
 
 extern "C" const char* od_plan_op_kernel_name(od_plan* pl, int i) {
-  if (!pl || i < 0 || i >= (int)pl->names.size()) return "";
-  return pl->names[i];
+  if (!pl || i < 0 || i >= (int)pl->ops.size()) return "";
+  return pl->ops[i].l[0].name;
 }

@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <unordered_map>
 
@@ -58,12 +59,69 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 static inline int od_ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int od_round_up(int a, int b) { return od_ceil_div(a, b) * b; }
 
-// conv launcher (conv_mfma.hip); kernel_name receives the device symbol launched (may be NULL)
-int od_conv2d_fwd_impl(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name,
-                       bool dry_run);
-const char* od_conv_first_kernel_name();
-const char* od_bottleneck_kernel_name(int C);
-const char* od_stem_kernel_name();
+// ---- launch records.  The forward entry points of the conv families and od_wide_add PREPARE an op (validate it, select
+//      the kernel, fill its parameter struct, raise its LDS limit) into launch records, then issue them.  A forward plan
+//      prepares each op once, at od_plan_create.
+struct od_launch {
+  const char* name;                                      // the kernel launched (od_plan_op_kernel_name)
+  int (*issue)(const od_launch& l, hipStream_t stream);  // the family's launch call
+  const void* fn;
+  dim3 grid, block;
+  size_t lds;
+  alignas(16) unsigned char args[352];  // the kernel's arguments (their structs are private to the family's source file)
+  template <class T> const T& arg() const { return *reinterpret_cast<const T*>(args); }
+};
+struct od_launches {  // one op: six cover a grouped conv issued segment by segment, each with a split-K finish
+  int n = 0;
+  od_launch l[6];
+};
+
+template <class T>
+int od_add_launch(od_launches* L, od_launch l, const T& args) {
+  static_assert(sizeof(T) <= sizeof(l.args) && alignof(T) <= 16, "kernel arguments do not fit an od_launch");
+  OD_REQUIRE(L->n < 6, "%s: more than 6 launches in one op", l.name);
+  memcpy(l.args, &args, sizeof(T));
+  L->l[L->n++] = l;
+  return OD_OK;
+}
+static inline int od_issue(const od_launches& L, hipStream_t stream) {
+  for (int i = 0; i < L.n; ++i)
+    if (int rc = L.l[i].issue(L.l[i], stream)) return rc;
+  return OD_OK;
+}
+
+// the direct entry points: prepare(args..., &L), then issue on the caller's stream
+template <class F, class... A>
+int od_prepare_issue(void* stream, F prepare, A... args) {
+  od_launches L;
+  if (int rc = prepare(args..., &L)) return rc;
+  return od_issue(L, (hipStream_t)stream);
+}
+// issue functions of the kernels that take one parameter struct, and of those that take (parameter struct, int)
+static inline int od_issue_kp(const od_launch& l, hipStream_t stream) {
+  void* args[] = {(void*)l.args};
+  OD_CHECK_HIP(hipLaunchKernel(l.fn, l.grid, l.block, args, l.lds, stream));
+  return OD_OK;
+}
+template <class KP>
+struct od_kp_int {
+  KP p;
+  int n;
+};
+template <class KP>
+int od_issue_kp_int(const od_launch& l, hipStream_t stream) {
+  const od_kp_int<KP>& a = l.arg<od_kp_int<KP>>();
+  void* args[] = {(void*)&a.p, (void*)&a.n};
+  OD_CHECK_HIP(hipLaunchKernel(l.fn, l.grid, l.block, args, l.lds, stream));
+  return OD_OK;
+}
+
+int od_conv_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L);
+int od_conv_first_prepare(od_ctx* ctx, const uint8_t* x, const void* w, const float* scale, const float* bias, void* out,
+                          int B, int H, int W, int Cout, int act, float alpha, od_launches* L);
+int od_bottleneck_prepare(od_ctx* ctx, const od_bneck_desc* d, od_launches* L);
+int od_stem_prepare(od_ctx* ctx, const od_stem_desc* d, od_launches* L);
+int od_wide_prepare(od_ctx* ctx, const od_wide_desc* d, od_launches* L);
 
 // weight-gradient launcher (conv_wgrad.hip): per-split f32 slabs [split][Cout][k*k*Cin]; *nsplit receives the split count
 int od_wgrad_slabs_impl(od_ctx* ctx, const void* x, const void* dz, float* slabs, int B, int H, int W, int Cin, int Cout,

@@ -437,9 +437,7 @@ extern "C" int od_bottleneck_supported(int H, int W, int C) {
   return (C == 64 || C == 128) && H > 0 && W > 0 && (H % 16) == 0 && (W % 16) == 0;
 }
 
-const char* od_bottleneck_kernel_name(int C) { return C == 64 ? "od_bneck<64, 1>" : "od_bneck<128, 1>"; }
-
-extern "C" int od_bottleneck_fwd(od_ctx* ctx, const od_bneck_desc* d, void* stream) {
+int od_bottleneck_prepare(od_ctx* ctx, const od_bneck_desc* d, od_launches* L) {
   OD_REQUIRE(ctx && d, "od_bottleneck_fwd: null ctx/desc");
   OD_REQUIRE(d->x && d->w1 && d->scale1 && d->bias1 && d->w3 && d->scale3 && d->bias3 && d->out,
              "od_bottleneck_fwd: null tensor");
@@ -467,23 +465,24 @@ extern "C" int od_bottleneck_fwd(od_ctx* ctx, const od_bneck_desc* d, void* stre
   p.alpha = d->alpha;
   p.tiles_x = d->W / 16;
   p.tiles_y = d->H / 16;
-  const void* fn;
-  if (d->C == 64) {
-    fn = d->act == OD_ACT_LEAKY ? (const void*)&od_bneck<64, OD_ACT_LEAKY>
-         : d->act == OD_ACT_ELU ? (const void*)&od_bneck<64, OD_ACT_ELU>
-                                : (const void*)&od_bneck<64, OD_ACT_LINEAR>;
-  } else {
-    fn = d->act == OD_ACT_LEAKY ? (const void*)&od_bneck<128, OD_ACT_LEAKY>
-         : d->act == OD_ACT_ELU ? (const void*)&od_bneck<128, OD_ACT_ELU>
-                                : (const void*)&od_bneck<128, OD_ACT_LINEAR>;
-  }
+  static_assert(OD_ACT_LINEAR == 0 && OD_ACT_LEAKY == 1 && OD_ACT_ELU == 2, "kernel table order");
+#define OD_BN(C, ACT) {(const void*)&od_bneck<C, ACT>, "od_bneck<" #C ", " #ACT ">"}
+  static const struct {
+    const void* fn;
+    const char* name;
+  } kernels[2][3] = {{OD_BN(64, 0), OD_BN(64, 1), OD_BN(64, 2)}, {OD_BN(128, 0), OD_BN(128, 1), OD_BN(128, 2)}};
+#undef OD_BN
+  const auto& k = kernels[d->C == 128][d->act];
   const int lds = d->C == 64 ? BneckCfg<64>::LDS_BYTES : BneckCfg<128>::LDS_BYTES;
-  if (int rc = od_ensure_lds(ctx, fn, (size_t)lds)) return rc;
-  int ntiles = d->B * p.tiles_x * p.tiles_y;
+  if (int rc = od_ensure_lds(ctx, k.fn, (size_t)lds)) return rc;
+  const int ntiles = d->B * p.tiles_x * p.tiles_y;
   // C = 64: persistent workgroups (one per CU) walk the tiles; C = 128: one workgroup per tile
   const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
   const int grid = d->C == 64 ? (ntiles < cus ? ntiles : cus) : ntiles;
-  void* args[] = {&p, &ntiles};
-  OD_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(d->C == 64 ? 768 : 512), args, (size_t)lds, (hipStream_t)stream));
-  return OD_OK;
+  return od_add_launch(L, {k.name, od_issue_kp_int<BneckKP>, k.fn, dim3((unsigned)grid), dim3(d->C == 64 ? 768 : 512), (size_t)lds},
+                       od_kp_int<BneckKP>{p, ntiles});
+}
+
+extern "C" int od_bottleneck_fwd(od_ctx* ctx, const od_bneck_desc* d, void* stream) {
+  return od_prepare_issue(stream, od_bottleneck_prepare, ctx, d);
 }

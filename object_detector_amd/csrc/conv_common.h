@@ -293,10 +293,10 @@ int od_conv_8ph_num_cfgs();
 bool od_conv_8ph_select(int idx, const ConvKP& p, int ksize, ConvKernelInfo* info, size_t* lds_bytes);
 // conv_tconv.hip: streaming backward-data kernel of the first stride-2 convolution (dZ 64 channels -> dX 32 channels)
 bool od_tconv_small_supported(const od_conv_desc* d);
-int od_tconv_small_launch(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name, bool dry_run);
+int od_tconv_small_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L);
 // conv_rdirect.hip: 3x3, 64 -> 128 channels on large maps: all weights in LDS, pixel operand straight from global memory
 bool od_conv_rdirect_supported(const od_conv_desc* d);
-int od_conv_rdirect_launch(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name, bool dry_run);
+int od_conv_rdirect_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L);
 // conv_stream3.hip: streaming 3x3 kernels of the 32 <-> 64-channel layers on the largest maps
 bool od_conv_stream3_supported(const od_conv_desc* d);
-int od_conv_stream3_launch(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name, bool dry_run);
+int od_conv_stream3_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L);

@@ -93,21 +93,36 @@ __global__ __launch_bounds__(256) void od_conv_first(const uint8_t* __restrict__
   }
 }
 
+struct FirstArgs {
+  const uint8_t* x;
+  const f16* w;
+  const float *scale, *bias;
+  f16* out;
+  int H, W, act;
+  float alpha;
+};
+int first_issue(const od_launch& l, hipStream_t stream) {
+  const FirstArgs& a = l.arg<FirstArgs>();
+  hipLaunchKernelGGL(od_conv_first, l.grid, l.block, 0, stream, a.x, a.w, a.scale, a.bias, a.out, a.H, a.W, a.act, a.alpha);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
 }  // namespace
 
-const char* od_conv_first_kernel_name() { return "od_conv_first"; }
-
-extern "C" int od_conv_first_fwd(od_ctx* ctx, const uint8_t* x, const void* w, const float* scale, const float* bias,
-                                 void* out, int B, int H, int W, int Cout, int act, float alpha, void* stream) {
+int od_conv_first_prepare(od_ctx* ctx, const uint8_t* x, const void* w, const float* scale, const float* bias, void* out,
+                          int B, int H, int W, int Cout, int act, float alpha, od_launches* L) {
   OD_REQUIRE(ctx && x && w && scale && bias && out, "od_conv_first_fwd: null argument");
   OD_REQUIRE(Cout == 32, "od_conv_first_fwd: Cout must be 32 (got %d)", Cout);
   OD_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535, "od_conv_first_fwd: bad dims");
   OD_REQUIRE((long long)B * H * W * 32 < (1LL << 31), "od_conv_first_fwd: tensor too large");
   dim3 grid(od_ceil_div(W, TW), od_ceil_div(H, TH), B);
-  hipLaunchKernelGGL(od_conv_first, grid, dim3(256), 0, (hipStream_t)stream, x, (const f16*)w, scale, bias, (f16*)out,
-                     H, W, act, alpha);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
+  return od_add_launch(L, {"od_conv_first", first_issue, (const void*)&od_conv_first, grid, dim3(256), 0},
+                       FirstArgs{x, (const f16*)w, scale, bias, (f16*)out, H, W, act, alpha});
+}
+
+extern "C" int od_conv_first_fwd(od_ctx* ctx, const uint8_t* x, const void* w, const float* scale, const float* bias,
+                                 void* out, int B, int H, int W, int Cout, int act, float alpha, void* stream) {
+  return od_prepare_issue(stream, od_conv_first_prepare, ctx, x, w, scale, bias, out, B, H, W, Cout, act, alpha);
 }
 
 // ---- K11 for the first layer: dW[co][tap*3 + c] += in_scale * sum_pixels dz[pixel][co] * x_u8[shifted pixel][c] ----------

@@ -366,51 +366,27 @@ struct TileCfg {
   int BM, BN, BK, threads;
   size_t lds;
   const void* k1;   // KS == 1 (channel tail masked per lane: any Cin % 8 == 0)
-  const void* k3;   // KS == 3, Cin % BK == 0
-  const void* k3g;  // KS == 3, any Cin % 8 == 0 (per-lane tap decomposition); may be null
   const char* name1;
+  const void* k3;   // KS == 3, Cin % BK == 0
   const char* name3;
+  const void* k3g;  // KS == 3, any Cin % 8 == 0 (per-lane tap decomposition); may be null
   const char* name3g;
 };
 
-#define OD_STR2(x) #x
-#define OD_STR(x) OD_STR2(x)
-#define OD_NAME(BM, BN, BK, ST, WM, WN, KS, MINW, UNI)                                                              \
-  "od_conv_igemm<" OD_STR(BM) ", " OD_STR(BN) ", " OD_STR(BK) ", " OD_STR(ST) ", " OD_STR(WM) ", " OD_STR(WN) ", " OD_STR(KS) ", " OD_STR(MINW) ", " #UNI ", 0, false>"
-#define OD_CFG(BM, BN, BK, ST, WM, WN, MINW)                                                                        \
-  {                                                                                                                 \
-    BM, BN, BK, WM* WN * 64, (size_t)ConvCfg<BM, BN, BK, ST, WM, WN>::LDS_BYTES,                                    \
-        (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, 1, MINW, true, 0>,                                      \
-        (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, 3, MINW, true, 0>, nullptr,                                \
-        OD_NAME(BM, BN, BK, ST, WM, WN, 1, MINW, true), OD_NAME(BM, BN, BK, ST, WM, WN, 3, MINW, true), ""          \
-  }
-#define OD_CFG_S(BM, BN, BK, ST, WM, WN, MINW)                                                                      \
-  {                                                                                                                 \
-    BM, BN, BK, WM* WN * 128, (size_t)ConvCfg<BM, BN, BK, ST, WM, WN, 1>::LDS_BYTES,                                \
-        (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, 1, MINW, true, 1>,                                      \
-        (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, 3, MINW, true, 1>, nullptr,                             \
-        "od_conv_igemm<" OD_STR(BM) ", " OD_STR(BN) ", " OD_STR(BK) ", " OD_STR(ST) ", " OD_STR(WM) ", " OD_STR(WN) ", 1, " OD_STR(MINW) ", true, 1, false>", \
-        "od_conv_igemm<" OD_STR(BM) ", " OD_STR(BN) ", " OD_STR(BK) ", " OD_STR(ST) ", " OD_STR(WM) ", " OD_STR(WN) ", 3, " OD_STR(MINW) ", true, 1, false>", "" \
-  }
-#define OD_CFG_S2(BM, BN, BK, ST, WM, WN, MINW)                                                                     \
-  {                                                                                                                 \
-    BM, BN, BK, WM* WN * 128, (size_t)ConvCfg<BM, BN, BK, ST, WM, WN, 1>::LDS_BYTES,                                \
-        (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, 1, MINW, true, 2>,                                      \
-        (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, 3, MINW, true, 2>, nullptr,                             \
-        "od_conv_igemm<" OD_STR(BM) ", " OD_STR(BN) ", " OD_STR(BK) ", " OD_STR(ST) ", " OD_STR(WM) ", " OD_STR(WN) ", 1, " OD_STR(MINW) ", true, 2, false>", \
-        "od_conv_igemm<" OD_STR(BM) ", " OD_STR(BN) ", " OD_STR(BK) ", " OD_STR(ST) ", " OD_STR(WM) ", " OD_STR(WN) ", 3, " OD_STR(MINW) ", true, 2, false>", "" \
-  }
-#define OD_CFG_G(BM, BN, BK, ST, WM, WN, MINW)                                                                      \
-  {                                                                                                                 \
-    BM, BN, BK, WM* WN * 64, (size_t)ConvCfg<BM, BN, BK, ST, WM, WN>::LDS_BYTES,                                    \
-        (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, 1, MINW, true, 0>,                                      \
-        (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, 3, MINW, true, 0>,                                      \
-        (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, 3, MINW, false, 0>,                                        \
-        OD_NAME(BM, BN, BK, ST, WM, WN, 1, MINW, true), OD_NAME(BM, BN, BK, ST, WM, WN, 3, MINW, true),             \
-        OD_NAME(BM, BN, BK, ST, WM, WN, 3, MINW, false)                                                             \
-  }
+// an od_conv_igemm instantiation and its name
+#define OD_K(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC)                                                              \
+  (const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC>,                                            \
+      "od_conv_igemm<" #BM ", " #BN ", " #BK ", " #ST ", " #WM ", " #WN ", " #KS ", " #MINW ", " #UNI ", " #SPEC ", false>"
+// SPEC = 1: wave-specialised, twice the threads; OD_CFG_G adds the generic 3x3 kernel
+#define OD_CFG(BM, BN, BK, ST, WM, WN, MINW, SPEC)                                                                     \
+  {BM, BN, BK, WM * WN * 64 * (SPEC + 1), (size_t)ConvCfg<BM, BN, BK, ST, WM, WN, SPEC>::LDS_BYTES,                    \
+   OD_K(BM, BN, BK, ST, WM, WN, 1, MINW, true, SPEC), OD_K(BM, BN, BK, ST, WM, WN, 3, MINW, true, SPEC), nullptr, ""}
+#define OD_CFG_G(BM, BN, BK, ST, WM, WN, MINW)                                                                         \
+  {BM, BN, BK, WM * WN * 64, (size_t)ConvCfg<BM, BN, BK, ST, WM, WN>::LDS_BYTES,                                       \
+   OD_K(BM, BN, BK, ST, WM, WN, 1, MINW, true, 0), OD_K(BM, BN, BK, ST, WM, WN, 3, MINW, true, 0),                     \
+   OD_K(BM, BN, BK, ST, WM, WN, 3, MINW, false, 0)}
 
-//                   BM   BN  BK ST WM WN minwaves/SIMD
+//                   BM   BN  BK ST WM WN minwaves/SIMD, SPEC
 // Only what pick_cfg / the bn_partials fallback can select (round 3: the 22 table configs, the LDS-window kernels and the
 // persistent window kernel that never won a layer are gone -- profiles/r01/conv_cfg_sweep.txt, profiles/r02/spec64_sweep.txt
 // record what they measured).
@@ -419,10 +395,10 @@ const TileCfg g_cfgs[] = {
     OD_CFG_G(128, 64, 64, 2, 2, 2, 2),   // 1
     OD_CFG_G(64, 128, 64, 2, 2, 2, 2),   // 2
     OD_CFG_G(64, 64, 64, 2, 2, 2, 2),    // 3
-    OD_CFG_S(128, 128, 64, 2, 2, 2, 4),  // 4: 4 MFMA waves + 4 DMA waves, 64 KiB, 2 WG/CU
-    OD_CFG_S(128, 128, 64, 3, 2, 2, 2),  // 5: same, 3-deep ring (96 KiB, 1 WG/CU): few tiles, long K
-    OD_CFG(64, 64, 64, 4, 2, 2, 2),      // 6: deep ring for the short-K 1x1 layers (cold L2: latency, not bandwidth)
-    OD_CFG_S(64, 128, 64, 3, 2, 2, 4),   // 7: specialised 64 x 128, 72 KiB: small-M layers
+    OD_CFG(128, 128, 64, 2, 2, 2, 4, 1), // 4: 4 MFMA waves + 4 DMA waves, 64 KiB, 2 WG/CU
+    OD_CFG(128, 128, 64, 3, 2, 2, 2, 1), // 5: same, 3-deep ring (96 KiB, 1 WG/CU): few tiles, long K
+    OD_CFG(64, 64, 64, 4, 2, 2, 2, 0),   // 6: deep ring for the short-K 1x1 layers (cold L2: latency, not bandwidth)
+    OD_CFG(64, 128, 64, 3, 2, 2, 4, 1),  // 7: specialised 64 x 128, 72 KiB: small-M layers
 };
 constexpr int kNumCfgs = sizeof(g_cfgs) / sizeof(g_cfgs[0]);
 
@@ -520,80 +496,25 @@ extern "C" int od_conv_weight_dims(int cout, int cin, int ksize, int* cout_pad, 
   return OD_OK;
 }
 
-static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name, bool dry_run,
-                              int* mtiles_out, bool* fused_out);
-
-// od_conv_desc.w2 (the pointwise layer that consumes this launch's output): inside the 8-wave kernel's epilogue when the
-// selected kernel can do it, otherwise as a second launch right behind the first -- the caller's plan is the same either way
-static int od_conv2d_fwd_impl2(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name, bool dry_run,
-                               int* mtiles_out) {
-  bool fused = false;
+// Validates d, selects its kernel and appends the launches: the kernel (+ split-K finish); one launch per segment when the
+// 8-wave kernel does not take a grouped layer; w2 as a second launch when the selected kernel cannot run it in its epilogue.
+// want_stats selects the BatchNorm-statistics kernels (d->bn_partials, or od_conv2d_fwd_bn_rows asking for their rows).
+static int conv_prepare(od_ctx* ctx, const od_conv_desc* d, bool want_stats, od_launches* L) {
+  od_conv_desc g;
   if (d && d->nseg > 1) {
-    // grouped launch: one launch when the 8-wave kernel takes the layer, else one ordinary launch per segment
     OD_REQUIRE(d->nseg <= 3, "od_conv2d_fwd: nseg %d > 3", d->nseg);
-    OD_REQUIRE(d->ksize == 3 && d->stride == 1 && d->res_mode == OD_RES_NONE && !d->w2 && !d->bn_partials && !d->transposed,
+    OD_REQUIRE(d->ksize == 3 && d->stride == 1 && d->res_mode == OD_RES_NONE && !d->w2 && !want_stats && !d->transposed,
                "od_conv2d_fwd: a grouped launch (nseg > 1) is a 3x3 stride-1 layer without residual / w2 / bn_partials / "
                "transposed mode");
     for (int i = 0; i < d->nseg; ++i)
       OD_REQUIRE(d->seg_x[i] && d->seg_out[i] && d->seg_H[i] > 0 && d->seg_W[i] > 0, "od_conv2d_fwd: segment %d is incomplete", i);
-    od_conv_desc q = *d;  // the first segment stands in for x / out / H / W in the shared validation
-    q.x = d->seg_x[0];
-    q.out = d->seg_out[0];
-    q.H = d->seg_H[0];
-    q.W = d->seg_W[0];
-    bool grouped = false;
-    int rc = od_conv2d_fwd_main(ctx, &q, stream, kernel_name, dry_run, mtiles_out, &grouped);
-    if (rc != OD_OK || grouped) return rc;
-    for (int i = 0; i < d->nseg; ++i) {
-      q.nseg = 0;
-      q.x = d->seg_x[i];
-      q.out = d->seg_out[i];
-      q.H = d->seg_H[i];
-      q.W = d->seg_W[i];
-      rc = od_conv2d_fwd_main(ctx, &q, stream, i == 0 ? kernel_name : nullptr, dry_run, nullptr, nullptr);
-      if (rc != OD_OK) return rc;
-    }
-    return OD_OK;
+    g = *d;  // the first segment stands in for x / out / H / W in the shared validation
+    g.x = d->seg_x[0];
+    g.out = d->seg_out[0];
+    g.H = d->seg_H[0];
+    g.W = d->seg_W[0];
+    d = &g;
   }
-  const int rc = od_conv2d_fwd_main(ctx, d, stream, kernel_name, dry_run, mtiles_out, &fused);
-  if (rc != OD_OK || !d->w2 || fused || dry_run) return rc;
-  const int pad = d->ksize / 2;
-  od_conv_desc q;
-  memset(&q, 0, sizeof(q));
-  q.x = d->out;
-  q.w = d->w2;
-  q.scale = d->scale2;
-  q.bias = d->bias2;
-  q.out = d->out2;
-  q.B = d->B;
-  q.H = (d->H + 2 * pad - d->ksize) / d->stride + 1;
-  q.W = (d->W + 2 * pad - d->ksize) / d->stride + 1;
-  q.Cin = d->Cout;
-  q.Cout = d->Cout2;
-  q.ksize = 1;
-  q.stride = 1;
-  q.act = d->act2;
-  q.alpha = d->alpha2;
-  q.res_mode = OD_RES_NONE;
-  q.out_dtype = OD_DT_F16;
-  q.tile_cfg = d->tile_cfg < 0 ? d->tile_cfg : -1;
-  q.splitk = d->splitk;
-  q.splitk_workspace = d->splitk_workspace;  // same stream: the first launch's finish kernel is done with it
-  q.splitk_workspace_bytes = d->splitk_workspace_bytes;
-  return od_conv2d_fwd_main(ctx, &q, stream, nullptr, false, nullptr, nullptr);
-}
-
-int od_conv2d_fwd_impl(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name,
-                       bool dry_run) {
-  return od_conv2d_fwd_impl2(ctx, d, stream, kernel_name, dry_run, nullptr);
-}
-
-static int od_conv2d_fwd_rows_impl(od_ctx* ctx, const od_conv_desc* d, int* rows) {
-  return od_conv2d_fwd_impl2(ctx, d, nullptr, nullptr, true, rows);
-}
-
-static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name, bool dry_run,
-                              int* mtiles_out, bool* fused_out) {
   OD_REQUIRE(ctx && d, "od_conv2d_fwd: null ctx/desc");
   OD_REQUIRE(d->x && d->w && d->scale && d->bias && d->out, "od_conv2d_fwd: null tensor");
   OD_REQUIRE(d->ksize == 1 || d->ksize == 3, "od_conv2d_fwd: ksize %d unsupported", d->ksize);
@@ -618,13 +539,12 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
   const long long M64 = (long long)d->B * Ho * Wo;
   OD_REQUIRE(M64 * d->Cout < (1LL << 31) && (long long)d->B * d->H * d->W * d->Cin < (1LL << 31),
              "od_conv2d_fwd: tensor too large for 32-bit element offsets");
-  const bool grouped = d->nseg > 1;  // (validated by the caller: 3x3, stride 1, plain epilogue; q.H / q.W = segment 0)
+  const bool grouped = d->nseg > 1;  // (validated above: 3x3, stride 1, plain epilogue; H / W = segment 0)
   long long Mg = 0;
   for (int i = 0; grouped && i < d->nseg; ++i) Mg += (long long)d->B * d->seg_H[i] * d->seg_W[i];
   OD_REQUIRE(!grouped || Mg * d->Cout < (1LL << 31), "od_conv2d_fwd: grouped launch too large for 32-bit element offsets");
   const int M = grouped ? (int)Mg : (int)M64;
 
-  const bool want_stats = d->bn_partials != nullptr;
   if (want_stats)
     OD_REQUIRE(!tconv && d->out_dtype == OD_DT_F16 && d->act == OD_ACT_LINEAR && d->res_mode == OD_RES_NONE,
                "od_conv2d_fwd: bn_partials needs the raw convolution (f16 output, no activation, no residual, no transposed "
@@ -639,12 +559,11 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
                    (d->out_pix_stride == 0 || d->out_pix_stride == d->Cout),
                "od_conv2d_fwd: w2 (the consuming pointwise layer) needs a dense f16 output of the first layer");
   }
-  if (tconv && d->tile_cfg < 0 && od_tconv_small_supported(d))
-    return od_tconv_small_launch(ctx, d, stream, kernel_name, dry_run);
-  if (d->tile_cfg < 0 && od_conv_rdirect_supported(d))  // (also the transposed form of b.down2's backward-data)
-    return od_conv_rdirect_launch(ctx, d, stream, kernel_name, dry_run);
-  if (!tconv && d->tile_cfg < 0 && od_conv_stream3_supported(d))
-    return od_conv_stream3_launch(ctx, d, stream, kernel_name, dry_run);
+  if (d->tile_cfg < 0 && !want_stats && !grouped) {  // (these kernels have neither the statistics epilogue nor a segment table)
+    if (tconv && od_tconv_small_supported(d)) return od_tconv_small_prepare(ctx, d, L);
+    if (od_conv_rdirect_supported(d)) return od_conv_rdirect_prepare(ctx, d, L);  // (also the transposed form of b.down2's backward-data)
+    if (!tconv && od_conv_stream3_supported(d)) return od_conv_stream3_prepare(ctx, d, L);
+  }
   int cfg = d->tile_cfg;
   if (cfg < 0)  // (the 8-wave kernel has its own epilogue without the statistics path: not offered when they are asked for)
     cfg = pick_cfg(ctx, M, d->Cin, d->Cout, d->ksize,
@@ -660,7 +579,15 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
   OD_REQUIRE(cfg < cfg_e8 + od_conv_8ph_num_cfgs(), "od_conv2d_fwd: tile_cfg %d out of range", cfg);
   const bool use_e8 = cfg >= cfg_e8;
   if (grouped && !(use_e8 && d->Cin % 64 == 0)) {  // the table kernels have no segment table: one launch per segment
-    if (fused_out) *fused_out = false;
+    od_conv_desc q = *d;
+    q.nseg = 0;
+    for (int i = 0; i < d->nseg; ++i) {
+      q.x = d->seg_x[i];
+      q.out = d->seg_out[i];
+      q.H = d->seg_H[i];
+      q.W = d->seg_W[i];
+      if (int rc = conv_prepare(ctx, &q, false, L)) return rc;
+    }
     return OD_OK;
   }
   OD_REQUIRE(!(want_stats && use_e8), "od_conv2d_fwd: bn_partials is supported by the table kernels only (tile_cfg %d)", cfg);
@@ -743,7 +670,6 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
     p.seg_tile0[3] = t0;
     p.mtiles = t0;
     if (!d->out_batch_stride) p.obs = 0;  // dense outputs: the kernel takes every segment's own H * W * Cout
-    if (fused_out) *fused_out = true;  // (the caller's "ran as one grouped launch" flag)
   }
   p.Mq = 0;
   if (tconv) {  // rows per parity class padded to whole tiles, classes interleaved tile by tile (od_tconv_pixel)
@@ -752,13 +678,12 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
     p.M = p.mtiles * tc.BM;
   }
   p.ntiles = od_ceil_div(d->Cout, tc.BN);
-  if (mtiles_out) *mtiles_out = p.mtiles;
   // split-K for layers that cannot fill the chip with output tiles (batch-1 inference): every K-range workgroup writes
   // its partial tile to its own slab of the caller's f32 workspace; splitk == 0 lets the library choose
   p.splitk = 1;
   p.steps_per_split = 0;
   p.ws = (float*)d->splitk_workspace;
-  if (want_stats && !dry_run) {
+  if (d->bn_partials) {
     const long long need = (long long)p.mtiles * 2 * d->Cout * 4;
     if (d->bn_partials_bytes < need) {
       od_set_error("od_conv2d_fwd: bn_partials holds %lld bytes, %d rows x 2 x %d channels need %lld", (long long)d->bn_partials_bytes,
@@ -788,7 +713,6 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
     size_t lds = 0;
     if (!od_conv_8ph_select(cfg - cfg_e8, p, d->ksize, &e8, &lds)) return OD_ERR_INVALID;
   }
-  if (fused_out) *fused_out = grouped || p.w2 != nullptr;
   // weights/scale/bias are padded to a multiple of 256 output channels, so any BN <= 256 tile stays in bounds.
 
   // kernel variant: 1x1 / 3x3-uniform-tap / 3x3-generic (odd channel counts fall back to a config that has one)
@@ -805,34 +729,60 @@ static int od_conv2d_fwd_main(od_ctx* ctx, const od_conv_desc* d, hipStream_t st
       return OD_ERR_INVALID;
     }
   }
-  if (kernel_name) *kernel_name = use_e8 ? e8.name : (variant == 0 ? tc.name1 : (variant == 1 ? tc.name3 : tc.name3g));
-  if (dry_run) return OD_OK;
-
+  const char* name = use_e8 ? e8.name : (variant == 0 ? tc.name1 : (variant == 1 ? tc.name3 : tc.name3g));
   if (int rc = od_ensure_lds(ctx, fn, tc.lds)) return rc;
-  void* args[] = {&p};
   // the 8-wave kernel's epilogue needs no LDS unless it writes split-K slabs: ask only for the two K-tile buffers then
   // (128 KiB), which leaves room on the CU for a small workgroup of another stream
   const size_t launch_lds = (use_e8 && p.splitk <= 1 && tc.lds > (size_t)128 * 1024) ? (size_t)128 * 1024 : tc.lds;
-  OD_CHECK_HIP(hipLaunchKernel(fn, dim3(p.mtiles * p.ntiles * p.splitk), dim3(tc.threads), args, launch_lds, stream));
+  if (int rc = od_add_launch(L, {name, od_issue_kp, fn, dim3(p.mtiles * p.ntiles * p.splitk), dim3(tc.threads), launch_lds}, p))
+    return rc;
   if (p.splitk > 1) {
     const long long nvec = (long long)p.M * (p.Cout / 8);
     long long fb = (nvec + 255) / 256;
     if (fb > 2048) fb = 2048;
-    hipLaunchKernelGGL(od_conv_finish, dim3((unsigned)fb), dim3(256), 0, stream, p);
-    OD_CHECK_LAUNCH();
+    if (int rc = od_add_launch(L, {"od_conv_finish", od_issue_kp, (const void*)&od_conv_finish, dim3((unsigned)fb), dim3(256), 0}, p))
+      return rc;
   }
-  return OD_OK;
+  if (!d->w2 || p.w2) return OD_OK;
+  // the consuming pointwise layer as a second launch right behind the first
+  od_conv_desc q;
+  memset(&q, 0, sizeof(q));
+  q.x = d->out;
+  q.w = d->w2;
+  q.scale = d->scale2;
+  q.bias = d->bias2;
+  q.out = d->out2;
+  q.B = d->B;
+  q.H = (d->H + 2 * pad - d->ksize) / d->stride + 1;
+  q.W = (d->W + 2 * pad - d->ksize) / d->stride + 1;
+  q.Cin = d->Cout;
+  q.Cout = d->Cout2;
+  q.ksize = 1;
+  q.stride = 1;
+  q.act = d->act2;
+  q.alpha = d->alpha2;
+  q.res_mode = OD_RES_NONE;
+  q.out_dtype = OD_DT_F16;
+  q.tile_cfg = d->tile_cfg < 0 ? d->tile_cfg : -1;
+  q.splitk = d->splitk;
+  q.splitk_workspace = d->splitk_workspace;  // same stream: the first launch's finish kernel is done with it
+  q.splitk_workspace_bytes = d->splitk_workspace_bytes;
+  return conv_prepare(ctx, &q, false, L);
+}
+
+int od_conv_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) {
+  return conv_prepare(ctx, d, d && d->bn_partials, L);
 }
 
 extern "C" int od_conv2d_fwd(od_ctx* ctx, const od_conv_desc* d, void* stream) {
-  return od_conv2d_fwd_impl(ctx, d, (hipStream_t)stream, nullptr, false);
+  return od_prepare_issue(stream, od_conv_prepare, ctx, d);
 }
 
 extern "C" int od_conv2d_fwd_bn_rows(od_ctx* ctx, const od_conv_desc* d) {
   if (!ctx || !d) return -1;
   od_conv_desc q = *d;
-  if (!q.bn_partials) q.bn_partials = (float*)(uintptr_t)16;  // dry run: only the tile choice matters
-  int rows = 0;
-  if (od_conv2d_fwd_rows_impl(ctx, &q, &rows) != OD_OK) return -1;
-  return rows;
+  q.bn_partials = nullptr;  // the row count is the statistics kernel's m-tile count, whatever buffer is (or is not) given
+  od_launches L;
+  if (conv_prepare(ctx, &q, true, &L) != OD_OK) return -1;
+  return L.l[0].arg<ConvKP>().mtiles;
 }

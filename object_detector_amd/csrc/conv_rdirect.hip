@@ -347,11 +347,9 @@ bool od_conv_rdirect_supported(const od_conv_desc* d) {
   return (long long)d->B * d->H * d->W * (d->transposed ? 4 : 1) >= min_px;  // (transposed: the output map is the large one)
 }
 
-int od_conv_rdirect_launch(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name, bool dry_run) {
+int od_conv_rdirect_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) {
   const RdEntry* e = rd_find(d);
   if (!e) return OD_ERR_INVALID;
-  if (kernel_name) *kernel_name = e->name;
-  if (dry_run) return OD_OK;
   RdKP p;
   p.x = (const f16*)d->x;
   p.w = (const f16*)d->w;
@@ -372,7 +370,5 @@ int od_conv_rdirect_launch(od_ctx* ctx, const od_conv_desc* d, hipStream_t strea
   int grid = d->ksize == 1 ? 2 * cus : cus;  // (the 3x3 form holds 147 KiB of LDS: one workgroup per CU)
   if (grid * 8 > p.nitems) grid = od_ceil_div(p.nitems, 8);
   if (int rc = od_ensure_lds(ctx, e->fn, e->lds)) return rc;
-  void* args[] = {&p};
-  OD_CHECK_HIP(hipLaunchKernel(e->fn, dim3(grid), dim3(512), args, e->lds, stream));
-  return OD_OK;
+  return od_add_launch(L, {e->name, od_issue_kp, e->fn, dim3(grid), dim3(512), e->lds}, p);
 }

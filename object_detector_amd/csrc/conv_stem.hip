@@ -308,9 +308,7 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
 
 extern "C" int od_stem_supported(int H, int W) { return H > 0 && W > 0 && (H % 32) == 0 && (W % 32) == 0; }  // net input rule
 
-const char* od_stem_kernel_name() { return "od_stem_k<1>"; }
-
-extern "C" int od_stem_fwd(od_ctx* ctx, const od_stem_desc* d, void* stream) {
+int od_stem_prepare(od_ctx* ctx, const od_stem_desc* d, od_launches* L) {
   OD_REQUIRE(ctx && d, "od_stem_fwd: null ctx/desc");
   OD_REQUIRE(d->x && d->w0 && d->scale0 && d->bias0 && d->w3 && d->scale3 && d->bias3 && d->out, "od_stem_fwd: null tensor");
   OD_REQUIRE(od_stem_supported(d->H, d->W), "od_stem_fwd: H and W must be multiples of 32 (got %dx%d)", d->H, d->W);
@@ -334,14 +332,22 @@ extern "C" int od_stem_fwd(od_ctx* ctx, const od_stem_desc* d, void* stream) {
   p.alpha = d->alpha;
   p.tiles_x = d->W / 32;
   p.tiles_y = d->H / 32;
-  int ntiles = d->B * p.tiles_x * p.tiles_y;
+  const int ntiles = d->B * p.tiles_x * p.tiles_y;
   const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
   const int grid = ntiles < cus ? ntiles : cus;
-  const void* fn = d->act == OD_ACT_LEAKY ? (const void*)&od_stem_k<OD_ACT_LEAKY>
-                   : d->act == OD_ACT_ELU ? (const void*)&od_stem_k<OD_ACT_ELU>
-                                          : (const void*)&od_stem_k<OD_ACT_LINEAR>;
-  if (int rc = od_ensure_lds(ctx, fn, (size_t)S_LDS)) return rc;
-  void* args[] = {&p, &ntiles};
-  OD_CHECK_HIP(hipLaunchKernel(fn, dim3((unsigned)grid), dim3(512), args, (size_t)S_LDS, (hipStream_t)stream));
-  return OD_OK;
+  static_assert(OD_ACT_LINEAR == 0 && OD_ACT_LEAKY == 1 && OD_ACT_ELU == 2, "kernel table order");
+#define OD_STEM(ACT) {(const void*)&od_stem_k<ACT>, "od_stem_k<" #ACT ">"}
+  static const struct {
+    const void* fn;
+    const char* name;
+  } kernels[3] = {OD_STEM(0), OD_STEM(1), OD_STEM(2)};
+#undef OD_STEM
+  const auto& k = kernels[d->act];
+  if (int rc = od_ensure_lds(ctx, k.fn, (size_t)S_LDS)) return rc;
+  return od_add_launch(L, {k.name, od_issue_kp_int<StemKP>, k.fn, dim3((unsigned)grid), dim3(512), (size_t)S_LDS},
+                       od_kp_int<StemKP>{p, ntiles});
+}
+
+extern "C" int od_stem_fwd(od_ctx* ctx, const od_stem_desc* d, void* stream) {
+  return od_prepare_issue(stream, od_stem_prepare, ctx, d);
 }

@@ -206,11 +206,9 @@ bool od_conv_stream3_supported(const od_conv_desc* d) {
   return s3_find(d) != nullptr && Ho % 4 == 0 && Wo % 16 == 0 && (long long)d->B * d->H * d->W * d->Cin < (1LL << 31);
 }
 
-int od_conv_stream3_launch(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name, bool dry_run) {
+int od_conv_stream3_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) {
   const S3Entry* e = s3_find(d);
   if (!e) return OD_ERR_INVALID;
-  if (kernel_name) *kernel_name = e->name;
-  if (dry_run) return OD_OK;
   Stream3KP p;
   p.x = (const f16*)d->x;
   p.w = (const f16*)d->w;
@@ -232,7 +230,5 @@ int od_conv_stream3_launch(od_ctx* ctx, const od_conv_desc* d, hipStream_t strea
   int grid = 2 * cus;
   if (grid > p.ntiles) grid = p.ntiles;
   if (int rc = od_ensure_lds(ctx, e->fn, e->lds)) return rc;
-  void* args[] = {&p};
-  OD_CHECK_HIP(hipLaunchKernel(e->fn, dim3(grid), dim3(256), args, e->lds, stream));
-  return OD_OK;
+  return od_add_launch(L, {e->name, od_issue_kp, e->fn, dim3(grid), dim3(256), e->lds}, p);
 }

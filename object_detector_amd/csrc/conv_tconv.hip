@@ -179,9 +179,7 @@ bool od_tconv_small_supported(const od_conv_desc* d) {
          d->H % T_R == 0 && d->W % T_C == 0 && !d->bn_partials && !d->w2;
 }
 
-int od_tconv_small_launch(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream, const char** kernel_name, bool dry_run) {
-  if (kernel_name) *kernel_name = "od_tconv_64_32";
-  if (dry_run) return OD_OK;
+int od_tconv_small_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) {
   TconvKP p;
   p.dz = (const f16*)d->x;
   p.wt = (const f16*)d->w;
@@ -200,7 +198,5 @@ int od_tconv_small_launch(od_ctx* ctx, const od_conv_desc* d, hipStream_t stream
   int grid = 2 * cus;
   if (grid > p.ntiles) grid = p.ntiles;
   if (int rc = od_ensure_lds(ctx, (const void*)&od_tconv_64_32, (size_t)T_LDS)) return rc;
-  hipLaunchKernelGGL(od_tconv_64_32, dim3(grid), dim3(256), T_LDS, stream, p);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
+  return od_add_launch(L, {"od_tconv_64_32", od_issue_kp, (const void*)&od_tconv_64_32, dim3(grid), dim3(256), T_LDS}, p);
 }

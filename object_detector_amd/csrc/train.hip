@@ -574,7 +574,7 @@ extern "C" int od_conv2d_bwd_data(od_ctx* ctx, const void* dz, const void* w_bwd
   d.tile_cfg = -1;
   d.transposed = stride == 2;
   d.splitk = 1;
-  return od_conv2d_fwd_impl(ctx, &d, (hipStream_t)stream, nullptr, false);
+  return od_conv2d_fwd(ctx, &d, stream);
 }
 
 extern "C" size_t od_bn_workspace_bytes(long long M, int C) {

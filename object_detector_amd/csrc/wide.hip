@@ -58,7 +58,16 @@ __global__ __launch_bounds__(256) void od_wide_add_k(const float* __restrict__ y
   }
 }
 
-extern "C" int od_wide_add(od_ctx* ctx, const od_wide_desc* d, void* stream) {
+template <bool RES32>
+static int wide_issue(const od_launch& l, hipStream_t stream) {
+  const od_wide_desc* d = &l.arg<od_wide_desc>();
+  hipLaunchKernelGGL(od_wide_add_k<RES32>, l.grid, l.block, 0, stream, d->y, d->res, d->out32, (f16*)d->out16,
+                     (f16*)d->out_hilo, d->M * (d->C / 8), d->C / 8, d->res_up2, d->H, d->W);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
+int od_wide_prepare(od_ctx* ctx, const od_wide_desc* d, od_launches* L) {
   OD_REQUIRE(ctx && d && d->y && d->M > 0 && d->C > 0 && d->C % 8 == 0, "od_wide_add: bad argument (C must be a multiple of 8)");
   OD_REQUIRE(d->out32 || d->out16 || d->out_hilo, "od_wide_add: no output");
   OD_REQUIRE((((uintptr_t)d->y | (uintptr_t)d->res | (uintptr_t)d->out32 | (uintptr_t)d->out16 | (uintptr_t)d->out_hilo) & 15) == 0,
@@ -69,12 +78,13 @@ extern "C" int od_wide_add(od_ctx* ctx, const od_wide_desc* d, void* stream) {
   const long long nvec = d->M * (d->C / 8);
   long long blocks = (nvec + 255) / 256;
   if (blocks > 8192) blocks = 8192;
-  if (d->res && d->res_f32)
-    hipLaunchKernelGGL(od_wide_add_k<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d->y, d->res, d->out32,
-                       (f16*)d->out16, (f16*)d->out_hilo, nvec, d->C / 8, d->res_up2, d->H, d->W);
-  else
-    hipLaunchKernelGGL(od_wide_add_k<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d->y, d->res, d->out32,
-                       (f16*)d->out16, (f16*)d->out_hilo, nvec, d->C / 8, d->res_up2, d->H, d->W);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
+  const bool res32 = d->res && d->res_f32;
+  return od_add_launch(L, {"od_wide_add_k", res32 ? wide_issue<true> : wide_issue<false>,
+                           res32 ? (const void*)&od_wide_add_k<true> : (const void*)&od_wide_add_k<false>, dim3((unsigned)blocks),
+                           dim3(256), 0},
+                       *d);
+}
+
+extern "C" int od_wide_add(od_ctx* ctx, const od_wide_desc* d, void* stream) {
+  return od_prepare_issue(stream, od_wide_prepare, ctx, d);
 }

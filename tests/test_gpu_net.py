@@ -64,6 +64,20 @@ def test_graph_replay_matches_eager(small_setup, cuda):
     assert (a.cpu().numpy() == got).all() and (b.cpu().numpy() == got).all()  # split-K slabs are summed in a fixed order
 
 
+def test_kernel_names_carry_the_backbone_activation(cuda, monkeypatch):
+    """od_plan_op_kernel_name is the kernel the op launches: the fused stem and residual blocks are instantiated per
+    activation, and their names carry its template argument (OD_ACT_ELU = 2; the leaky plans keep <1>)."""
+    from object_detector_amd import _lib
+    from object_detector_amd import weights as W
+    from object_detector_amd.net import Net
+    monkeypatch.delenv("OD_FUSE_BLOCKS", raising=False)
+    for act, code in ((("elu", 1.0), _lib.OD_ACT_ELU), (("leaky", 0.1), _lib.OD_ACT_LEAKY)):
+        net = Net(W.random_init(2), 1, (64, 64), device=cuda, backbone_act=act)
+        names = set(net.time_ops()[1])
+        fused = {n for n in names if n.startswith(("od_stem_k", "od_bneck"))}
+        assert fused == {f"od_stem_k<{code}>", f"od_bneck<64, {code}>", f"od_bneck<128, {code}>"}, names
+
+
 def test_predict_end_to_end(cuda):
     from object_detector_amd.detector import ObjectDetector
     B, S = 2, 160
