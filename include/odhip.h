@@ -258,6 +258,10 @@ int od_gather_detections_pred(od_ctx* ctx, const float* pred, const float* boxes
  *   y f32 [B,P,2+NC+4]: col 0 = background, col 1 = assigned ("y[:,1]==1", :25), cols 2..2+NC one-hot class (:26),
  *   last 4 = regression target = inverse of od_decode_locs (:27).  An all-zero row = ignored prior.
  *   assigned_gt i32 [B,P] (may be NULL): GT index, -1 background, -2 ignore;  npos i32 [B] assigned priors per image.
+ * od_assign_anchors_ign: the same with ignore regions.  gt_flags i32 [B,Gmax], bit 0 = ignore region (COCO iscrowd, VOC
+ *   difficult, a mosaic sliver): such a box owns no prior and is not counted in npos; a prior that would be background
+ *   becomes an all-zero "ignore" row (assigned_gt -3) when inter(prior, region) / area(prior) >= ign_thr for any region.
+ *   With no flag set the result equals od_assign_anchors bit for bit.  Same workspace.
  * Rule [BUILD-DEFINED]: best GT per prior with IoU >= pos_thr; neg_thr <= IoU < pos_thr ignored; every GT force-takes
  * its best prior (ascending GT index, later wins).  Gmax <= 128.
  * ---------------------------------------------------------------------------------------------- */
@@ -266,6 +270,10 @@ int od_assign_anchors(od_ctx* ctx, const float* priors, const float* gt_boxes, c
                       const int32_t* gt_counts, int B, int P, int Gmax, int NC, float pos_thr, float neg_thr,
                       float loc_scale, float* y, int32_t* assigned_gt, int32_t* npos, void* workspace,
                       size_t workspace_bytes, void* stream);
+int od_assign_anchors_ign(od_ctx* ctx, const float* priors, const float* gt_boxes, const int32_t* gt_classes,
+                          const int32_t* gt_counts, const int32_t* gt_flags, float ign_thr, int B, int P, int Gmax,
+                          int NC, float pos_thr, float neg_thr, float loc_scale, float* y, int32_t* assigned_gt,
+                          int32_t* npos, void* workspace, size_t workspace_bytes, void* stream);
 
 /* K10: loss forward + gradient (reference docs/MODEL.md:33-52): focal(objectness, 2-class softmax) +
  * softmax-CE(classes, assigned priors) + box loss (box_mode 0 smooth-L1 / 1 MSE, assigned priors), each weighted and
@@ -419,6 +427,23 @@ typedef struct od_aug_params {
 int od_aug_params_bytes(void);
 int od_augment_batch(od_ctx* ctx, const uint8_t* src, const void* params, uint8_t* out, int B, int H, int W,
                      void* stream);
+/* Mosaic: four sources composed into one output image.  The frame is cut at (split_x, split_y), 1 <= split_x <= W and
+ * 1 <= split_y <= H in output pixels; tile[0..3] = TL, TR, BL, BR.  A pixel of a tile with origin (X0, Y0) and extent
+ * Wt x Ht samples its source at u = ((x - X0) + 0.5) / Wt, v = ((y - Y0) + 0.5) / Ht with od_augment_batch's arithmetic and
+ * that tile's parameters (a tile's n_erase must be 0); an empty tile (split_x == W, split_y == H) is never sampled.  The
+ * erase list acts on the whole frame, in normalised output coordinates.  split = (W, H): the output is od_augment_batch's
+ * for tile[0] (+ the erase list), byte for byte.  src / src_offset as in od_augment_batch. */
+typedef struct od_mosaic_params {
+  int32_t split_x, split_y;
+  od_aug_params tile[4];
+  int32_t n_erase;
+  int32_t pad_;
+  float erase[3][4];
+  uint8_t erase_rgb[3][4];
+} od_mosaic_params;
+int od_mosaic_params_bytes(void);
+int od_augment_mosaic(od_ctx* ctx, const uint8_t* src, const void* params, uint8_t* out, int B, int H, int W,
+                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K15: image decode + resize into the network input for ObjectDetector(image_decode="device") (reference

@@ -49,6 +49,12 @@ class AugParams(C.Structure):
                 ("n_erase", C.c_int32), ("erase", (C.c_float * 4) * 3), ("erase_rgb", (C.c_uint8 * 4) * 3)]
 
 
+class MosaicParams(C.Structure):
+    C_NAME = "od_mosaic_params"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
+    _fields_ = [("split_x", C.c_int32), ("split_y", C.c_int32), ("tile", AugParams * 4), ("n_erase", C.c_int32),
+                ("pad_", C.c_int32), ("erase", (C.c_float * 4) * 3), ("erase_rgb", (C.c_uint8 * 4) * 3)]
+
+
 class BneckDesc(C.Structure):
     C_NAME = "od_bneck_desc"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
     _fields_ = [
@@ -109,7 +115,7 @@ class ImgDesc(C.Structure):
                                          "hcoef_off", "vcoef_off", "coef_ws", "plane_ws", "rgb_ws", "tmp_ws", "state_ws")]
 
 
-STRUCTS = (ConvDesc, AugParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
+STRUCTS = (ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
 
 
 class OdError(RuntimeError):
@@ -214,7 +220,13 @@ _PROTOS = {
     "od_allreduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "od_comm_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "od_comm_destroy": (C.c_int, [C.c_void_p]),
+    "od_assign_anchors_ign": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "od_aug_params_bytes": (C.c_int, []),
+    "od_mosaic_params_bytes": (C.c_int, []),
+    "od_augment_mosaic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p]),
     "od_augment_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p]),
     "od_img_workspace_plan": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]),

@@ -101,6 +101,10 @@ const std::vector<StructInfo>& od_struct_table() {
         OD_F(od_aug_params, crop_y2), OD_F(od_aug_params, flip), OD_F(od_aug_params, brightness),
         OD_F(od_aug_params, contrast), OD_F(od_aug_params, saturation), OD_F(od_aug_params, n_erase),
         OD_F(od_aug_params, erase), OD_F(od_aug_params, erase_rgb)}},
+      {"od_mosaic_params", sizeof(od_mosaic_params),
+       {OD_F(od_mosaic_params, split_x), OD_F(od_mosaic_params, split_y), OD_F(od_mosaic_params, tile),
+        OD_F(od_mosaic_params, n_erase), OD_F(od_mosaic_params, pad_), OD_F(od_mosaic_params, erase),
+        OD_F(od_mosaic_params, erase_rgb)}},
       {"od_img_desc", sizeof(od_img_desc),
        {OD_F(od_img_desc, kind), OD_F(od_img_desc, width), OD_F(od_img_desc, height), OD_F(od_img_desc, out_w),
         OD_F(od_img_desc, out_h), OD_F(od_img_desc, ncomp), OD_F(od_img_desc, samp_h), OD_F(od_img_desc, samp_v),

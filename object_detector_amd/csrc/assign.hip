@@ -6,6 +6,11 @@
 //   1. prior p takes GT g* = argmax_g IoU(g,p) (ties: lowest g) if IoU >= pos_thr; if neg_thr <= IoU < pos_thr the
 //      row is "ignore" (all zeros: no objectness loss); otherwise background
 //   2. every GT g (ascending g, later wins) force-takes p* = argmax_p IoU(g,p) (ties: lowest p) when that IoU > 0
+// Ignore regions (od_assign_anchors_ign, gt_flags bit 0; [BUILD-DEFINED] like the rule above, mirrored by
+// tests/assign_ign_ref.py): a flagged GT (COCO iscrowd, VOC difficult, a mosaic sliver) never owns a prior -- it is left out
+// of steps 1 and 2 and of npos -- and
+//   3. a prior that came out of 1 + 2 as BACKGROUND becomes "ignore" (all-zero row, assigned_gt -3) when
+//      inter(prior, r) / area(prior) >= ign_thr for any flagged box r.  Positives stay positive; -2 rows stay -2.
 // HBM-bound elementwise work; IoU uses IEEE f32 division; compiled with -ffp-contract=off => bit-exact vs numpy.
 #include "common.h"
 
@@ -25,33 +30,68 @@ __device__ __forceinline__ float iou_f32(const f32x4 a, const f32x4 c) {
   return uni > 0.f ? inter / uni : 0.f;
 }
 
+// share of prior c that lies inside region a: intersection over the PRIOR's area (>= IoU)
+__device__ __forceinline__ float cover_f32(const f32x4 a, const f32x4 c) {
+  const float ix1 = fmaxf(a[0], c[0]), iy1 = fmaxf(a[1], c[1]);
+  const float ix2 = fminf(a[2], c[2]), iy2 = fminf(a[3], c[3]);
+  const float iw = fmaxf(ix2 - ix1, 0.f), ih = fmaxf(iy2 - iy1, 0.f);
+  const float inter = iw * ih;
+  const float area_c = (c[2] - c[0]) * (c[3] - c[1]);
+  return area_c > 0.f ? inter / area_c : 0.f;
+}
+
+// IGN: bit g of smask[g >> 6] <- bit 0 of flags[g] for g < G (G <= 128: waves 0 and 1 of the block, one ballot each)
+__device__ __forceinline__ void stage_flags(const int* __restrict__ flags, int G, int tid, u64* smask) {
+  if (tid < GMAX) {
+    const bool f = tid < G && (flags[tid] & 1);
+    const u64 m = __ballot(f);
+    if ((tid & 63) == 0) smask[tid >> 6] = m;
+  }
+}
+
+// the per-prior loop of pass 1 over the boxes in LDS; SKIP: a flagged box (bit g of smask) owns no prior
+template <bool SKIP>
+__device__ __forceinline__ void match_boxes(const f32x4* sg, u64* sbest, const u64* smask, int G, const f32x4 pr, int p,
+                                            int& bg, float& bi) {
+  for (int g = 0; g < G; ++g) {
+    if (SKIP && ((smask[g >> 6] >> (g & 63)) & 1ull)) continue;
+    const float v = iou_f32(sg[g], pr);
+    if (v > bi) {
+      bi = v;
+      bg = g;
+    }
+    if (v > 0.f) atomicMax(&sbest[g], ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)p));
+  }
+}
+
 // pass 1: per prior best GT; per GT best prior (u64 atomicMax on (iou_bits << 32 | ~p))
+template <bool IGN>
 __global__ __launch_bounds__(256) void od_assign_match(const float* __restrict__ priors, const float* __restrict__ gt_boxes,
-                                                       const int* __restrict__ gt_counts, int P, int Gmax,
+                                                       const int* __restrict__ gt_counts,
+                                                       const int* __restrict__ gt_flags, int P, int Gmax,
                                                        int* __restrict__ best_g, float* __restrict__ best_iou,
                                                        u64* __restrict__ gt_best) {
   __shared__ f32x4 sg[GMAX];
   __shared__ u64 sbest[GMAX];
+  __shared__ u64 smask[GMAX / 64];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int G = min(gt_counts[b], Gmax);
   for (int g = tid; g < G; g += 256) {
     sg[g] = *(const f32x4*)(gt_boxes + ((long long)b * Gmax + g) * 4);
     sbest[g] = 0ull;
   }
+  if (IGN) stage_flags(gt_flags + (long long)b * Gmax, G, tid, smask);
   __syncthreads();
   const int p = blockIdx.x * 256 + tid;
   if (p < P) {
     const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
     int bg = -1;
     float bi = 0.f;
-    for (int g = 0; g < G; ++g) {
-      const float v = iou_f32(sg[g], pr);
-      if (v > bi) {
-        bi = v;
-        bg = g;
-      }
-      if (v > 0.f) atomicMax(&sbest[g], ((u64)__float_as_uint(v) << 32) | (u64)(0xFFFFFFFFu - (unsigned)p));
-    }
+    // an image without regions (the usual case) runs the loop of od_assign_anchors; with regions, flagged boxes are skipped
+    if (!IGN || !(smask[0] | smask[1]))
+      match_boxes<false>(sg, sbest, smask, G, pr, p, bg, bi);
+    else
+      match_boxes<true>(sg, sbest, smask, G, pr, p, bg, bi);
     best_g[(long long)b * P + p] = bg;
     best_iou[(long long)b * P + p] = bi;
   }
@@ -61,21 +101,25 @@ __global__ __launch_bounds__(256) void od_assign_match(const float* __restrict__
 }
 
 // pass 2: resolve + encode dense rows; counts positives per image
+template <bool IGN>
 __global__ __launch_bounds__(256) void od_assign_encode(const float* __restrict__ priors, const float* __restrict__ gt_boxes,
                                                         const int* __restrict__ gt_classes,
-                                                        const int* __restrict__ gt_counts, int P, int Gmax, int NC,
-                                                        float pos_thr, float neg_thr, float loc_scale,
+                                                        const int* __restrict__ gt_counts,
+                                                        const int* __restrict__ gt_flags, int P, int Gmax, int NC,
+                                                        float pos_thr, float neg_thr, float ign_thr, float loc_scale,
                                                         const int* __restrict__ best_g, const float* __restrict__ best_iou,
                                                         const u64* __restrict__ gt_best, float* __restrict__ y,
                                                         int* __restrict__ assigned_gt, int* __restrict__ npos) {
   __shared__ unsigned sforce[GMAX];
   __shared__ int scount;
+  __shared__ u64 smask[GMAX / 64];
   const int b = blockIdx.y, tid = threadIdx.x;
   const int G = min(gt_counts[b], Gmax);
   for (int g = tid; g < G; g += 256) {
-    const u64 k = gt_best[(long long)b * Gmax + g];
+    const u64 k = gt_best[(long long)b * Gmax + g];  // 0 for a flagged box: the match pass never offered it a prior
     sforce[g] = k ? 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull) : 0xFFFFFFFFu;
   }
+  if (IGN) stage_flags(gt_flags + (long long)b * Gmax, G, tid, smask);
   if (tid == 0) scount = 0;
   __syncthreads();
   const int p = blockIdx.x * 256 + tid;
@@ -89,6 +133,15 @@ __global__ __launch_bounds__(256) void od_assign_encode(const float* __restrict_
     else if (bg >= 0 && bi >= neg_thr) ignore = true;
     for (int q = 0; q < G; ++q)
       if (sforce[q] == (unsigned)p) g = q;  // later GT wins
+    bool region = false;
+    if (IGN && g < 0 && !ignore && (smask[0] | smask[1])) {  // background prior of an image that has regions
+      const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
+      for (int w = 0; w < GMAX / 64; ++w)
+        for (u64 m = smask[w]; m; m &= m - 1) {  // the flagged boxes only; the address is the same for the whole block
+          const int r = w * 64 + __builtin_ctzll(m);
+          region |= cover_f32(*(const f32x4*)(gt_boxes + ((long long)b * Gmax + r) * 4), pr) >= ign_thr;
+        }
+    }
     float* row = y + ((long long)b * P + p) * C;
     for (int c = 0; c < C; ++c) row[c] = 0.f;
     if (g >= 0) {
@@ -103,10 +156,10 @@ __global__ __launch_bounds__(256) void od_assign_encode(const float* __restrict_
       row[2 + NC + 2] = ((gb[2] - pr[2]) / pw) / loc_scale;
       row[2 + NC + 3] = ((gb[3] - pr[3]) / ph) / loc_scale;
       atomicAdd(&scount, 1);
-    } else if (!ignore) {
+    } else if (!ignore && !region) {
       row[0] = 1.f;
     }
-    if (assigned_gt) assigned_gt[(long long)b * P + p] = g >= 0 ? g : (ignore ? -2 : -1);
+    if (assigned_gt) assigned_gt[(long long)b * P + p] = g >= 0 ? g : (ignore ? -2 : (region ? -3 : -1));
   }
   __syncthreads();
   if (tid == 0 && scount) atomicAdd(&npos[b], scount);
@@ -135,18 +188,19 @@ extern "C" size_t od_assign_workspace_bytes(int B, int P, int Gmax) {
   return assign_layout(B, P, Gmax).total;
 }
 
-extern "C" int od_assign_anchors(od_ctx* ctx, const float* priors, const float* gt_boxes, const int32_t* gt_classes,
-                                 const int32_t* gt_counts, int B, int P, int Gmax, int NC, float pos_thr, float neg_thr,
-                                 float loc_scale, float* y, int32_t* assigned_gt, int32_t* npos, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-  OD_REQUIRE(ctx && priors && gt_boxes && gt_classes && gt_counts && y && npos && workspace,
-             "od_assign_anchors: null argument");
-  OD_REQUIRE(B > 0 && B <= 65535 && P > 0 && NC > 0 && Gmax > 0 && Gmax <= GMAX,
-             "od_assign_anchors: bad dims (Gmax <= %d)", GMAX);
-  OD_REQUIRE(loc_scale > 0.f && pos_thr >= neg_thr, "od_assign_anchors: bad thresholds");
+namespace {
+template <bool IGN>
+int assign_launch(const char* who, od_ctx* ctx, const float* priors, const float* gt_boxes, const int32_t* gt_classes,
+                  const int32_t* gt_counts, const int32_t* gt_flags, int B, int P, int Gmax, int NC, float pos_thr,
+                  float neg_thr, float ign_thr, float loc_scale, float* y, int32_t* assigned_gt, int32_t* npos,
+                  void* workspace, size_t workspace_bytes, void* stream) {
+  OD_REQUIRE(ctx && priors && gt_boxes && gt_classes && gt_counts && y && npos && workspace && (!IGN || gt_flags),
+             "%s: null argument", who);
+  OD_REQUIRE(B > 0 && B <= 65535 && P > 0 && NC > 0 && Gmax > 0 && Gmax <= GMAX, "%s: bad dims (Gmax <= %d)", who, GMAX);
+  OD_REQUIRE(loc_scale > 0.f && pos_thr >= neg_thr && (!IGN || ign_thr > 0.f), "%s: bad thresholds", who);
   const AssignLayout l = assign_layout(B, P, Gmax);
   if (workspace_bytes < l.total) {
-    od_set_error("od_assign_anchors: workspace %zu < %zu bytes", workspace_bytes, l.total);
+    od_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, l.total);
     return OD_ERR_WORKSPACE;
   }
   char* ws = (char*)workspace;
@@ -154,12 +208,32 @@ extern "C" int od_assign_anchors(od_ctx* ctx, const float* priors, const float* 
   OD_CHECK_HIP(hipMemsetAsync(ws + l.gt_best, 0, (size_t)B * Gmax * 8, s));
   OD_CHECK_HIP(hipMemsetAsync(npos, 0, (size_t)B * 4, s));
   dim3 grid(od_ceil_div(P, 256), B);
-  hipLaunchKernelGGL(od_assign_match, grid, dim3(256), 0, s, priors, gt_boxes, gt_counts, P, Gmax,
+  hipLaunchKernelGGL(od_assign_match<IGN>, grid, dim3(256), 0, s, priors, gt_boxes, gt_counts, gt_flags, P, Gmax,
                      (int*)(ws + l.best_g), (float*)(ws + l.best_iou), (u64*)(ws + l.gt_best));
   OD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(od_assign_encode, grid, dim3(256), 0, s, priors, gt_boxes, gt_classes, gt_counts, P, Gmax, NC,
-                     pos_thr, neg_thr, loc_scale, (const int*)(ws + l.best_g), (const float*)(ws + l.best_iou),
-                     (const u64*)(ws + l.gt_best), y, assigned_gt, npos);
+  hipLaunchKernelGGL(od_assign_encode<IGN>, grid, dim3(256), 0, s, priors, gt_boxes, gt_classes, gt_counts, gt_flags, P,
+                     Gmax, NC, pos_thr, neg_thr, ign_thr, loc_scale, (const int*)(ws + l.best_g),
+                     (const float*)(ws + l.best_iou), (const u64*)(ws + l.gt_best), y, assigned_gt, npos);
   OD_CHECK_LAUNCH();
   return OD_OK;
+}
+}  // namespace
+
+extern "C" int od_assign_anchors(od_ctx* ctx, const float* priors, const float* gt_boxes, const int32_t* gt_classes,
+                                 const int32_t* gt_counts, int B, int P, int Gmax, int NC, float pos_thr, float neg_thr,
+                                 float loc_scale, float* y, int32_t* assigned_gt, int32_t* npos, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  return assign_launch<false>("od_assign_anchors", ctx, priors, gt_boxes, gt_classes, gt_counts, nullptr, B, P, Gmax, NC,
+                              pos_thr, neg_thr, 0.f, loc_scale, y, assigned_gt, npos, workspace, workspace_bytes, stream);
+}
+
+// the same two passes with ignore regions (rule 3 of the header comment); workspace: od_assign_workspace_bytes
+extern "C" int od_assign_anchors_ign(od_ctx* ctx, const float* priors, const float* gt_boxes, const int32_t* gt_classes,
+                                     const int32_t* gt_counts, const int32_t* gt_flags, float ign_thr, int B, int P,
+                                     int Gmax, int NC, float pos_thr, float neg_thr, float loc_scale, float* y,
+                                     int32_t* assigned_gt, int32_t* npos, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  return assign_launch<true>("od_assign_anchors_ign", ctx, priors, gt_boxes, gt_classes, gt_counts, gt_flags, B, P, Gmax,
+                             NC, pos_thr, neg_thr, ign_thr, loc_scale, y, assigned_gt, npos, workspace, workspace_bytes,
+                             stream);
 }

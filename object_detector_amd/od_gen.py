@@ -8,6 +8,21 @@ constrained so that boxes are not hidden too much): horizontal flip, random crop
 brightness / contrast / saturation jitter, Random Erasing limited to <= 40 % of any box.  Augmentation PARAMETERS are
 sampled on the host (numpy Generator, seeded); the pixel work runs on the device through od_augment_batch when a GPU
 is present (`device=`), prior-box encoding always runs on the device (encode_truth = od.pb.encode_truth).
+
+Mosaic [BUILD-DEFINED, opt-in: `create_generator(..., mosaic=P, device=...)`]: with probability P an output image is
+composed of four images (the batch's own + three drawn from the whole dataset) around a split point; the pixel work is one
+od_augment_mosaic launch that gathers from the four sources where they live (device_cache: in HBM).  The numbers, all named
+arguments of `sample_mosaic` with these defaults:
+  split_range = (0.3, 0.7)  the split point is uniform over this part of the frame, per axis, in whole output pixels
+  max_aspect  = 1.5         a tile's crop is narrowed about its centre (widened on the other axis only where it would
+                            get thinner than a source pixel) until x-scale / y-scale of the tile lies in [1/1.5, 1.5]
+  drop_frac   = 0.1         a box of which less than this share stays inside its tile is dropped
+  ignore_frac = 0.4         below this share (and >= drop_frac) the box is a sliver: kept as an ignore region
+                            (difficults = True) if ignore_regions=True, dropped otherwise -- never trained as a positive
+  min_px      = 2.0         a clipped box thinner than this many output pixels is dropped
+Each tile gets its own `sample_params` draw (crop / flip / colour, no erasing); Random Erasing acts once on the whole frame.
+More than pb.GMAX boxes after merging: ignore regions go first, smallest area first, then ordinary boxes, smallest first.
+`Generator.stats` counts mosaics, boxes_dropped, boxes_ignored, boxes_over_gmax.
 """
 from __future__ import annotations
 
@@ -15,7 +30,7 @@ import math
 
 import numpy as np
 
-from .pb import ObjectsAnnotation
+from .pb import GMAX, ObjectsAnnotation
 
 
 class AugParams:
@@ -47,18 +62,24 @@ def sample_params(rng: np.random.Generator, ann: ObjectsAnnotation, random_erasi
     p.contrast = float(rng.uniform(0.6, 1.4)) if rng.random() < 0.5 else 1.0
     p.saturation = float(rng.uniform(0.6, 1.4)) if rng.random() < 0.5 else 1.0
     if random_erasing and rng.random() < 0.5:
-        nb = transform_boxes(b, p)
-        for _ in range(int(rng.integers(1, 4))):
-            for _try in range(10):
-                area = rng.uniform(0.02, 0.2)
-                ar = math.exp(rng.uniform(math.log(0.3), math.log(1 / 0.3)))
-                w, h = min(1.0, math.sqrt(area * ar)), min(1.0, math.sqrt(area / ar))
-                x1, y1 = rng.uniform(0, 1 - w), rng.uniform(0, 1 - h)
-                r = np.array([x1, y1, x1 + w, y1 + h], np.float32)
-                if _hidden_fraction(r, nb) <= 0.4:  # box-aware constraint
-                    p.erase.append((tuple(float(v) for v in r), tuple(int(v) for v in rng.integers(0, 256, 3))))
-                    break
+        p.erase = _sample_erase(rng, transform_boxes(b, p))
     return p
+
+
+def _sample_erase(rng, nb):
+    """1-3 Random-Erasing rectangles in normalised output coordinates, none hiding more than 40 % of a box of `nb`."""
+    erase = []
+    for _ in range(int(rng.integers(1, 4))):
+        for _try in range(10):
+            area = rng.uniform(0.02, 0.2)
+            ar = math.exp(rng.uniform(math.log(0.3), math.log(1 / 0.3)))
+            w, h = min(1.0, math.sqrt(area * ar)), min(1.0, math.sqrt(area / ar))
+            x1, y1 = rng.uniform(0, 1 - w), rng.uniform(0, 1 - h)
+            r = np.array([x1, y1, x1 + w, y1 + h], np.float32)
+            if _hidden_fraction(r, nb) <= 0.4:  # box-aware constraint
+                erase.append((tuple(float(v) for v in r), tuple(int(v) for v in rng.integers(0, 256, 3))))
+                break
+    return erase
 
 
 def _hidden_fraction(rect, boxes):
@@ -70,15 +91,152 @@ def _hidden_fraction(rect, boxes):
     return float((iw * ih / area).max())
 
 
-def transform_boxes(bboxes, p: AugParams):
-    """Boxes follow the crop then the flip; clipped to the frame."""
+def transform_boxes(bboxes, p: AugParams, clip=True):
+    """Boxes follow the crop then the flip; clipped to the frame (clip=False: as they fall, for the visible share)."""
     b = np.asarray(bboxes, np.float32).reshape(-1, 4).copy()
     x1, y1, x2, y2 = p.crop
     b[:, [0, 2]] = (b[:, [0, 2]] - x1) / (x2 - x1)
     b[:, [1, 3]] = (b[:, [1, 3]] - y1) / (y2 - y1)
     if p.flip:
         b[:, [0, 2]] = 1.0 - b[:, [2, 0]]
-    return np.clip(b, 0.0, 1.0)
+    return np.clip(b, 0.0, 1.0) if clip else b
+
+
+class MosaicParams:
+    """One mosaic output image: the split point in output pixels, the four tiles' parameters (TL, TR, BL, BR; no erasing
+    of their own) and the whole-frame erase list."""
+    __slots__ = ("split", "tiles", "erase")
+
+    def __init__(self, split, tiles, erase=()):
+        self.split = (int(split[0]), int(split[1]))  # (split_x, split_y)
+        self.tiles = list(tiles)
+        self.erase = list(erase)
+
+    @classmethod
+    def single(cls, p: AugParams, input_size):
+        """The degenerate mosaic of one image: split = (W, H), p in the TL tile, p's erase list on the frame -- the output
+        of od_augment_mosaic equals od_augment_batch(p) byte for byte."""
+        q = AugParams()
+        q.crop, q.flip, q.brightness, q.contrast, q.saturation = p.crop, p.flip, p.brightness, p.contrast, p.saturation
+        return cls((input_size[1], input_size[0]), [q, AugParams(), AugParams(), AugParams()], p.erase)
+
+
+def tile_rects(split, input_size):
+    """-> the four tiles' (X0, Y0, Wt, Ht) in output pixels: TL, TR, BL, BR."""
+    H, W = input_size
+    sx, sy = split
+    return [(0, 0, sx, sy), (sx, 0, W - sx, sy), (0, sy, sx, H - sy), (sx, sy, W - sx, H - sy)]
+
+
+def _span(a, b, new_len):
+    """[a, b] resized to new_len (<= 1) about its centre, shifted back into [0, 1]."""
+    new_len = min(float(new_len), 1.0)
+    c = 0.5 * (a + b)
+    a, b = c - 0.5 * new_len, c + 0.5 * new_len
+    if a < 0.0:
+        a, b = 0.0, new_len
+    if b > 1.0:
+        a, b = 1.0 - new_len, 1.0
+    return a, b
+
+
+def fit_tile_aspect(crop, src_wh, tile_wh, max_aspect=1.5):
+    """Crop (normalised source coordinates) whose picture, stretched over a tile of tile_wh pixels, is distorted by at most
+    max_aspect: d = x-scale / y-scale in [1/max_aspect, max_aspect].  The crop is NARROWED about its centre on the axis that
+    is squeezed -- a mosaic tile is a cut-out of its image, and what the cut leaves of an object is what mosaic_boxes
+    weighs -- and only a crop that would become thinner than one source pixel is widened on the other axis instead."""
+    x1, y1, x2, y2 = (float(v) for v in crop)
+    sw, sh = max(1.0, float(src_wh[0])), max(1.0, float(src_wh[1]))
+    tw, th = float(tile_wh[0]), float(tile_wh[1])
+    if tw <= 0 or th <= 0:
+        return (x1, y1, x2, y2)
+    d = (tw / ((x2 - x1) * sw)) / (th / ((y2 - y1) * sh))
+    if d > max_aspect:      # stretched in x: show less of the source's height
+        want = (y2 - y1) * max_aspect / d
+        if want * sh >= 1.0:
+            y1, y2 = _span(y1, y2, want)
+        else:
+            x1, x2 = _span(x1, x2, (x2 - x1) * d / max_aspect)
+    elif d < 1.0 / max_aspect:
+        want = (x2 - x1) * d * max_aspect
+        if want * sw >= 1.0:
+            x1, x2 = _span(x1, x2, want)
+        else:
+            y1, y2 = _span(y1, y2, (y2 - y1) / (d * max_aspect))
+    return (x1, y1, x2, y2)
+
+
+def mosaic_boxes(anns4, tiles, split, input_size, drop_frac=0.1, ignore_frac=0.4, min_px=2.0, ignore_regions=False,
+                 gmax=GMAX, stats=None):
+    """The merged annotation of a mosaic: every box follows its tile (transform_boxes into tile coordinates, through the
+    tile rectangle into output coordinates, clipped to the tile), then visible = clipped area / unclipped area decides:
+    < drop_frac or thinner than min_px output pixels -> dropped; < ignore_frac -> an ignore region (difficults = True) with
+    ignore_regions, dropped without; else kept.  Input difficults are carried through.  More than gmax boxes: flagged
+    boxes go first, smallest area first, then unflagged ones, smallest first (ties: lowest index)."""
+    H, W = input_size
+    st = stats if stats is not None else {}
+    rows = []  # the tiles that show objects: (annotation, per-box row of tile numbers)
+    for a, p, (X0, Y0, Wt, Ht) in zip(anns4, tiles, tile_rects(split, input_size)):
+        if a.num_objects == 0:
+            continue
+        if Wt <= 0 or Ht <= 0:  # an empty tile shows nothing
+            st["boxes_dropped"] = st.get("boxes_dropped", 0) + a.num_objects
+            continue
+        x1, y1, x2, y2 = p.crop
+        rows.append((a, (x1, y1, x2 - x1, y2 - y1, float(p.flip), X0, Y0, Wt, Ht)))
+    if not rows:
+        return ObjectsAnnotation(anns4[0].path, W, H)
+    # all tiles' boxes in one pass (float64; the arithmetic of transform_boxes, unclipped and clipped)
+    t = np.repeat(np.array([r[1] for r in rows], np.float64), [r[0].num_objects for r in rows], axis=0)
+    b = np.concatenate([r[0].bboxes for r in rows]).astype(np.float64)
+    rx = (b[:, [0, 2]] - t[:, 0:1]) / t[:, 2:3]
+    ry = (b[:, [1, 3]] - t[:, 1:2]) / t[:, 3:4]
+    rx = np.where(t[:, 4:5] > 0, 1.0 - rx[:, ::-1], rx)
+    cx, cy = np.clip(rx, 0.0, 1.0), np.clip(ry, 0.0, 1.0)
+    area_raw = (rx[:, 1] - rx[:, 0]) * (ry[:, 1] - ry[:, 0])
+    area_cl = (cx[:, 1] - cx[:, 0]) * (cy[:, 1] - cy[:, 0])
+    visible = np.where(area_raw > 0, area_cl / np.where(area_raw > 0, area_raw, 1.0), 0.0)
+    thin = ((cx[:, 1] - cx[:, 0]) * t[:, 7] < min_px) | ((cy[:, 1] - cy[:, 0]) * t[:, 8] < min_px)
+    drop = thin | (visible < drop_frac)
+    sliver = ~drop & (visible < ignore_frac)
+    if not ignore_regions:
+        drop, sliver = drop | sliver, np.zeros(len(b), bool)
+    st["boxes_dropped"] = st.get("boxes_dropped", 0) + int(drop.sum())
+    st["boxes_ignored"] = st.get("boxes_ignored", 0) + int(sliver.sum())
+    out = np.stack([(t[:, 5] + cx[:, 0] * t[:, 7]) / W, (t[:, 6] + cy[:, 0] * t[:, 8]) / H,
+                    (t[:, 5] + cx[:, 1] * t[:, 7]) / W, (t[:, 6] + cy[:, 1] * t[:, 8]) / H], 1)
+    merged = ObjectsAnnotation(anns4[0].path, W, H, np.concatenate([r[0].classes for r in rows]), np.clip(out, 0.0, 1.0),
+                               np.concatenate([r[0].difficults for r in rows]) | sliver).select(~drop)
+    over = merged.num_objects - gmax
+    if over > 0:
+        b = merged.bboxes.astype(np.float64)
+        area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+        order = np.lexsort((np.arange(len(area)), area, ~merged.difficults))  # flagged first, then area, then index
+        keep = np.ones(len(area), bool)
+        keep[order[:over]] = False
+        merged = merged.select(keep)
+        st["boxes_over_gmax"] = st.get("boxes_over_gmax", 0) + int(over)
+    return merged
+
+
+def sample_mosaic(rng: np.random.Generator, anns4, input_size, random_erasing=True, split_range=(0.3, 0.7), max_aspect=1.5,
+                  drop_frac=0.1, ignore_frac=0.4, min_px=2.0, ignore_regions=False, gmax=GMAX, stats=None):
+    """Four annotations (TL, TR, BL, BR) -> (MosaicParams, merged ObjectsAnnotation in output coordinates).  Draws, in this
+    order: split_x, split_y, the four tiles' sample_params (erasing off), then the whole-frame erase list."""
+    H, W = input_size
+    assert len(anns4) == 4
+    sx = int(rng.integers(max(1, int(round(split_range[0] * W))), min(W, int(round(split_range[1] * W))) + 1))
+    sy = int(rng.integers(max(1, int(round(split_range[0] * H))), min(H, int(round(split_range[1] * H))) + 1))
+    tiles = []
+    for a, (_x0, _y0, Wt, Ht) in zip(anns4, tile_rects((sx, sy), input_size)):
+        p = sample_params(rng, a, random_erasing=False)
+        p.crop = fit_tile_aspect(p.crop, (a.width or 1, a.height or 1), (Wt, Ht), max_aspect)
+        tiles.append(p)
+    merged = mosaic_boxes(anns4, tiles, (sx, sy), input_size, drop_frac, ignore_frac, min_px, ignore_regions, gmax, stats)
+    erase = _sample_erase(rng, merged.bboxes) if random_erasing and rng.random() < 0.5 else []
+    if stats is not None:
+        stats["mosaics"] = stats.get("mosaics", 0) + 1
+    return MosaicParams((sx, sy), tiles, erase), merged
 
 
 def apply_pixels_host(img_u8: np.ndarray, p: AugParams, out_hw) -> np.ndarray:
@@ -103,6 +261,87 @@ def apply_pixels_host(img_u8: np.ndarray, p: AugParams, out_hw) -> np.ndarray:
     for (ex1, ey1, ex2, ey2), col in p.erase:
         a[int(ey1 * H):int(math.ceil(ey2 * H)), int(ex1 * W):int(math.ceil(ex2 * W))] = col
     return a
+
+
+def _fill_aug(q, p: AugParams, offset, src_h, src_w):
+    q.src_offset, q.src_h, q.src_w = offset, src_h, src_w
+    q.crop_x1, q.crop_y1, q.crop_x2, q.crop_y2 = p.crop
+    q.flip, q.brightness, q.contrast, q.saturation = int(p.flip), p.brightness, p.contrast, p.saturation
+
+
+def _fill_erase(q, erase):
+    q.n_erase = min(3, len(erase))
+    for e, (rect, col) in enumerate(erase[:3]):
+        for k in range(4):
+            q.erase[e][k] = rect[k]
+        for k in range(3):
+            q.erase_rgb[e][k] = col[k]
+
+
+def apply_mosaic_device(images, params, out_hw, device):
+    """K14, four sources per output image: images = list of B 4-tuples (TL, TR, BL, BR) of uint8 [h,w,3] host arrays or
+    uint8 DEVICE tensors (None for a tile that is empty or unused: it is never sampled) + list[MosaicParams] -> uint8
+    torch tensor [B,H,W,3] on `device` through od_augment_mosaic.  Device tensors are read where they are: one base pointer
+    and a SIGNED 64-bit offset per tile, so the sources may lie anywhere in the device's address space."""
+    import torch
+
+    from . import _lib
+    from .net import Context, _stream_ptr
+    ctx = Context.get(device)
+    H, Wd = out_hw
+    B = len(images)
+    arr = (_lib.MosaicParams * B)()
+    flat = [im for quad in images for im in quad if im is not None]
+    resident = len(flat) > 0 and all(isinstance(im, torch.Tensor) for im in flat)
+    if not flat or (not resident and any(isinstance(im, torch.Tensor) for im in flat)):
+        raise ValueError("apply_mosaic_device: sources must be all host arrays or all device tensors, at least one")
+    base = flat[0].data_ptr() if resident else 0
+    off, chunks, packed_at = 0, [], {}
+    for i, (quad, mp) in enumerate(zip(images, params)):
+        q = arr[i]
+        sx, sy = mp.split
+        if not (1 <= sx <= Wd and 1 <= sy <= H):
+            raise ValueError(f"mosaic split {mp.split} outside [1, {Wd}] x [1, {H}]")
+        q.split_x, q.split_y = sx, sy
+        first = None
+        for t, (X0, Y0, Wt, Ht) in enumerate(tile_rects((sx, sy), out_hw)):
+            img, p = quad[t], mp.tiles[t]
+            if Wt > 0 and Ht > 0:
+                if img is None:
+                    raise ValueError(f"image {i}: tile {t} is {Wt}x{Ht} pixels but has no source")
+                if p.erase:
+                    raise ValueError("a mosaic tile carries no erase list of its own (MosaicParams.erase acts on the frame)")
+            if img is None:  # never sampled: any valid source will do
+                img = first if first is not None else next(im for im in quad if im is not None)
+            first = img if first is None else first
+            if resident:
+                assert img.is_cuda and img.dtype == torch.uint8 and img.is_contiguous() and img.shape[-1] == 3
+                this_off, sh, sw = img.data_ptr() - base, img.shape[0], img.shape[1]
+            else:
+                if id(img) not in packed_at:  # one copy of an image however many tiles show it
+                    a = np.ascontiguousarray(img[..., :3], np.uint8)
+                    packed_at[id(img)] = (off, a.shape[0], a.shape[1])
+                    chunks.append((off, a.reshape(-1)))
+                    off += (a.size + 15) // 16 * 16
+                this_off, sh, sw = packed_at[id(img)]
+            _fill_aug(q.tile[t], p, this_off, sh, sw)
+            q.tile[t].n_erase = 0
+        _fill_erase(q, mp.erase)
+    dev = torch.device(device)
+    if resident:
+        src_ptr, src = base, flat
+    else:
+        packed = np.zeros(off, np.uint8)
+        for o, c in chunks:
+            packed[o:o + c.size] = c
+        src = torch.from_numpy(packed).to(dev)
+        src_ptr = src.data_ptr()
+    prm = torch.from_numpy(np.frombuffer(bytes(arr), np.uint8).copy()).to(dev)
+    out = torch.empty((B, H, Wd, 3), dtype=torch.uint8, device=dev)
+    _lib.check(ctx.lib.od_augment_mosaic(ctx.handle, src_ptr, prm.data_ptr(), out.data_ptr(), B, H, Wd, _stream_ptr()),
+               "od_augment_mosaic")
+    del src
+    return out
 
 
 def apply_pixels_device(images, params, out_hw, device):
@@ -131,16 +370,8 @@ def apply_pixels_device(images, params, out_hw, device):
             a = np.ascontiguousarray(img[..., :3], np.uint8)
             chunks.append(a.reshape(-1))
             this_off = off
-        q = arr[i]
-        q.src_offset, q.src_h, q.src_w = this_off, a.shape[0], a.shape[1]
-        q.crop_x1, q.crop_y1, q.crop_x2, q.crop_y2 = p.crop
-        q.flip, q.brightness, q.contrast, q.saturation = int(p.flip), p.brightness, p.contrast, p.saturation
-        q.n_erase = min(3, len(p.erase))
-        for e, (rect, col) in enumerate(p.erase[:3]):
-            for k in range(4):
-                q.erase[e][k] = rect[k]
-            for k in range(3):
-                q.erase_rgb[e][k] = col[k]
+        _fill_aug(arr[i], p, this_off, a.shape[0], a.shape[1])
+        _fill_erase(arr[i], p.erase)
         if not resident:
             off += (a.size + 15) // 16 * 16
     dev = torch.device(device)
@@ -162,7 +393,7 @@ def apply_pixels_device(images, params, out_hw, device):
 
 class Generator:
     def __init__(self, input_size, preprocess_input=None, encode_truth=None, random_erasing=True, device=None, workers=None,
-                 on_device=False, device_cache=False):
+                 on_device=False, device_cache=False, mosaic=0.0, ignore_regions=False, mosaic_args=None):
         # device_cache (needs device=): every image is decoded and uploaded ONCE and stays in HBM as a uint8 tensor; from the
         # second epoch on a batch costs the host only its augmentation parameters.  VOC07+12 trainval decoded is ~9 GB --
         # a few per cent of one MI355X's 288 GB -- so the dataset lives where the augmentation kernel reads it.
@@ -176,6 +407,18 @@ class Generator:
         self.on_device = bool(on_device)
         if self.on_device and device is None:
             raise ValueError("on_device=True needs device=")
+        # mosaic (needs device=): the probability that an output image of flow(data_augmentation=True) is composed of four
+        # images (module docstring); ignore_regions: what becomes of a sliver a tile border leaves of an object -- an ignore
+        # region (difficults = True; the PriorBoxes must be built with ignore_regions=True as well) or nothing.
+        # mosaic_args: sample_mosaic's named numbers (split_range, max_aspect, drop_frac, ignore_frac, min_px, gmax).
+        self.mosaic = float(mosaic)
+        if not 0.0 <= self.mosaic <= 1.0:
+            raise ValueError(f"mosaic is a probability, got {mosaic!r}")
+        if self.mosaic > 0.0 and device is None:
+            raise ValueError("mosaic > 0 needs device= (the composition is od_augment_mosaic; there is no host path)")
+        self.ignore_regions = bool(ignore_regions)
+        self.mosaic_args = dict(mosaic_args or {})
+        self.stats = {"mosaics": 0, "boxes_dropped": 0, "boxes_ignored": 0, "boxes_over_gmax": 0}
         self.input_size = tuple(int(v) for v in input_size)
         self.preprocess_input = preprocess_input
         self.encode_truth = encode_truth
@@ -244,6 +487,43 @@ class Generator:
                     out.append(im)
                 return out
 
+            def plain_annotation(i, p):
+                return ObjectsAnnotation(y[i].path, self.input_size[1], self.input_size[0], y[i].classes,
+                                         transform_boxes(y[i].bboxes, p), y[i].difficults)
+
+            def draw_with_mosaic(idx):
+                """Per output image, in index order: one uniform draw decides; a mosaic then draws its three partners from
+                the whole dataset and its parameters (sample_mosaic), any other image its sample_params as always."""
+                prm, mos = [], []
+                for i in idx:
+                    if rng.random() < self.mosaic:
+                        four = [int(i)] + [int(j) for j in rng.integers(0, n, 3)]
+                        mp, ann = sample_mosaic(rng, [y[j] for j in four], self.input_size, self.random_erasing,
+                                                ignore_regions=self.ignore_regions, stats=self.stats, **self.mosaic_args)
+                        prm.append(None), mos.append((four, mp, ann))
+                    else:
+                        prm.append(sample_params(rng, y[i], self.random_erasing)), mos.append(None)
+                return prm, mos
+
+            def compose(idx, raw, prm, mos):
+                """One od_augment_mosaic launch for the whole batch; an image that is no mosaic rides along as the
+                degenerate one (byte-identical to od_augment_batch).  Partner images come through fetch / to_resident."""
+                partners = [j for m in mos if m is not None for j in m[0][1:]]
+                got = [f.result() for f in [fetch(j) for j in partners]]
+                if resident is not None:
+                    got = to_resident(partners, got)
+                got = iter(got)
+                quads, mps, anns = [], [], []
+                for i, im, p, m in zip(idx, raw, prm, mos):
+                    if m is None:
+                        quads.append((im, None, None, None))
+                        mps.append(MosaicParams.single(p, self.input_size))
+                        anns.append(plain_annotation(i, p))
+                    else:
+                        quads.append((im, next(got), next(got), next(got)))
+                        mps.append(m[1]), anns.append(m[2])
+                return apply_mosaic_device(quads, mps, self.input_size, self.device), anns
+
             while True:
                 order = rng.permutation(n) if shuffle else np.arange(n)
                 batches = [order[s:s + batch_size] for s in range(0, n, batch_size)]
@@ -253,8 +533,18 @@ class Generator:
                     raw = [f.result() for f in futs] if futs is not None else [self._load(X[i]) for i in idx]
                     if resident is not None:
                         raw = to_resident(idx, raw)
-                    prm = [sample_params(rng, y[i], self.random_erasing) if data_augmentation else AugParams() for i in idx]
-                    if self.device is not None:
+                    mos = None
+                    if self.mosaic > 0.0 and data_augmentation:
+                        prm, mos = draw_with_mosaic(idx)
+                        if not any(m is not None for m in mos):
+                            mos = None
+                    else:  # not one draw more than before mosaic existed: the stream of batches is unchanged
+                        prm = [sample_params(rng, y[i], self.random_erasing) if data_augmentation else AugParams() for i in idx]
+                    if mos is not None:
+                        xb, anns = compose(idx, raw, prm, mos)
+                        if not self.on_device:
+                            xb = xb.cpu().numpy()
+                    elif self.device is not None:
                         xb = apply_pixels_device(raw, prm, self.input_size, self.device)
                         if not self.on_device:
                             xb = xb.cpu().numpy()
@@ -262,9 +552,8 @@ class Generator:
                         xb = np.stack(list(pool.map(lambda ip: apply_pixels_host(ip[0], ip[1], self.input_size), zip(raw, prm))))
                     else:
                         xb = np.stack([apply_pixels_host(img, p, self.input_size) for img, p in zip(raw, prm)])
-                    anns = [ObjectsAnnotation(y[i].path, self.input_size[1], self.input_size[0], y[i].classes,
-                                              transform_boxes(y[i].bboxes, p), y[i].difficults)
-                            for i, p in zip(idx, prm)]
+                    if mos is None:
+                        anns = [plain_annotation(i, p) for i, p in zip(idx, prm)]
                     if self.preprocess_input is not None:
                         xb = self.preprocess_input(xb)
                     yb = self.encode_truth(list(anns)) if self.encode_truth is not None else list(anns)

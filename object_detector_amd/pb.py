@@ -2,6 +2,11 @@
 
 `decode_locs(locs, xp=np)` and `encode_truth(y)` keep the reference call shapes; both run the HIP kernels
 (od_decode_locs / od_assign_anchors) and hand numpy arrays back, exactly what check_assign.py consumes.
+
+`PriorBoxes(..., ignore_regions=True)` [BUILD-DEFINED, opt-in]: `ObjectsAnnotation.difficults` (COCO iscrowd, VOC difficult,
+a sliver a mosaic tile border left of an object) marks ignore regions, as both evaluators treat them.  Such a box owns no
+prior, and a prior that would be background is not trained on (all-zero target row) when at least `ign_thr` of ITS area lies
+inside a region (od_assign_anchors_ign).  IGN_THR = 0.5 is a policy value of this build, not a tolerance.
 """
 from __future__ import annotations
 
@@ -14,6 +19,7 @@ from . import _lib, priors as PR
 from .net import Context, _stream_ptr
 
 POS_THR, NEG_THR, LOC_SCALE = 0.5, 0.4, 0.1
+IGN_THR = 0.5
 GMAX = 128
 
 
@@ -33,15 +39,27 @@ class ObjectsAnnotation:
     def num_objects(self):
         return len(self.classes)
 
+    def select(self, keep, bboxes=None, difficults=None, width=None, height=None):
+        """The objects `keep` (bool mask or indices) names: classes, boxes and difficult flags are filtered TOGETHER, so a
+        dropped box never shifts another box's flag.  bboxes / difficults (full length) replace the stored ones first."""
+        b = self.bboxes if bboxes is None else np.asarray(bboxes, np.float32).reshape(-1, 4)
+        d = self.difficults if difficults is None else np.asarray(difficults, bool).reshape(-1)
+        assert len(b) == len(d) == len(self.classes)
+        return ObjectsAnnotation(self.path, self.width if width is None else width, self.height if height is None else height,
+                                 self.classes[keep], b[keep], d[keep])
+
 
 class PriorBoxes:
     def __init__(self, input_size=(320, 320), num_classes=20, prior_wh=PR.DEFAULT_PRIOR_WH, device="cuda:0",
-                 pos_thr=POS_THR, neg_thr=NEG_THR, loc_scale=LOC_SCALE):
+                 pos_thr=POS_THR, neg_thr=NEG_THR, loc_scale=LOC_SCALE, ignore_regions=False, ign_thr=IGN_THR):
         self.input_size = tuple(int(v) for v in input_size)
         self.num_classes = int(num_classes)
         self.prior_wh = np.asarray(prior_wh, np.float64)
         self.pb_locs = PR.make_priors(self.input_size, self.prior_wh)  # f32 [P,4]
         self.pos_thr, self.neg_thr, self.loc_scale = float(pos_thr), float(neg_thr), float(loc_scale)
+        self.ignore_regions, self.ign_thr = bool(ignore_regions), float(ign_thr)
+        if self.ignore_regions and not self.ign_thr > 0.0:
+            raise ValueError(f"ign_thr must be > 0, got {ign_thr!r}")
         self.device = torch.device(device)
         self._ctx = None
         self._priors_dev = None
@@ -75,7 +93,9 @@ class PriorBoxes:
         return out
 
     def encode_batch(self, annotations, return_device=False):
-        """list[ObjectsAnnotation] -> y f32 [B,P,2+NC+4] (+ npos [B]) through od_assign_anchors."""
+        """list[ObjectsAnnotation] -> y f32 [B,P,2+NC+4] (+ npos [B], assigned [B,P]) through od_assign_anchors, or, with
+        ignore_regions=True, through od_assign_anchors_ign with `difficults` as the region flags (assigned -3 = ignored by a
+        region)."""
         ctx = self._ensure()
         B, P, NC = len(annotations), len(self.pb_locs), self.num_classes
         gmax = max(1, max((a.num_objects for a in annotations), default=1))
@@ -84,9 +104,12 @@ class PriorBoxes:
         gb = np.zeros((B, gmax, 4), np.float32)
         gc = np.zeros((B, gmax), np.int32)
         gn = np.zeros((B,), np.int32)
+        gf = np.zeros((B, gmax), np.int32) if self.ignore_regions else None
         for i, a in enumerate(annotations):
             n = a.num_objects
             gb[i, :n], gc[i, :n], gn[i] = a.bboxes, a.classes, n
+            if gf is not None:
+                gf[i, :n] = a.difficults
         dev = self.device
         gb_t, gc_t, gn_t = (torch.from_numpy(v).to(dev) for v in (gb, gc, gn))
         y = torch.empty((B, P, NC + 6), dtype=torch.float32, device=dev)
@@ -94,6 +117,16 @@ class PriorBoxes:
         assigned = torch.empty((B, P), dtype=torch.int32, device=dev)
         wsb = ctx.lib.od_assign_workspace_bytes(B, P, gmax)
         ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+        if gf is not None:
+            gf_t = torch.from_numpy(gf).to(dev)
+            _lib.check(ctx.lib.od_assign_anchors_ign(ctx.handle, self._priors_dev.data_ptr(), gb_t.data_ptr(), gc_t.data_ptr(),
+                                                     gn_t.data_ptr(), gf_t.data_ptr(), self.ign_thr, B, P, gmax, NC,
+                                                     self.pos_thr, self.neg_thr, self.loc_scale, y.data_ptr(),
+                                                     assigned.data_ptr(), npos.data_ptr(), ws.data_ptr(), wsb, _stream_ptr()),
+                       "od_assign_anchors_ign")
+            if return_device:
+                return y, npos, assigned
+            return y.cpu().numpy(), npos.cpu().numpy(), assigned.cpu().numpy()
         _lib.check(ctx.lib.od_assign_anchors(ctx.handle, self._priors_dev.data_ptr(), gb_t.data_ptr(), gc_t.data_ptr(),
                                              gn_t.data_ptr(), B, P, gmax, NC, self.pos_thr, self.neg_thr,
                                              self.loc_scale, y.data_ptr(), assigned.data_ptr(), npos.data_ptr(),

@@ -44,7 +44,7 @@ class Trainer:
     def __init__(self, params, batch_size, input_size=(320, 320), device="cuda:0", lr=1e-3, momentum=0.9,
                  weight_decay=0.0, loss_scale=1024.0, box_mode="smooth_l1", backbone_act=("leaky", 0.1),
                  head_act=("elu", 1.0), comm=None, world_size=1, grad_payload=None, dynamic_loss_scale=True,
-                 lr_multipliers=None, prior_wh=None):
+                 lr_multipliers=None, prior_wh=None, ignore_regions=False, ign_thr=None):
         self.ctx = Context.get(device)
         self.lib = self.ctx.lib
         self.device = torch.device(device)
@@ -71,8 +71,11 @@ class Trainer:
         self.loss_scale_growth_interval = 2000
         # prior_wh: the [3, 8, 2] table of prior sizes in grid-cell units (priors.fit: KMeans over the training boxes,
         # docs/MODEL.md:29-31); None = the frozen default table
-        self.pb = PriorBoxes((self.H0, self.W0), self.num_classes, device=self.device,
-                             **({} if prior_wh is None else {"prior_wh": prior_wh}))
+        # ignore_regions / ign_thr: handed to the PriorBoxes (pb.py): annotations' `difficults` become ignore regions in
+        # step(x, annotations=...) and in tr.pb.encode_truth_device, the generator callback
+        self.pb = PriorBoxes((self.H0, self.W0), self.num_classes, device=self.device, ignore_regions=ignore_regions,
+                             **({} if prior_wh is None else {"prior_wh": prior_wh}),
+                             **({} if ign_thr is None else {"ign_thr": ign_thr}))
         self.P = len(self.pb)
         dev = self.device
 

@@ -41,11 +41,16 @@ SHAPE_CLASSES = (1, 6, 7, 11, 14)  # bicycle, car, cat, dog, person
 SHAPE_COLOURS = ((220, 40, 40), (40, 200, 60), (50, 80, 230), (230, 210, 40), (200, 60, 210))
 
 
-def shapes_dataset(n, seed=0, size_range=(240, 400)):
-    """-> (X: object array of uint8 [h,w,3] images, y: object array of ObjectsAnnotation)."""
+def shapes_dataset(n, seed=0, size_range=(240, 400), difficult_frac=0.0, crowd_frac=0.0):
+    """-> (X: object array of uint8 [h,w,3] images, y: object array of ObjectsAnnotation).
+    difficult_frac: this share of the objects is marked `difficult` and drawn half faded into the background (VOC's hard
+    objects); crowd_frac: this share of the images gets a "crowd" -- a cluster of 6-12 small shapes of one class under ONE
+    loose box marked difficult, the way COCO annotates iscrowd regions.  Both are drawn from a generator of their own: the
+    images and boxes of the default call do not depend on them."""
     from scipy.ndimage import uniform_filter
     from object_detector_amd.pb import ObjectsAnnotation
     rng = np.random.default_rng(seed)
+    marks = np.random.default_rng([int(seed), 0x1646]) if (difficult_frac > 0 or crowd_frac > 0) else None
     X, y = [], []
     for _ in range(n):
         h, w = (int(v) for v in rng.integers(size_range[0], size_range[1] + 1, 2))
@@ -70,8 +75,35 @@ def shapes_dataset(n, seed=0, size_range=(240, 400)):
             img[px[1]:px[3], px[0]:px[2]] = col + 10.0 * rng.standard_normal((px[3] - px[1], px[2] - px[0], 3), dtype=np.float32)
             boxes.append(np.array([px[0] / w, px[1] / h, px[2] / w, px[3] / h]))
             classes.append(SHAPE_CLASSES[ci])
+        difficults = [False] * len(boxes)
+        if marks is not None:
+            for k, b in enumerate(boxes):
+                if marks.random() < difficult_frac:
+                    px = (int(round(b[0] * w)), int(round(b[1] * h)), int(round(b[2] * w)), int(round(b[3] * h)))
+                    reg = (slice(px[1], px[3]), slice(px[0], px[2]))
+                    img[reg] = 0.5 * img[reg] + 0.5 * bg[reg]
+                    difficults[k] = True
+            if marks.random() < crowd_frac:
+                for _try in range(20):
+                    bw, bh = marks.uniform(0.25, 0.45, 2)
+                    x1, y1 = marks.uniform(0.02, 0.98 - bw), marks.uniform(0.02, 0.98 - bh)
+                    b = np.array([x1, y1, x1 + bw, y1 + bh])
+                    if all(_iou(b, o) < 0.05 for o in boxes):
+                        break
+                else:
+                    b = None
+                if b is not None:
+                    ci = int(marks.integers(0, len(SHAPE_CLASSES)))
+                    for _k in range(int(marks.integers(6, 13))):
+                        sw, sh = marks.uniform(0.04, 0.08, 2)
+                        sx, sy = marks.uniform(b[0], b[2] - sw), marks.uniform(b[1], b[3] - sh)
+                        px = (int(round(sx * w)), int(round(sy * h)), int(round((sx + sw) * w)), int(round((sy + sh) * h)))
+                        img[px[1]:px[3], px[0]:px[2]] = np.asarray(SHAPE_COLOURS[ci], np.float64) * marks.uniform(0.85, 1.0)
+                    boxes.append(b)
+                    classes.append(SHAPE_CLASSES[ci])
+                    difficults.append(True)
         X.append(np.clip(np.rint(img), 0, 255).astype(np.uint8))
-        y.append(ObjectsAnnotation(None, w, h, classes, np.asarray(boxes, np.float32)))
+        y.append(ObjectsAnnotation(None, w, h, classes, np.asarray(boxes, np.float32), difficults))
     Xa = np.empty(n, dtype=object)
     Xa[:] = X
     return Xa, np.array(y, dtype=object)
@@ -99,8 +131,8 @@ def write_voc_layout(vocdevkit_dir, X, y, image_set="test", year=2007, fmt="png"
         h, w = img.shape[:2]
         Image.fromarray(img).save(base / "JPEGImages" / f"{name}.{fmt}", **({"quality": 95} if fmt == "jpg" else {}))
         objs = ""
-        for c, b in zip(a.classes, a.bboxes):  # VOC pixels are 1-based inclusive (tk.data.voc.load_annotation undoes this)
-            objs += (f"<object><name>{CLASS_NAMES[int(c)]}</name><difficult>0</difficult><bndbox>"
+        for c, b, d in zip(a.classes, a.bboxes, a.difficults):  # VOC pixels are 1-based inclusive (load_annotation undoes this)
+            objs += (f"<object><name>{CLASS_NAMES[int(c)]}</name><difficult>{int(d)}</difficult><bndbox>"
                      f"<xmin>{int(round(b[0] * w)) + 1}</xmin><ymin>{int(round(b[1] * h)) + 1}</ymin>"
                      f"<xmax>{int(round(b[2] * w))}</xmax><ymax>{int(round(b[3] * h))}</ymax></bndbox></object>\n")
         (base / "Annotations" / f"{name}.xml").write_text(

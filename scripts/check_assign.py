@@ -17,6 +17,9 @@ def _main():
     p.add_argument("--weights", default=None, type=pathlib.Path)
     p.add_argument("--synthetic", default=0, type=int)
     p.add_argument("--batches", default=32, type=int)
+    p.add_argument("--ignore-regions", action="store_true",
+                   help="treat difficult / iscrowd boxes as ignore regions; the priors they switch off are drawn as class 0 "
+                        "boxes of their own image <i>_ignored.jpg")
     args = p.parse_args()
     if args.synthetic:
         X_val, y_val = _common.synthetic_dataset(1)
@@ -26,6 +29,9 @@ def _main():
     # as the reference does (check_assign.py:19,21): the detector at ITS default input size, the generator at 512 x 512 --
     # prior boxes live in normalised image coordinates, so encode_truth / decode_locs do not depend on the image size
     od = _common.make_detector(tk, args, 1, use_multi_gpu=False)
+    if args.ignore_regions:
+        od.pb.ignore_regions = True
+        y_val[0].difficults[-1:] = True  # so that there is a region to look at: the image's last box
     gen = tk.dl.od.od_gen.create_generator((512, 512), preprocess_input=lambda x: x, encode_truth=od.pb.encode_truth)
     g, _ = gen.flow(X_val, y_val, data_augmentation=True)
     for i, (X_batch, y_batch) in zip(tk.tqdm(range(args.batches)), g):
@@ -35,6 +41,11 @@ def _main():
             bboxes = od.pb.decode_locs(np.zeros((len(y), 4)), xp=np)[obj_pb, :]  # the prior boxes themselves
             img = tk.ml.plot_objects(rgb, classes, None, bboxes, tk.data.voc.CLASS_NAMES)
             tk.ndimage.save(args.save_dir / f"{i}.jpg", img)
+            if args.ignore_regions:
+                off = ~y.any(axis=-1)  # all-zero rows: no objectness loss (IoU band or ignore region)
+                boxes = od.pb.decode_locs(np.zeros((len(y), 4)), xp=np)[off, :]
+                img = tk.ml.plot_objects(rgb, np.zeros(len(boxes), int), None, boxes, tk.data.voc.CLASS_NAMES)
+                tk.ndimage.save(args.save_dir / f"{i}_ignored.jpg", img)
 
 
 if __name__ == "__main__":

@@ -14,13 +14,19 @@ def _main():
     p.add_argument("--save-dir", default=pathlib.Path("___generator_check"), type=pathlib.Path)
     p.add_argument("--synthetic", default=0, type=int)
     p.add_argument("--batches", default=32, type=int)
+    p.add_argument("--mosaic", default=0.0, type=float, metavar="P",
+                   help="probability of a four-image mosaic (composed on the GPU: needs one)")
     args = p.parse_args()
     if args.synthetic:
         X_val, y_val = _common.synthetic_dataset(1)
     else:
         X_val, y_val = tk.data.voc.load_07_test(args.vocdevkit_dir)
-    X_val, y_val = X_val[:1], y_val[:1]
-    gen = tk.dl.od.od_gen.create_generator((512, 512), preprocess_input=lambda x: x, encode_truth=None)
+    if args.mosaic > 0:  # a mosaic wants partners: up to 16 images (4 synthetic ones) instead of the reference's one
+        X_val, y_val = _common.synthetic_dataset(4) if args.synthetic else (X_val[:16], y_val[:16])
+    else:
+        X_val, y_val = X_val[:1], y_val[:1]
+    kw = {"mosaic": args.mosaic, "device": "cuda:0", "ignore_regions": True} if args.mosaic > 0 else {}
+    gen = tk.dl.od.od_gen.create_generator((512, 512), preprocess_input=lambda x: x, encode_truth=None, **kw)
     g, _ = gen.flow(X_val, y_val, data_augmentation=True)
     for i, (X_batch, y_batch) in zip(tk.tqdm(range(args.batches)), g):
         for rgb, y in zip(X_batch, y_batch):

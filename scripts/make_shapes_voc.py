@@ -14,8 +14,12 @@ def _main():
     p.add_argument("--seed", default=1000, type=int)
     p.add_argument("--image-set", default="test")
     p.add_argument("--format", default="png", choices=("png", "jpg"))
+    p.add_argument("--difficult", default=0.0, type=float, metavar="FRAC",
+                   help="mark this share of the objects <difficult>1</difficult> (drawn half faded)")
+    p.add_argument("--crowd", default=0.0, type=float, metavar="FRAC",
+                   help="give this share of the images a cluster of small shapes under one loose box marked difficult")
     args = p.parse_args()
-    X, y = _common.shapes_dataset(args.n, seed=args.seed)
+    X, y = _common.shapes_dataset(args.n, seed=args.seed, difficult_frac=args.difficult, crowd_frac=args.crowd)
     base = _common.write_voc_layout(args.vocdevkit_dir, X, y, image_set=args.image_set, fmt=args.format)
     print(f"{args.n} images -> {base}")
 

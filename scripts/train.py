@@ -11,6 +11,7 @@ Data: a VOCdevkit directory (--vocdevkit-dir, image set --image-set of VOC<year>
 --shapes N generated images (_common.shapes_dataset; VOC07+12 cannot be fetched offline).  Under torch.distributed.run every rank trains on its shard of
 the images and the gradients are all-reduced through RCCL (od_allreduce)."""
 import argparse
+import json
 import pathlib
 import time
 
@@ -55,6 +56,12 @@ def _main():
     p.add_argument("--log-every", default=50, type=int)
     p.add_argument("--no-device-cache", action="store_true",
                    help="decode and upload every image every epoch instead of keeping the decoded dataset in HBM")
+    p.add_argument("--mosaic", default=0.0, type=float, metavar="P",
+                   help="probability that a training image is a mosaic of four (od_augment_mosaic; off by default)")
+    p.add_argument("--ignore-regions", action="store_true",
+                   help="difficult / iscrowd boxes and the slivers a mosaic leaves are ignore regions instead of positives")
+    p.add_argument("--shapes-difficult", default=0.0, type=float, help="--shapes: share of objects marked difficult")
+    p.add_argument("--shapes-crowd", default=0.0, type=float, help="--shapes: share of images with a crowd region")
     p.add_argument("--prefetch", default=2, type=int, help="batches the generator thread runs ahead (0 = in the training thread)")
     args = p.parse_args()
     with tk.dl.session():
@@ -97,7 +104,8 @@ def _run(args):
         args.warmup = 50 if args.batch_size * world >= 32 else 200
     class_names = None
     if args.shapes:
-        X, y = _common.shapes_dataset(args.shapes, seed=args.seed)
+        X, y = _common.shapes_dataset(args.shapes, seed=args.seed, difficult_frac=args.shapes_difficult,
+                                      crowd_frac=args.shapes_crowd)
     elif args.coco_json is not None:
         if args.coco_image_dir is None:
             raise SystemExit("--coco-json needs --coco-image-dir")
@@ -126,9 +134,11 @@ def _run(args):
         prior_wh = PR.fit(np.concatenate([a.bboxes for a in y_all if a.num_objects]), tuple(args.input_size), seed=args.seed)
         log.info(f"fitted prior sizes (grid-cell units), level 0: {np.round(prior_wh[0], 2).tolist()}")
     tr = Trainer(params, args.batch_size, tuple(args.input_size), device=dev, lr=args.lr, momentum=args.momentum,
-                 weight_decay=args.weight_decay, comm=comm, world_size=world, lr_multipliers=mult, prior_wh=prior_wh, box_mode=args.box_loss)
+                 weight_decay=args.weight_decay, comm=comm, world_size=world, lr_multipliers=mult, prior_wh=prior_wh, box_mode=args.box_loss,
+                 ignore_regions=args.ignore_regions)
     gen = od_gen.create_generator(tuple(args.input_size), preprocess_input=None, encode_truth=tr.pb.encode_truth_device,
-                                  device=dev, on_device=True, device_cache=not args.no_device_cache)
+                                  device=dev, on_device=True, device_cache=not args.no_device_cache, mosaic=args.mosaic,
+                                  ignore_regions=args.ignore_regions)
     batches, per_epoch = gen.flow(X, y, batch_size=args.batch_size, data_augmentation=True, shuffle=True, seed=args.seed + rank,
                                   prefetch=args.prefetch)
     log.info(f"{n} images on rank {rank} of {world}, {per_epoch} steps per epoch, {args.steps} steps, lr {args.lr}, "
@@ -138,6 +148,8 @@ def _run(args):
                   log=log.info)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.mosaic > 0:
+        log.info(f"mosaic: {json.dumps(gen.stats)}")
     batches.close()  # ends the generator's prefetch thread (a thread still issuing GPU work at interpreter exit aborts)
     k = max(1, min(20, args.steps // 10))
     log.info(f"loss first {k} steps {hist[:k, 3].mean():.4f} -> last {k} steps {hist[-k:, 3].mean():.4f}; "
