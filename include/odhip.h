@@ -253,6 +253,50 @@ int od_gather_detections_pred(od_ctx* ctx, const float* pred, const float* boxes
                               const int32_t* keep_count, int B, int P, int NC, int max_det, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Test-time augmentation (BUILD-DEFINED; DESIGN.md "Flip test-time augmentation"): several views of a batch are run
+ * through the network, each view's top-K candidates are taken with od_detect_candidates, and od_tta_merge merges the
+ * lists, runs ONE NMS over the merged list and refines the kept boxes by confidence-weighted box voting.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* dst[b,y,x,:] = src[b,y,W-1-x,:] for uint8 NHWC [B,H,W,3].  src and dst must not overlap. */
+int od_hflip_u8(od_ctx* ctx, const uint8_t* src, uint8_t* dst, int B, int H, int W, void* stream);
+
+/* od_detect without its two NMS launches: pred -> boxes [B,P,4], SORTED keys [B,K] (unused slots 0) and counts [B], bit-identical
+ * to what od_detect returns for the same pred, by the same kernels (both dispatches: NC <= 76 and the streamed ones above).
+ * Same workspace as od_detect (left ready for the next call of either).  nms_workspace (od_nms_workspace_bytes(B, K)) receives
+ * the rank-ordered keys / boxes / classes the sort kernel gathers, as in od_detect; nothing else in it is touched. */
+int od_detect_candidates(od_ctx* ctx, const float* pred, const float* priors, int B, int P, int NC, float loc_scale, int clip,
+                         float conf_threshold, int K, float* boxes, float* conf, uint64_t* keys, int32_t* counts,
+                         void* workspace, size_t workspace_bytes, void* nms_workspace, size_t nms_workspace_bytes,
+                         void* stream);
+
+/* One view of od_tta_merge: the keys / counts / boxes od_detect_candidates (or od_detect) produced for it with the same NC and
+ * K, its prior count, and whether its input was mirrored left-to-right. */
+typedef struct od_tta_view {
+  const uint64_t* keys;  /* u64 [B,K], sorted descending */
+  const int32_t* counts; /* i32 [B] */
+  const float* boxes;    /* f32 [B,P,4] */
+  int32_t P;
+  int32_t flip;
+} od_tta_view;
+
+/* Merge V views (1 <= V <= 8, host array `views`; the views may differ in P), all f32, one rounding per op, no contraction:
+ *   candidate (v, r), r < counts_v[b]: conf = float(key >> 32), flat = 0xFFFFFFFF - low word, p = flat / NC, c = flat % NC,
+ *       box = boxes_v[b][p], mirrored to (1 - x2, y1, 1 - x1, y2) when flip_v
+ *   merged order: conf bits desc, view asc, flat asc; the first Km = min(K, sum_v counts_v[b]) are kept
+ *   greedy NMS over the merged list by od_nms's rule (same class unless strict, at most max_det kept, rank order)
+ *   vote_iou > 0: every kept candidate i takes the box  sum_j conf_j * box_j / sum_j conf_j  over j = i and every merged
+ *       candidate j (kept or not) of i's class with inter(i,j) > vote_iou * union(i,j), accumulated in ascending rank j
+ *       (multiply and add rounded separately); confidence and rank stay.  vote_iou <= 0: the box stays.
+ *   out f32 [B][1 + 6*max_det] in od_gather_detections' layout, word 0 of a row = the CLASS (int bits; -1 beyond the count)
+ *   src i32 [B,max_det,2] (may be NULL): (view, flat index in that view) of each kept detection, -1 beyond the count
+ *   keep_count i32 [B].  K <= 1024.  workspace: od_tta_merge_workspace_bytes(B, V, K), needs no initialisation. */
+size_t od_tta_merge_workspace_bytes(int B, int V, int K);
+int od_tta_merge(od_ctx* ctx, const od_tta_view* views, int V, int B, int NC, int K, float iou_threshold, int strict,
+                 int max_det, float vote_iou, float* out, int32_t* src, int32_t* keep_count, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K9: prior-box assignment + target encoding = od.pb.encode_truth (reference check_assign.py:21,25-27).
  *   priors f32 [P,4]; gt_boxes f32 [B,Gmax,4] corner form, normalised; gt_classes i32 [B,Gmax]; gt_counts i32 [B]
  *   y f32 [B,P,2+NC+4]: col 0 = background, col 1 = assigned ("y[:,1]==1", :25), cols 2..2+NC one-hot class (:26),

@@ -115,7 +115,12 @@ class ImgDesc(C.Structure):
                                          "hcoef_off", "vcoef_off", "coef_ws", "plane_ws", "rgb_ws", "tmp_ws", "state_ws")]
 
 
-STRUCTS = (ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
+class TtaView(C.Structure):
+    C_NAME = "od_tta_view"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
+    _fields_ = [("keys", C.c_void_p), ("counts", C.c_void_p), ("boxes", C.c_void_p), ("P", C.c_int32), ("flip", C.c_int32)]
+
+
+STRUCTS = (TtaView, ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
 
 
 class OdError(RuntimeError):
@@ -165,6 +170,13 @@ _PROTOS = {
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "od_gather_detections_pred": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                             C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "od_hflip_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "od_detect_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                       C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "od_tta_merge_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "od_tta_merge": (C.c_int, [C.c_void_p, C.POINTER(TtaView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                               C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "od_assign_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "od_assign_anchors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,

@@ -101,6 +101,9 @@ const std::vector<StructInfo>& od_struct_table() {
         OD_F(od_aug_params, crop_y2), OD_F(od_aug_params, flip), OD_F(od_aug_params, brightness),
         OD_F(od_aug_params, contrast), OD_F(od_aug_params, saturation), OD_F(od_aug_params, n_erase),
         OD_F(od_aug_params, erase), OD_F(od_aug_params, erase_rgb)}},
+      {"od_tta_view", sizeof(od_tta_view),
+       {OD_F(od_tta_view, keys), OD_F(od_tta_view, counts), OD_F(od_tta_view, boxes), OD_F(od_tta_view, P),
+        OD_F(od_tta_view, flip)}},
       {"od_mosaic_params", sizeof(od_mosaic_params),
        {OD_F(od_mosaic_params, split_x), OD_F(od_mosaic_params, split_y), OD_F(od_mosaic_params, tile),
         OD_F(od_mosaic_params, n_erase), OD_F(od_mosaic_params, pad_), OD_F(od_mosaic_params, erase),

@@ -12,6 +12,7 @@
 //           bitonic sort of the K winners in LDS, gather of their boxes / classes for the NMS, counts; re-zeroes the histogram
 //   od_nms_mask, od_nms_scan  as in od_nms (nms.hip)
 // Same total order, same exact selection, same kept indices as the three-call path (tests compare them bit for bit).
+// od_detect_candidates is the same call stopped after refine (boxes, sorted keys, counts): one view of od_tta_merge (tta.hip).
 // Compiled with -ffp-contract=off like post.hip / topk.hip / nms.hip.  NC <= 76 (256 whole rows in LDS); larger class counts
 // take the streamed kernels of detect_wide.hip through the same entry points.
 #include <string.h>
@@ -342,27 +343,26 @@ extern "C" int od_detect_workspace_init(od_ctx* ctx, void* workspace, size_t wor
   return OD_OK;
 }
 
-extern "C" int od_detect(od_ctx* ctx, const float* pred, const float* priors, int B, int P, int NC, float loc_scale, int clip,
-                         float conf_threshold, int K, float iou_threshold, int strict, int max_det, float* boxes, float* conf,
-                         uint64_t* keys, int32_t* counts, int32_t* keep_flat, int32_t* keep_count, void* workspace,
-                         size_t workspace_bytes, void* nms_workspace, size_t nms_workspace_bytes, void* stream) {
-  OD_REQUIRE(ctx && pred && priors && boxes && keys && counts && keep_flat && keep_count && workspace && nms_workspace,
-             "od_detect: null argument");
-  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "od_detect: NC = %d outside the supported class counts 1..%d", NC, OD_MAX_NC);
-  OD_REQUIRE(B > 0 && B <= 65535 && P > 0 && P % 2 == 0 && K > 0 && K <= 1024 && max_det > 0,
-             "od_detect: bad dims (P even, K <= 1024)");
-  OD_REQUIRE((long long)P * NC < (1LL << 31), "od_detect: P * NC must fit 31 bits");
-  OD_REQUIRE(conf_threshold >= 0.f, "od_detect: conf_threshold must be >= 0 (scores are probabilities)");
+namespace {
+// pass 1 / pass 2 / refine of od_detect (either dispatch): pred -> boxes, sorted keys, counts, and the rank-ordered keys / boxes /
+// classes in the NMS workspace.  od_detect queues the two NMS launches behind it; od_detect_candidates stops here.
+int detect_candidates_launch(od_ctx* ctx, const char* who, const float* pred, const float* priors, int B, int P, int NC,
+                             float loc_scale, int clip, float conf_threshold, int K, float* boxes, float* conf, uint64_t* keys,
+                             int32_t* counts, void* workspace, size_t workspace_bytes, void* nms_workspace,
+                             size_t nms_workspace_bytes, hipStream_t s) {
+  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "%s: NC = %d outside the supported class counts 1..%d", who, NC, OD_MAX_NC);
+  OD_REQUIRE(B > 0 && B <= 65535 && P > 0 && P % 2 == 0 && K > 0 && K <= 1024, "%s: bad dims (P even, K <= 1024)", who);
+  OD_REQUIRE((long long)P * NC < (1LL << 31), "%s: P * NC must fit 31 bits", who);
+  OD_REQUIRE(conf_threshold >= 0.f, "%s: conf_threshold must be >= 0 (scores are probabilities)", who);
   const DetLayout l = det_layout(B, P, NC);
   if (workspace_bytes < l.total) {
-    od_set_error("od_detect: workspace %zu < %zu bytes", workspace_bytes, l.total);
+    od_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, l.total);
     return OD_ERR_WORKSPACE;
   }
   if (nms_workspace_bytes < od_nms_workspace_bytes(B, K)) {
-    od_set_error("od_detect: NMS workspace %zu < %zu bytes", nms_workspace_bytes, od_nms_workspace_bytes(B, K));
+    od_set_error("%s: NMS workspace %zu < %zu bytes", who, nms_workspace_bytes, od_nms_workspace_bytes(B, K));
     return OD_ERR_WORKSPACE;
   }
-  hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;
   int* hist = (int*)(ws + l.hist);
   TopkState* st = (TopkState*)(ws + l.state);
@@ -382,11 +382,9 @@ extern "C" int od_detect(od_ctx* ctx, const float* pred, const float* priors, in
   int KP;
   od_nms_sorted_buffers(nms_workspace, B, K, &skeys, &sbox, &scls, &KP);
   if (NC > OD_MAX_LDS_NC) {
-    if (int rc = od_detect_wide_launch(pred, priors, B, P, NC, loc_scale, clip, conf_threshold, dbase, dshift, K, KP, boxes,
-                                       conf, (u64*)keys, counts, hist, st, rowmax, (int*)(ws + l.nhot),
-                                       (HotRow*)(ws + l.hot), skeys, sbox, scls, s))
-      return rc;
-    return od_nms_mask_scan_launch(ctx, nms_workspace, counts, B, K, iou_threshold, strict, max_det, keep_flat, keep_count, s);
+    return od_detect_wide_launch(pred, priors, B, P, NC, loc_scale, clip, conf_threshold, dbase, dshift, K, KP, boxes, conf,
+                                 (u64*)keys, counts, hist, st, rowmax, (int*)(ws + l.nhot), (HotRow*)(ws + l.hot), skeys, sbox,
+                                 scls, s);
   }
   const size_t lds1 = (size_t)DT_ROWS * C * 4 + (size_t)NB * 4;
   if (int rc = od_ensure_lds(ctx, (const void*)&od_detect_pass1, lds1)) return rc;
@@ -401,7 +399,32 @@ extern "C" int od_detect(od_ctx* ctx, const float* pred, const float* priors, in
   hipLaunchKernelGGL(od_detect_refine_sort, dim3(B), dim3(1024), 0, s, boxes, st, (u64*)keys, cand, hist, counts, P, NC, K, KP,
                      l.cand_stride, skeys, sbox, scls, dbase, dshift);
   OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+}  // namespace
+
+extern "C" int od_detect(od_ctx* ctx, const float* pred, const float* priors, int B, int P, int NC, float loc_scale, int clip,
+                         float conf_threshold, int K, float iou_threshold, int strict, int max_det, float* boxes, float* conf,
+                         uint64_t* keys, int32_t* counts, int32_t* keep_flat, int32_t* keep_count, void* workspace,
+                         size_t workspace_bytes, void* nms_workspace, size_t nms_workspace_bytes, void* stream) {
+  OD_REQUIRE(ctx && pred && priors && boxes && keys && counts && keep_flat && keep_count && workspace && nms_workspace,
+             "od_detect: null argument");
+  OD_REQUIRE(max_det > 0, "od_detect: bad dims (P even, K <= 1024)");
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = detect_candidates_launch(ctx, "od_detect", pred, priors, B, P, NC, loc_scale, clip, conf_threshold, K, boxes, conf,
+                                        keys, counts, workspace, workspace_bytes, nms_workspace, nms_workspace_bytes, s))
+    return rc;
   return od_nms_mask_scan_launch(ctx, nms_workspace, counts, B, K, iou_threshold, strict, max_det, keep_flat, keep_count, s);
+}
+
+extern "C" int od_detect_candidates(od_ctx* ctx, const float* pred, const float* priors, int B, int P, int NC, float loc_scale,
+                                    int clip, float conf_threshold, int K, float* boxes, float* conf, uint64_t* keys,
+                                    int32_t* counts, void* workspace, size_t workspace_bytes, void* nms_workspace,
+                                    size_t nms_workspace_bytes, void* stream) {
+  OD_REQUIRE(ctx && pred && priors && boxes && keys && counts && workspace && nms_workspace, "od_detect_candidates: null argument");
+  return detect_candidates_launch(ctx, "od_detect_candidates", pred, priors, B, P, NC, loc_scale, clip, conf_threshold, K, boxes,
+                                  conf, keys, counts, workspace, workspace_bytes, nms_workspace, nms_workspace_bytes,
+                                  (hipStream_t)stream);
 }
 
 extern "C" int od_gather_detections_pred(od_ctx* ctx, const float* pred, const float* boxes, const int32_t* keep_flat,

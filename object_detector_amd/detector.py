@@ -20,6 +20,7 @@ from . import weights as W
 from .net import Net
 from .pb import ObjectsAnnotation, PriorBoxes
 from .postprocess import Postprocessor
+from .tta import VOTE_IOU, TtaPostprocessor, normalize_views
 
 DEFAULT_CONF_THRESHOLD = 0.01  # [BUILD-DEFINED]: mAP needs the low-confidence tail (voc_evaluate.py:27 passes 0.6)
 VOC_WEIGHTS_ENV = "OD_VOC_WEIGHTS"
@@ -137,15 +138,21 @@ def stream_queue_sets(device, n, candidates=6, seed_streams=(), beside=None):
 class _Pipeline:
     """One batch in flight: its own activation buffers (Net), post-processing buffers and HIP stream."""
 
-    def __init__(self, net, post, stream):
+    def __init__(self, net, post, stream, tta=None):
         self.net, self.post, self.stream = net, post, stream
+        self.tta = tta  # TtaPostprocessor beside `post` when the detector runs test-time augmentation
         self.done = torch.cuda.Event()
         self.decoder = None  # devdecode.BatchDecoder of image_decode="device", made on first use
 
 
 class ObjectDetector:
     def __init__(self, params, batch_size=16, input_size=(320, 320), keep_aspect=False, strict_nms=False,
-                 use_multi_gpu=True, device=None, prior_wh=None, n_inflight=None, precision=None, image_decode="host"):
+                 use_multi_gpu=True, device=None, prior_wh=None, n_inflight=None, precision=None, image_decode="host",
+                 tta=None, tta_vote_iou=VOTE_IOU):
+        # test-time augmentation: None = off (the plain path, unchanged); () = the identity view alone (box voting only);
+        # ("flip",) = identity + horizontal mirror, merged on the device (tta.py).  Checked before anything touches the GPU.
+        self.tta = normalize_views(tta)
+        self.tta_vote_iou = float(tta_vote_iou)
         if device is None:  # one process per GPU; the modulo only matters when several ranks rehearse on one GPU
             device = f"cuda:{int(os.environ.get('LOCAL_RANK', 0)) % max(1, torch.cuda.device_count())}"
         if not torch.cuda.is_available():
@@ -178,16 +185,26 @@ class ObjectDetector:
         # tails, epilogue write bursts and the small post-processing kernels of one batch overlap the convolutions of the
         # next (measured +23 % images/s at batch 32 with 2-3 in flight, profiles/r01/inflight_sweep.txt).  Pipeline 0 =
         # (self.net, self.post) on the caller's stream is what predict_batch_device uses.
-        self._pipes = [_Pipeline(self.net, self.post, torch.cuda.Stream(device=self.device))]
+        self._pipes = [_Pipeline(self.net, self.post, torch.cuda.Stream(device=self.device), self._make_tta(self.post))]
         for _ in range(max(1, n) - 1):
             net = Net(params, self.batch_size, self.input_size, device=self.device, overlapped=True,
                       share_weights_with=self.net, precision=self.precision, stream_stages=self.net.stream_stages,
                       split=self.net.split, wide_fpn=self.net.wide_fpn)
             post = Postprocessor(self.batch_size, net.P, self.num_classes, self.pb.pb_locs, device=self.device,
                                  strict_nms=self.strict_nms, loc_scale=self.pb.loc_scale)
-            self._pipes.append(_Pipeline(net, post, torch.cuda.Stream(device=self.device)))
+            self._pipes.append(_Pipeline(net, post, torch.cuda.Stream(device=self.device), self._make_tta(post)))
         self._next = 0
         self._calibrated = len(self._pipes) < 2 or os.environ.get("OD_INFLIGHT_CALIBRATE", "1") == "0"
+
+    def _make_tta(self, post):
+        if self.tta is None:
+            return None
+        return TtaPostprocessor(post, self.net.input.shape, self.tta, self.tta_vote_iou)
+
+    @staticmethod
+    def _no_graph_with_tta(graph):
+        if graph:
+            raise ValueError("graph=True is not available with tta: the captured plan replays one view")
 
     # -- construction -----------------------------------------------------------------------------------------
     @classmethod
@@ -214,8 +231,13 @@ class ObjectDetector:
 
     # -- inference --------------------------------------------------------------------------------------------
     def predict_batch_device(self, x_u8: torch.Tensor, conf_threshold=DEFAULT_CONF_THRESHOLD, graph=False):
-        """uint8 [B,H,W,3] on device -> (keep_flat [B,max_det], keep_count [B]) on device.  The timed hot path."""
+        """uint8 [B,H,W,3] on device -> (keep_flat [B,max_det], keep_count [B]) on device.  The timed hot path.
+        With tta: -> (det f32 [B, 1 + 6*max_det], keep_count [B]) on device; det is od_tta_merge's record block (word 0 =
+        keep count, row r = {class (int bits), conf, x1, y1, x2, y2}): a merged detection has no single flat index."""
         torch.cuda.current_stream(self.device).wait_stream(self._pipes[0].stream)  # pipeline 0's buffers may be in flight
+        if self.tta is not None:
+            self._no_graph_with_tta(graph)
+            return self._pipes[0].tta.run(self.net, x_u8, conf_threshold)
         pred = self.net.forward(x_u8, graph=graph)
         return self.post.run(pred, conf_threshold)
 
@@ -226,7 +248,10 @@ class ObjectDetector:
 
     def submit(self, x_u8: torch.Tensor, conf_threshold=DEFAULT_CONF_THRESHOLD, graph=False, gather=False) -> int:
         """Queue one batch on the next pipeline's stream and return its ticket.  Never blocks the host: a pipeline's new
-        batch is stream-ordered behind its previous one (whose results it overwrites -- collect() them first)."""
+        batch is stream-ordered behind its previous one (whose results it overwrites -- collect() them first).
+        With tta every view runs on that stream and the merged record block is always copied to the host (`gather` is moot)."""
+        if self.tta is not None:
+            self._no_graph_with_tta(graph)
         if not self._calibrated:
             self._pick_streams()
         i = self._next
@@ -234,10 +259,13 @@ class ObjectDetector:
         p = self._pipes[i]
         p.stream.wait_stream(torch.cuda.current_stream(self.device))  # x_u8 was produced on the caller's stream
         with torch.cuda.stream(p.stream):
-            pred = p.net.forward(x_u8, graph=graph)
-            p.post.run(pred, conf_threshold)
-            if gather:
-                p.post.gather()  # kept detections -> one record block -> pinned host memory, still on this stream
+            if p.tta is not None:
+                p.tta.run(p.net, x_u8, conf_threshold)
+            else:
+                pred = p.net.forward(x_u8, graph=graph)
+                p.post.run(pred, conf_threshold)
+                if gather:
+                    p.post.gather()  # kept detections -> one record block -> pinned host memory, still on this stream
             p.done.record()
         x_u8.record_stream(p.stream)
         return i
@@ -256,9 +284,12 @@ class ObjectDetector:
         p.stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(p.stream):
             p.decoder.run(items, p.net.input)
-            pred = p.net.forward(None)
-            p.post.run(pred, conf_threshold)
-            p.post.gather()
+            if p.tta is not None:
+                p.tta.run(p.net, None, conf_threshold)  # the mirror is taken from the decoded input
+            else:
+                pred = p.net.forward(None)
+                p.post.run(pred, conf_threshold)
+                p.post.gather()
             p.done.record()
         for it in items:
             self.decode_stats[it[0]] += 1
@@ -277,9 +308,12 @@ class ObjectDetector:
         self._next = 0
 
     def collect(self, ticket: int):
-        """Wait for the batch submitted with `ticket`; -> (keep_flat [B,max_det], keep_count [B]) on device."""
+        """Wait for the batch submitted with `ticket`; -> (keep_flat [B,max_det], keep_count [B]) on device.
+        With tta: -> (det [B, 1 + 6*max_det], keep_count [B]), as predict_batch_device."""
         p = self._pipes[ticket]
         p.done.synchronize()
+        if p.tta is not None:
+            return p.post.det, p.post.keep_count
         return p.post.keep_flat, p.post.keep_count
 
     def synchronize(self):
@@ -296,7 +330,10 @@ class ObjectDetector:
             if scales is not None and scales[b] != (1.0, 1.0):  # keep_aspect: canvas coordinates -> image coordinates
                 sx, sy = scales[b]
                 bxs = np.clip(bxs / np.array([sx, sy, sx, sy], np.float32), 0.0, 1.0)
-            out.append(ObjectsPrediction(k % NC, confs, bxs, k))
+            if self.tta is not None:  # word 0 of a merged record is the class; there is no flat index
+                out.append(ObjectsPrediction(k, confs, bxs, None))
+            else:
+                out.append(ObjectsPrediction(k % NC, confs, bxs, k))
         return out
 
     def _decode_procs(self, n, nbytes):

@@ -24,10 +24,20 @@ def synthetic_dataset(n, size=(375, 500), seed=1):
     return np.array(X, dtype=object), np.array(y, dtype=object)
 
 
+def add_tta_arguments(p):
+    """--tta [flip] / --vote-iou X of the evaluation scripts (ObjectDetector(tta=..., tta_vote_iou=...))."""
+    p.add_argument("--tta", default=None, nargs="*", metavar="VIEW",
+                   help="test-time augmentation: `--tta flip` merges the mirrored view on the GPU; `--tta` alone runs the "
+                        "identity view with box voting only; absent = off")
+    p.add_argument("--vote-iou", default=0.5, type=float, help="box-voting overlap under --tta (<= 0: no voting)")
+
+
 def make_detector(tk, args, batch_size, input_size=(320, 320), device_decode=False, **kw):
     """device_decode: JPEG decode and resize of predict()'s inputs on the GPU (image_decode="device")."""
     OD = tk.dl.od.ObjectDetector
     kw["image_decode"] = "device" if device_decode else "host"
+    if getattr(args, "tta", None) is not None:
+        kw["tta"], kw["tta_vote_iou"] = tuple(args.tta), args.vote_iou
     if args.synthetic:
         return OD.synthetic(batch_size, input_size, **kw)
     return OD.load_voc(batch_size=batch_size, input_size=input_size, weights=args.weights, **kw)

@@ -21,6 +21,7 @@ def _main():
                    help="mixed = every logit within 1e-3 x scale of an fp32 run (ObjectDetector(precision=...)); default f16")
     p.add_argument("--device-decode", action="store_true",
                    help="decode JPEGs and resize every input on the GPU (ObjectDetector(image_decode='device'))")
+    _common.add_tta_arguments(p)
     p.add_argument("--synthetic", default=0, type=int)
     args = p.parse_args()
     with tk.dl.session():
