@@ -38,6 +38,11 @@ extern "C" int od_ctx_create(int device, od_ctx** out) {
     delete c;
     return OD_ERR_INVALID;
   }
+  if (c->num_cu <= 0) {  // every grid heuristic divides the work over num_cu
+    od_set_error("od_ctx_create: device %d reports %d compute units", device, c->num_cu);
+    delete c;
+    return OD_ERR_INVALID;
+  }
   OD_CHECK_HIP(hipMalloc(&c->zero_page, 8192));
   OD_CHECK_HIP(hipMemset(c->zero_page, 0, 8192));
   {

@@ -565,21 +565,25 @@ constexpr int kNumE8 = sizeof(g_e8) / sizeof(g_e8[0]);
 
 int od_conv_8ph_num_cfgs() { return kNumE8; }
 
-bool od_conv_8ph_select(int idx, const ConvKP& p, int ksize, ConvKernelInfo* info, size_t* lds_bytes) {
+long od_conv_8ph_tiles(int idx, int M, int Cout) { return (long)od_ceil_div(M, g_e8[idx].BM) * od_ceil_div(Cout, E_BN); }
+// us per BM x 256 tile: fixed cost + K tiles x cost per K tile (profiles/r01/conv_8ph_sweep_{320,640}.txt)
+double od_conv_8ph_tile_cost(int idx, int nk) { return 13.0 + 1.78 * nk * (0.5 + 0.0625 * (g_e8[idx].BM / 32)); }
+
+// one n tile holding all 256 channels of a pixel, 128 output channels (W2 = 64 KiB of LDS), no split-K slabs
+bool od_conv_8ph_can_fuse_pointwise(const ConvKP& p) { return p.splitk == 1 && p.Cout == E_BN && p.Cout2 == 128; }
+
+bool od_conv_8ph_select(int idx, const ConvKP& p, int ksize, ConvKernelInfo* info) {
   if (idx < 0 || idx >= kNumE8) return false;
   if ((p.Cin & 63) != 0 || p.tconv) return false;
   if (p.x_bytes >= 0x7F000000u || p.w_bytes >= 0x7F000000u || p.x_bytes == 0) return false;  // E_OOB must stay out of range
   const E8Entry& e = g_e8[idx];
   const bool pw = p.w2 != nullptr;  // the caller (od_conv2d_fwd) has checked od_conv_8ph_can_fuse_pointwise
-  info->fn = ksize == 1 ? (pw ? e.k1pw : e.k1) : (pw ? e.k3pw : e.k3seg);
-  info->name = ksize == 1 ? (pw ? e.name1pw : e.name1) : (pw ? e.name3pw : e.name3seg);
+  if (p.nseg > 1 && (ksize != 3 || pw || p.stride != 1 || p.res_mode != OD_RES_NONE)) return false;
+  const size_t epi = (size_t)(e.BM / 2) * (E_BN + 4) * 4;
   // ordinary 3x3 launches run the segment-capable instantiation too (its segment table is empty: nseg <= 1), so that the
   // kernel is ONE symbol whether or not a layer is grouped
-  if (p.nseg > 1 && (ksize != 3 || pw || p.stride != 1 || p.res_mode != OD_RES_NONE)) return false;
-  info->BM = e.BM;
-  info->BN = E_BN;
-  info->threads = 512;
-  const size_t epi = (size_t)(e.BM / 2) * (E_BN + 4) * 4;
-  *lds_bytes = epi > (size_t)2 * E_BUF ? epi : (size_t)2 * E_BUF;
+  *info = {ksize == 1 ? (pw ? e.k1pw : e.k1) : (pw ? e.k3pw : e.k3seg),
+           ksize == 1 ? (pw ? e.name1pw : e.name1) : (pw ? e.name3pw : e.name3seg),
+           e.BM, E_BN, E_BK, 512, epi > (size_t)2 * E_BUF ? epi : (size_t)2 * E_BUF};
   return true;
 }

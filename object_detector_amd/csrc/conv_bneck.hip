@@ -477,7 +477,7 @@ int od_bottleneck_prepare(od_ctx* ctx, const od_bneck_desc* d, od_launches* L) {
   if (int rc = od_ensure_lds(ctx, k.fn, (size_t)lds)) return rc;
   const int ntiles = d->B * p.tiles_x * p.tiles_y;
   // C = 64: persistent workgroups (one per CU) walk the tiles; C = 128: one workgroup per tile
-  const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+  const int cus = ctx->num_cu;
   const int grid = d->C == 64 ? (ntiles < cus ? ntiles : cus) : ntiles;
   return od_add_launch(L, {k.name, od_issue_kp_int<BneckKP>, k.fn, dim3((unsigned)grid), dim3(d->C == 64 ? 768 : 512), (size_t)lds},
                        od_kp_int<BneckKP>{p, ntiles});

@@ -1,4 +1,5 @@
-// Shared by the convolution translation units (conv_mfma.hip: implicit GEMM; conv_win.hip: LDS-window direct 3x3).
+// Shared by the convolution translation units: the kernel parameter struct, the common epilogue, and what each kernel
+// family (one per file) exports to the dispatcher (conv_dispatch.hip).
 #pragma once
 #include "common.h"
 
@@ -18,7 +19,7 @@ struct ConvKP {
   int res_mode, out_f32;
   long long obs, ops;
   int mtiles, ntiles;
-  int splitk, steps_per_split;  // split-K (small-M layers): each workgroup reduces a K range, f32 atomics into ws
+  int splitk, steps_per_split;  // split-K (small-M layers): each workgroup reduces a K range into its own slab of ws
   float* ws;                    // [splitk][M][Cout] f32 partial slabs; od_conv_finish sums them and applies the epilogue
   int Mq;             // transposed mode: B*Hs*Ws source positions (rows per parity class)
   int tconv, Hs, Ws;  // transposed (backward-data of a stride-2 conv): x is [B,Hs,Ws,Cin], gathered through a 2x zero-upsampled view
@@ -281,16 +282,28 @@ static __device__ __forceinline__ void conv_epilogue(const ConvKP& p, char* smem
   }
 }
 
-// a launchable convolution kernel variant
+// a launchable convolution kernel variant: the kernel, the tile it computes and the dynamic LDS it needs
 struct ConvKernelInfo {
   const void* fn;
   const char* name;
-  int BM, BN, threads;
+  int BM, BN, BK, threads;
+  size_t lds;
 };
 
-// conv_8ph.hip: 8-wave, BM x 256 tile, one workgroup per CU, staggered wave groups (3x3 and 1x1)
+// conv_mfma.hip: the table kernels (od_conv_igemm), configs 0 .. num_cfgs - 1.  select fills *info with the config's tile and
+// the kernel for this layer (want_stats: the BatchNorm-statistics instantiation); false when the config has no such kernel
+// (configs 4-7 have no generic 3x3 variant: fn stays null, the tile is still filled in).  od_conv_finish sums split-K slabs.
+int od_conv_igemm_num_cfgs();
+bool od_conv_igemm_select(int cfg, int ksize, int Cin, bool want_stats, ConvKernelInfo* info);
+int od_conv_finish_prepare(const ConvKP& p, od_launches* L);
+// conv_8ph.hip: 8-wave, BM x 256 tile, one workgroup per CU, staggered wave groups (3x3 and 1x1); idx 0 .. num_cfgs - 1 =
+// BM 256 .. 160.  tiles / tile_cost: the grid and the estimated us per tile (nk K tiles) that pick_cfg compares;
+// can_fuse_pointwise: whether the kernel runs the consuming 1x1 layer (p.w2) of this launch in its epilogue.
 int od_conv_8ph_num_cfgs();
-bool od_conv_8ph_select(int idx, const ConvKP& p, int ksize, ConvKernelInfo* info, size_t* lds_bytes);
+long od_conv_8ph_tiles(int idx, int M, int Cout);
+double od_conv_8ph_tile_cost(int idx, int nk);
+bool od_conv_8ph_can_fuse_pointwise(const ConvKP& p);
+bool od_conv_8ph_select(int idx, const ConvKP& p, int ksize, ConvKernelInfo* info);
 // conv_tconv.hip: streaming backward-data kernel of the first stride-2 convolution (dZ 64 channels -> dX 32 channels)
 bool od_tconv_small_supported(const od_conv_desc* d);
 int od_tconv_small_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L);

@@ -366,7 +366,7 @@ int od_conv_rdirect_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) 
   p.alpha = d->alpha;
   p.segs_per_row = (d->transposed ? d->W : p.Wo) / 16;
   p.nitems = d->B * (d->transposed ? d->H : p.Ho) * p.segs_per_row;
-  const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+  const int cus = ctx->num_cu;
   int grid = d->ksize == 1 ? 2 * cus : cus;  // (the 3x3 form holds 147 KiB of LDS: one workgroup per CU)
   if (grid * 8 > p.nitems) grid = od_ceil_div(p.nitems, 8);
   if (int rc = od_ensure_lds(ctx, e->fn, e->lds)) return rc;

@@ -333,7 +333,7 @@ int od_stem_prepare(od_ctx* ctx, const od_stem_desc* d, od_launches* L) {
   p.tiles_x = d->W / 32;
   p.tiles_y = d->H / 32;
   const int ntiles = d->B * p.tiles_x * p.tiles_y;
-  const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+  const int cus = ctx->num_cu;
   const int grid = ntiles < cus ? ntiles : cus;
   static_assert(OD_ACT_LINEAR == 0 && OD_ACT_LEAKY == 1 && OD_ACT_ELU == 2, "kernel table order");
 #define OD_STEM(ACT) {(const void*)&od_stem_k<ACT>, "od_stem_k<" #ACT ">"}

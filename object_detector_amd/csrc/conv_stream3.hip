@@ -226,7 +226,7 @@ int od_conv_stream3_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) 
   p.tiles_x = p.Wo / 16;
   p.tiles_per_img = (p.Ho / 4) * p.tiles_x;
   p.ntiles = d->B * p.tiles_per_img;
-  const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+  const int cus = ctx->num_cu;
   int grid = 2 * cus;
   if (grid > p.ntiles) grid = p.ntiles;
   if (int rc = od_ensure_lds(ctx, e->fn, e->lds)) return rc;

@@ -194,7 +194,7 @@ int od_tconv_small_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) {
   p.tiles_x = d->W / T_C;
   p.tiles_per_img = (d->H / T_R) * p.tiles_x;
   p.ntiles = d->B * p.tiles_per_img;
-  const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+  const int cus = ctx->num_cu;
   int grid = 2 * cus;
   if (grid > p.ntiles) grid = p.ntiles;
   if (int rc = od_ensure_lds(ctx, (const void*)&od_tconv_64_32, (size_t)T_LDS)) return rc;

@@ -525,13 +525,13 @@ static bool wgrad_thin_ok(int Cin, int Cout, int ksize, int stride, int H, int W
   return Cin == 32 && Cout == 64 && ksize == 3 && Wo % 32 == 0 && H == Ho * stride && W == Wo * stride;
 }
 static int wgrad_thin_grid(const od_ctx* ctx, long long nchunks) {
-  long long g = 2LL * (ctx->num_cu > 0 ? ctx->num_cu : 256);
+  long long g = 2LL * ctx->num_cu;
   return (int)(g < nchunks ? g : nchunks);
 }
 
 static int wgrad_split(const od_ctx* ctx, int M, int Cout, int Ktot, int* chunks_per_split) {
   const int nchunks = od_ceil_div(M, KC);
-  const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+  const int cus = ctx->num_cu;
   if (wgrad_use_w8(cus, M, Cout, Ktot)) return wgrad_w8_split(cus, nchunks, Cout, Ktot, chunks_per_split);
   const int rtiles = od_ceil_div(Cout, TILE), ctiles = od_ceil_div(Ktot, TILE);
   // workgroups per CU the pixel split aims at (every workgroup emits a full 64 KiB f32 tile, so more splits = more
@@ -587,7 +587,7 @@ static int wgrad_impl(od_ctx* ctx, const void* x, const void* dz, float* dw, flo
   }
   p.split = wgrad_split(ctx, p.M, Cout, p.Ktot, &p.chunks_per_split);
   if (nsplit) *nsplit = p.split;
-  if (wgrad_use_w8(ctx->num_cu > 0 ? ctx->num_cu : 256, p.M, Cout, p.Ktot)) {
+  if (wgrad_use_w8(ctx->num_cu, p.M, Cout, p.Ktot)) {
     p.rtiles = od_ceil_div(Cout, W8_TILE);
     p.ctiles = od_ceil_div(p.Ktot, W8_TILE);
     if (int rc = od_ensure_lds(ctx, (const void*)&od_conv_wgrad_w8, (size_t)W8_LDS)) return rc;

@@ -549,34 +549,6 @@ extern "C" int od_bn_fold(od_ctx* ctx, const float* gamma, const float* beta, co
   return OD_OK;
 }
 
-extern "C" int od_conv2d_bwd_data(od_ctx* ctx, const void* dz, const void* w_bwd, const void* dx_accumulate, void* dx, int B,
-                                  int Ho, int Wo, int Cin, int Cout, int ksize, int stride, void* stream) {
-  OD_REQUIRE(ctx && dz && w_bwd && dx, "od_conv2d_bwd_data: null argument");
-  OD_REQUIRE(Cin > 0 && Cin <= 2048, "od_conv2d_bwd_data: Cin out of range (1..2048)");
-  od_conv_desc d;
-  memset(&d, 0, sizeof(d));
-  d.x = dz;
-  d.w = w_bwd;
-  d.scale = ctx->ones;
-  d.bias = (const float*)ctx->zero_page;
-  d.res = dx_accumulate;
-  d.res_mode = dx_accumulate ? OD_RES_SAME : OD_RES_NONE;
-  d.out = dx;
-  d.B = B;
-  d.H = Ho;
-  d.W = Wo;
-  d.Cin = Cout;  // the backward-data conv contracts over the forward conv's output channels
-  d.Cout = Cin;
-  d.ksize = ksize;
-  d.stride = stride;
-  d.act = OD_ACT_LINEAR;
-  d.out_dtype = OD_DT_F16;
-  d.tile_cfg = -1;
-  d.transposed = stride == 2;
-  d.splitk = 1;
-  return od_conv2d_fwd(ctx, &d, stream);
-}
-
 extern "C" size_t od_bn_workspace_bytes(long long M, int C) {
   if (M <= 0 || C <= 0 || C % 8) return 0;
   const int rw = rows_per_wg_reduce(M, C);
