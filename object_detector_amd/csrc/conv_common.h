@@ -44,6 +44,7 @@ struct ConvKP {
   const f16* seg_x[3];
   void* seg_out[3];
   int seg_H[3], seg_W[3], seg_M[3];
+  int off32;  // every output element offset (batch * obs + pixel * ops + channel) fits 31 bits: the specialised epilogues' condition
 };
 
 static __device__ __forceinline__ void glds16(const void* gptr, void* lptr) {
@@ -59,12 +60,64 @@ static __device__ __forceinline__ float od_expm1_fast(float v) {
   return v > -0.25f ? poly : __expf(v) - 1.f;
 }
 
+// The same value with both branches computed for every lane and chosen by v_cndmask: a specialised epilogue stays
+// straight-line code (the ternaries of od_expm1_fast become an exec-mask region per element).
+static __device__ __forceinline__ float od_elu_select(float v, float alpha) {
+  const float poly = v * (1.f + v * (0.5f + v * (1.f / 6 + v * (1.f / 24 + v * (1.f / 120 + v * (1.f / 720))))));
+  const float ex = __expf(v) - 1.f;
+  const float em = v > -0.25f ? poly : ex;
+  const float neg = alpha * em;
+  return v > 0.f ? v : neg;
+}
+
+// Epilogue policy of a conv kernel instantiation: activation, residual mode and output type as ONE template argument,
+// act | res_mode << 2 | out_f32 << 4, or OD_EPI_RT = the run-time fields of ConvKP (the generic instantiation: split-K
+// slabs, BatchNorm statistics, backward-data and every combination without an instantiation of its own).  Literal
+// numbers, because the kernel tables spell the template arguments into the kernel names.
+#define OD_EPI_RT -1
+#define OD_EPI_LEAKY_NONE_F16 1
+#define OD_EPI_LEAKY_SAME_F16 5
+#define OD_EPI_ELU_NONE_F16 2
+#define OD_EPI_ELU_UP2_F16 10
+#define OD_EPI_LINEAR_NONE_F32 16
+#define OD_EPI_LEAKY_NONE_F32 17
+#define OD_EPI_ELU_NONE_F32 18
+constexpr int od_epi(int act, int res_mode, bool out_f32) { return act | (res_mode << 2) | ((int)out_f32 << 4); }
+static_assert(od_epi(OD_ACT_LEAKY, OD_RES_NONE, false) == OD_EPI_LEAKY_NONE_F16 &&
+                  od_epi(OD_ACT_LEAKY, OD_RES_SAME, false) == OD_EPI_LEAKY_SAME_F16 &&
+                  od_epi(OD_ACT_ELU, OD_RES_NONE, false) == OD_EPI_ELU_NONE_F16 &&
+                  od_epi(OD_ACT_ELU, OD_RES_UP2, false) == OD_EPI_ELU_UP2_F16 &&
+                  od_epi(OD_ACT_LINEAR, OD_RES_NONE, true) == OD_EPI_LINEAR_NONE_F32 &&
+                  od_epi(OD_ACT_LEAKY, OD_RES_NONE, true) == OD_EPI_LEAKY_NONE_F32 &&
+                  od_epi(OD_ACT_ELU, OD_RES_NONE, true) == OD_EPI_ELU_NONE_F32,
+              "OD_EPI_* literals");
+constexpr int od_epi_act(int epi) { return epi & 3; }
+constexpr int od_epi_res(int epi) { return (epi >> 2) & 3; }
+constexpr bool od_epi_f32(int epi) { return ((epi >> 4) & 1) != 0; }
+// the policy a launch asks for (p.off32: the specialised bodies form output offsets in 32 bits)
+static inline int od_epi_of(const ConvKP& p) {
+  return (p.off32 && p.splitk <= 1 && !p.tconv && !p.stats) ? od_epi(p.act, p.res_mode, p.out_f32 != 0) : OD_EPI_RT;
+}
+#define OD_STR_(x) #x
+#define OD_STR(x) OD_STR_(x)
+
 // v_permlane16_swap through inline asm (hipcc ROCm 7.2 folds repeated __builtin_amdgcn_permlane16_swap calls of an unrolled
 // loop into one).  The compiler's hazard recognizer does not see inside an asm statement: the caller must run
 // od_mfma_results_ready() once between the last MFMA that writes the swapped registers and the first swap (a VALU read
 // of an MFMA result needs up to 18 wait states); the s_nop pair here covers VALU-write -> permlane-read.
 static __device__ __forceinline__ void od_permlane16_swap(float& a, float& b) {
   asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
+}
+// Four swaps (the four accumulator registers of a fragment pair) inside ONE pair of wait states: the swaps read and
+// write disjoint registers, so only the first needs the VALU-write -> permlane-read distance.
+static __device__ __forceinline__ void od_permlane16_swap4(f32x4& a, f32x4& b) {
+  float a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
+  asm volatile(
+      "s_nop 1\n\tv_permlane16_swap_b32 %0, %4\n\tv_permlane16_swap_b32 %1, %5\n\tv_permlane16_swap_b32 %2, %6\n\t"
+      "v_permlane16_swap_b32 %3, %7\n\ts_nop 1"
+      : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3));
+  a = f32x4{a0, a1, a2, a3};
+  b = f32x4{b0, b1, b2, b3};
 }
 static __device__ __forceinline__ void od_mfma_results_ready() {
   __builtin_amdgcn_sched_barrier(0);
@@ -100,10 +153,18 @@ static __device__ __forceinline__ int od_tconv_pixel(const ConvKP& p, unsigned m
 // ---- epilogue shared by every conv kernel: accumulators -> LDS staging (one wave-row of the tile at a time) ->
 //      scale/bias/act (+ residual) in f32 on full NHWC lines, ONE rounding to f16, 16-B stores.
 //      acc[i][j][e] holds pixel (wave-row base + i*16 + l15), channel (wn*WTN + j*16 + lq*4 + e).
-template <int BN, int WM, int WN, int MT, int NTL, int NT = WM * WN * 64, bool STATS = false>
+//      EPI: the epilogue policy (above).  With a fixed policy the activation, the residual mode and the output type are
+//      compile-time constants, ELU is a select, offsets are 32-bit (p.off32), and the split-K / transposed paths are
+//      compiled out: what is left branches on the row / channel bounds only.
+template <int BN, int WM, int WN, int MT, int NTL, int NT = WM * WN * 64, bool STATS = false, int EPI = OD_EPI_RT>
 static __device__ __forceinline__ void conv_epilogue(const ConvKP& p, char* smem, f32x4 (&acc)[MT][NTL], int m0, int n0,
                                                      int tid, int wm, int wn, int l15, int lq) {
   constexpr int WTM = MT * 16, WTN = NTL * 16, SLD = BN + 4;
+  constexpr bool FX = EPI != OD_EPI_RT;
+  static_assert(!(FX && STATS), "the statistics epilogue has no policy");
+  const int act = FX ? od_epi_act(EPI) : p.act, res_mode = FX ? od_epi_res(EPI) : p.res_mode;
+  const bool out_f32 = FX ? od_epi_f32(EPI) : p.out_f32 != 0;
+  const bool splitk = !FX && p.splitk > 1, tconv = !FX && p.tconv;
   float* stg = (float*)smem;
   constexpr int CH = BN / 8;    // 8-channel chunks per row
   constexpr int RPP = NT / CH;  // rows per store pass
@@ -135,7 +196,7 @@ static __device__ __forceinline__ void conv_epilogue(const ConvKP& p, char* smem
   constexpr int NPASS = (WTM + RPP - 1) / RPP;
   constexpr bool RAGGED = (WTM % RPP) != 0;
   f16x8 resv[WM][NPASS];
-  if (p.res_mode != OD_RES_NONE && p.splitk <= 1) {
+  if (res_mode != OD_RES_NONE && !splitk) {
 #pragma unroll
     for (int wr = 0; wr < WM; ++wr)
 #pragma unroll
@@ -143,10 +204,10 @@ static __device__ __forceinline__ void conv_epilogue(const ConvKP& p, char* smem
         int m = m0 + wr * WTM + ps * RPP + tid / CH;
         f16x8 r = {0, 0, 0, 0, 0, 0, 0, 0};
         if (RAGGED && ps * RPP + tid / CH >= WTM) m = p.M;
-        if (p.tconv && m < p.M) m = od_tconv_pixel(p, (unsigned)m, WM * MT * 16);
+        if (tconv && m < p.M) m = od_tconv_pixel(p, (unsigned)m, WM * MT * 16);
         if (m >= 0 && m < p.M && n < p.Cout) {
           long long roff;
-          if (p.res_mode == OD_RES_SAME) {
+          if (res_mode == OD_RES_SAME) {
             roff = (long long)m * p.Cout + n;
           } else {
             const unsigned b = (unsigned)m / (unsigned)p.HoWo;
@@ -170,7 +231,7 @@ static __device__ __forceinline__ void conv_epilogue(const ConvKP& p, char* smem
       }
     }
     __syncthreads();
-    if (p.splitk > 1) {
+    if (splitk) {
       // split-K: store this workgroup's partial tile into ITS slab of the f32 workspace (plain 16-B stores, no atomics:
       // od_conv_finish sums the slabs in a fixed order, so the result is bit-reproducible); scale / bias / activation /
       // residual happen there too
@@ -192,7 +253,7 @@ static __device__ __forceinline__ void conv_epilogue(const ConvKP& p, char* smem
     for (int ps = 0; ps < NPASS; ++ps) {
       const int row = ps * RPP + tid / CH;
       int m = (RAGGED && row >= WTM) ? p.M : m0 + wr * WTM + row;
-      if (p.tconv && m < p.M) m = od_tconv_pixel(p, (unsigned)m, WM * MT * 16);
+      if (tconv && m < p.M) m = od_tconv_pixel(p, (unsigned)m, WM * MT * 16);
       if (m >= 0 && m < p.M && n < p.Cout) {
         const f32x4 v0 = *(const f32x4*)(stg + row * SLD + c8);
         const f32x4 v1 = *(const f32x4*)(stg + row * SLD + c8 + 4);
@@ -202,21 +263,22 @@ static __device__ __forceinline__ void conv_epilogue(const ConvKP& p, char* smem
           for (int e = 0; e < 8; ++e) v[e] = v[e] * sc[e] + bi[e];
         }
         if (STATS) {
-        } else if (p.act == OD_ACT_LEAKY) {
+        } else if (act == OD_ACT_LEAKY) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] = od_leaky(v[e], p.alpha);
-        } else if (p.act == OD_ACT_ELU) {
+        } else if (act == OD_ACT_ELU) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : p.alpha * od_expm1_fast(v[e]);
+          for (int e = 0; e < 8; ++e) v[e] = FX ? od_elu_select(v[e], p.alpha) : (v[e] > 0.f ? v[e] : p.alpha * od_expm1_fast(v[e]));
         }
-        if (!STATS && p.res_mode != OD_RES_NONE) {
+        if (!STATS && res_mode != OD_RES_NONE) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += (float)resv[wr][ps][e];
         }
         const unsigned b = (unsigned)m / (unsigned)p.HoWo;
         const unsigned pix = (unsigned)m - b * (unsigned)p.HoWo;
-        const long long ooff = (long long)b * p.obs + (long long)pix * p.ops + n;
-        if (p.out_f32) {
+        const long long ooff = FX ? (long long)(b * (unsigned)p.obs + pix * (unsigned)p.ops + (unsigned)n)
+                                  : (long long)b * p.obs + (long long)pix * p.ops + n;
+        if (out_f32) {
           float* o = (float*)p.out + ooff;
           *(f32x4*)o = f32x4{v[0], v[1], v[2], v[3]};
           *(f32x4*)(o + 4) = f32x4{v[4], v[5], v[6], v[7]};
@@ -291,10 +353,11 @@ struct ConvKernelInfo {
 };
 
 // conv_mfma.hip: the table kernels (od_conv_igemm), configs 0 .. num_cfgs - 1.  select fills *info with the config's tile and
-// the kernel for this layer (want_stats: the BatchNorm-statistics instantiation); false when the config has no such kernel
+// the kernel for this layer (want_stats: the BatchNorm-statistics instantiation; epi: the epilogue policy asked for, the
+// run-time instantiation where the config has none for it); false when the config has no such kernel
 // (configs 4-7 have no generic 3x3 variant: fn stays null, the tile is still filled in).  od_conv_finish sums split-K slabs.
 int od_conv_igemm_num_cfgs();
-bool od_conv_igemm_select(int cfg, int ksize, int Cin, bool want_stats, ConvKernelInfo* info);
+bool od_conv_igemm_select(int cfg, int ksize, int Cin, bool want_stats, int epi, ConvKernelInfo* info);
 int od_conv_finish_prepare(const ConvKP& p, od_launches* L);
 // conv_8ph.hip: 8-wave, BM x 256 tile, one workgroup per CU, staggered wave groups (3x3 and 1x1); idx 0 .. num_cfgs - 1 =
 // BM 256 .. 160.  tiles / tile_cost: the grid and the estimated us per tile (nk K tiles) that pick_cfg compares;
@@ -304,6 +367,12 @@ long od_conv_8ph_tiles(int idx, int M, int Cout);
 double od_conv_8ph_tile_cost(int idx, int nk);
 bool od_conv_8ph_can_fuse_pointwise(const ConvKP& p);
 bool od_conv_8ph_select(int idx, const ConvKP& p, int ksize, ConvKernelInfo* info);
+// conv_8ph_inst.hip, compiled once per tile height (MF1 = 4..1 <-> idx 0..3): the instantiation for (ksize, fused
+// pointwise layer, epilogue policies of the two layers); false when the tile height has none for that combination
+bool od_conv_8ph_variant_mf4(int ksize, bool pw, int epi, int epi2, const void** fn, const char** name);
+bool od_conv_8ph_variant_mf3(int ksize, bool pw, int epi, int epi2, const void** fn, const char** name);
+bool od_conv_8ph_variant_mf2(int ksize, bool pw, int epi, int epi2, const void** fn, const char** name);
+bool od_conv_8ph_variant_mf1(int ksize, bool pw, int epi, int epi2, const void** fn, const char** name);
 // conv_tconv.hip: streaming backward-data kernel of the first stride-2 convolution (dZ 64 channels -> dX 32 channels)
 bool od_tconv_small_supported(const od_conv_desc* d);
 int od_tconv_small_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L);

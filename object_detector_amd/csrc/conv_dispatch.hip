@@ -167,6 +167,12 @@ int conv_describe(const od_ctx* ctx, const od_conv_desc* d, bool want_stats, od_
   p.w_bytes = (unsigned)((long long)od_round_up(d->Cout, 256) * p.Kstride * 2);
   p.obs = d->out_batch_stride ? d->out_batch_stride : (long long)p.HoWo * d->Cout;
   p.ops = d->out_pix_stride ? d->out_pix_stride : d->Cout;
+  // 32-bit output offsets (the epilogues compiled for one activation / residual / output type form them that way): the
+  // last element an image's rows can reach through the strides, on the largest map of a grouped launch
+  long long hw_max = p.HoWo;
+  for (int i = 0; grouped && i < d->nseg; ++i) hw_max = hw_max > (long long)d->seg_H[i] * d->seg_W[i] ? hw_max : (long long)d->seg_H[i] * d->seg_W[i];
+  p.off32 = p.obs >= 0 && p.ops >= 0 && (long long)d->B * p.obs < (1LL << 31) &&
+            (long long)(d->B - 1) * p.obs + (hw_max - 1) * p.ops + d->Cout < (1LL << 31);
   p.splitk = 1;
   p.steps_per_split = 0;
   p.ws = (float*)d->splitk_workspace;
@@ -196,7 +202,7 @@ int conv_select(int cfg, const od_conv_desc* d, const ConvKP& p, bool want_stats
     od_set_error("od_conv2d_fwd: tile_cfg %d (8-phase kernel) needs Cin %% 64 == 0 and no transposed gather", cfg);
     return OD_ERR_INVALID;
   }
-  if (od_conv_igemm_select(cfg, d->ksize, d->Cin, want_stats, k)) return OD_OK;
+  if (od_conv_igemm_select(cfg, d->ksize, d->Cin, want_stats, od_epi_of(p), k)) return OD_OK;
   od_set_error("od_conv2d_fwd: tile_cfg %d needs Cin %% %d == 0 for 3x3 (Cin = %d); use cfg 0-3", cfg, k->BK, d->Cin);
   return OD_ERR_INVALID;
 }
@@ -289,10 +295,10 @@ int conv_prepare(od_ctx* ctx, const od_conv_desc* desc, bool want_stats, od_laun
       p.splitk = od_ceil_div(nk, p.steps_per_split);
     }
   }
-  if (d->w2 && use_e8 && od_conv_8ph_can_fuse_pointwise(p)) {
-    p.w2 = (const f16*)d->w2;
-    if (int rc = conv_select(cfg, d, p, want_stats, &k)) return rc;
-  }
+  if (d->w2 && use_e8 && od_conv_8ph_can_fuse_pointwise(p)) p.w2 = (const f16*)d->w2;
+  // split-K and the fused layer are settled: the instantiation for this launch's epilogue (same tile as above; split-K
+  // slabs take the run-time one)
+  if (int rc = conv_select(cfg, d, p, want_stats, &k)) return rc;
   // Step 7: the launch records
   if (int rc = od_ensure_lds(ctx, k.fn, k.lds)) return rc;
   // the 8-wave kernel's epilogue needs no LDS unless it writes split-K slabs: ask only for the two K-tile buffers then

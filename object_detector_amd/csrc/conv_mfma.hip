@@ -51,7 +51,9 @@ struct ConvCfg {
 // SPEC: wave specialisation.  The workgroup has 2 x WM*WN waves: the first half only runs MFMAs (consumers), the second
 // half only issues the LDS-DMA (loaders) -- an LDS-DMA instruction costs its issuing wave ~70 cycles, which otherwise
 // comes straight out of the MFMA stream.  Both halves meet at the same per-step barrier.
-template <int BM, int BN, int BK, int STAGES, int WM, int WN, int KS, int MINW, bool UNI, int SPEC, bool STATS = false>
+// EPI: the epilogue policy (conv_common.h), the last template argument.
+template <int BM, int BN, int BK, int STAGES, int WM, int WN, int KS, int MINW, bool UNI, int SPEC, bool STATS = false,
+          int EPI = OD_EPI_RT>
 __global__ __launch_bounds__(WM* WN * 64 * (SPEC ? 2 : 1), MINW) void od_conv_igemm(ConvKP p) {
   using Cf = ConvCfg<BM, BN, BK, STAGES, WM, WN, SPEC>;
   constexpr int NT = Cf::NT, AR = Cf::AR, BR = Cf::BR, RPR = Cf::RPR, ROWB = Cf::ROWB;
@@ -308,7 +310,7 @@ __global__ __launch_bounds__(WM* WN * 64 * (SPEC ? 2 : 1), MINW) void od_conv_ig
   }
   __syncthreads();  // all fragment reads done before the ring is reused as epilogue staging
 
-  conv_epilogue<BN, WM, WN, MT, NTL, Cf::NTHREADS, STATS>(p, smem, acc, m0, n0, tid_all, is_consumer ? wm : -1, wn, l15, lq);
+  conv_epilogue<BN, WM, WN, MT, NTL, Cf::NTHREADS, STATS, EPI>(p, smem, acc, m0, n0, tid_all, is_consumer ? wm : -1, wn, l15, lq);
 }
 
 // split-K finish: out = act(scale * sum_s slab[s] + bias) (+ residual); slabs summed in ascending s (deterministic)
@@ -370,12 +372,27 @@ struct TileCfg {
   // k[variant][STATS]; variant 0: KS == 1 (channel tail masked per lane: any Cin % 8 == 0), 1: KS == 3 with Cin % BK == 0,
   // 2: KS == 3 with any Cin % 8 == 0 (per-lane tap decomposition; fn is null where the config does not have it)
   struct { const void* fn; const char* name; } k[3][2];
+  // fx[variant 0 / 1][i]: the plain kernel compiled for epilogue policy kFxEpi[i]
+  struct { const void* fn; const char* name; } fx[2][4];
 };
+// the policies of the f16 plans' table-kernel launches: backbone 1x1 / 3x3 (+ residual), neck and prediction module.
+// Deliberately f16 only: every policy costs 16 more instantiations (8 configs x 1x1 / 3x3) in this translation unit, and the
+// f32-output launches of the mixed plan on the table configs (laterals, stage-5 residual stream) are not on the
+// benchmarked plan -- they run the run-time instantiation (tests/test_gpu_conv_epilogue_variants.py pins that).
+constexpr int kFxEpi[4] = {OD_EPI_LEAKY_NONE_F16, OD_EPI_LEAKY_SAME_F16, OD_EPI_ELU_NONE_F16, OD_EPI_ELU_UP2_F16};
 
 // an od_conv_igemm instantiation and its name; OD_K: the pair plain / STATS of one variant, OD_NOK: a variant left out
 #define OD_K1(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, STATS)                                                       \
   {(const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, STATS>,                                     \
-   "od_conv_igemm<" #BM ", " #BN ", " #BK ", " #ST ", " #WM ", " #WN ", " #KS ", " #MINW ", " #UNI ", " #SPEC ", " #STATS ">"}
+   "od_conv_igemm<" #BM ", " #BN ", " #BK ", " #ST ", " #WM ", " #WN ", " #KS ", " #MINW ", " #UNI ", " #SPEC ", " #STATS ", -1>"}
+#define OD_KX1(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, EPI)                                                         \
+  {(const void*)&od_conv_igemm<BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, false, EPI>,                                \
+   "od_conv_igemm<" #BM ", " #BN ", " #BK ", " #ST ", " #WM ", " #WN ", " #KS ", " #MINW ", " #UNI ", " #SPEC ", false, " OD_STR(EPI) ">"}
+#define OD_KX(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC)                                                             \
+  {OD_KX1(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, OD_EPI_LEAKY_NONE_F16),                                          \
+   OD_KX1(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, OD_EPI_LEAKY_SAME_F16),                                          \
+   OD_KX1(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, OD_EPI_ELU_NONE_F16),                                            \
+   OD_KX1(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, OD_EPI_ELU_UP2_F16)}
 #define OD_K(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC)                                                              \
   {OD_K1(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, false), OD_K1(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC, true)}
 #define OD_NOK(BM, BN, BK, ST, WM, WN, KS, MINW, UNI, SPEC) {}
@@ -383,7 +400,8 @@ struct TileCfg {
 #define OD_CFG(BM, BN, BK, ST, WM, WN, MINW, SPEC, K3G)                                                                 \
   {BM, BN, BK, WM * WN * 64 * (SPEC + 1), (size_t)ConvCfg<BM, BN, BK, ST, WM, WN, SPEC>::LDS_BYTES,                     \
    {OD_K(BM, BN, BK, ST, WM, WN, 1, MINW, true, SPEC), OD_K(BM, BN, BK, ST, WM, WN, 3, MINW, true, SPEC),               \
-    K3G(BM, BN, BK, ST, WM, WN, 3, MINW, false, SPEC)}}
+    K3G(BM, BN, BK, ST, WM, WN, 3, MINW, false, SPEC)},                                                                 \
+   {OD_KX(BM, BN, BK, ST, WM, WN, 1, MINW, true, SPEC), OD_KX(BM, BN, BK, ST, WM, WN, 3, MINW, true, SPEC)}}
 
 //         BM   BN  BK ST WM WN minwaves/SIMD, SPEC
 // Only what pick_cfg can select (round 3: the 22 table configs, the LDS-window kernels and the persistent window kernel
@@ -405,13 +423,19 @@ constexpr int kNumCfgs = sizeof(g_cfgs) / sizeof(g_cfgs[0]);
 
 int od_conv_igemm_num_cfgs() { return kNumCfgs; }
 
-bool od_conv_igemm_select(int cfg, int ksize, int Cin, bool want_stats, ConvKernelInfo* info) {
+bool od_conv_igemm_select(int cfg, int ksize, int Cin, bool want_stats, int epi, ConvKernelInfo* info) {
   if (cfg < 0 || cfg >= kNumCfgs) return false;
   const TileCfg& tc = g_cfgs[cfg];
   // kernel variant: 1x1 / 3x3-uniform-tap / 3x3-generic
-  const auto& k = tc.k[ksize == 1 ? 0 : ((Cin % tc.BK) == 0 ? 1 : 2)][want_stats];
+  const int var = ksize == 1 ? 0 : ((Cin % tc.BK) == 0 ? 1 : 2);
+  const auto& k = tc.k[var][want_stats];
   *info = {k.fn, k.name, tc.BM, tc.BN, tc.BK, tc.threads, tc.lds};
-  return k.fn != nullptr;
+  for (int i = 0; i < 4 && var < 2 && !want_stats; ++i)
+    if (kFxEpi[i] == epi) {  // the same tile with the epilogue compiled for this launch's policy
+      info->fn = tc.fx[var][i].fn;
+      info->name = tc.fx[var][i].name;
+    }
+  return info->fn != nullptr;
 }
 
 int od_conv_finish_prepare(const ConvKP& p, od_launches* L) {
