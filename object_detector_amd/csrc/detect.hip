@@ -6,10 +6,12 @@
 //   pass 1  (od_detect_pass1)  reads pred once: confidences in LDS, decoded boxes out, the 4096-bin first-digit histogram of
 //           all scores (LDS atomics -> global), and ONE float per prior: its largest confidence (rowmax)
 //   pass 2  (od_detect_pass2)  finds the first digit d0 of the K-th key from the histogram, then reads rowmax and recomputes
-//           (same code, bit-identical) the confidences of ONLY the priors whose best score reaches the d0 bin -- a fraction of
-//           a percent of them -- and partitions those into winners (digit > d0) and the d0-bin candidate list, as 64-bit keys
-//   refine  (od_detect_refine_sort)  one workgroup per image: radix-select inside the d0 bin on the remaining 51 key bits,
-//           bitonic sort of the K winners in LDS, gather of their boxes / classes for the NMS, counts; re-zeroes the histogram
+//           (od_row_conf again: bit-identical) the confidences of ONLY the priors whose best score reaches the d0 bin -- a
+//           fraction of a percent of them -- and partitions those into winners (digit > d0) and the d0-bin candidate list, as
+//           64-bit keys
+//   refine  (od_detect_refine_sort)  one workgroup per image: od_radix_refine inside the d0 bin on the remaining <= 51 key
+//           bits, od_bitonic_sort_desc of the K winners in LDS, od_rank_gather of their boxes / classes for the NMS, counts;
+//           re-zeroes the histogram.  All three are topk_common.h's, shared with topk.hip, nms.hip and detect_wide.hip
 //   od_nms_mask, od_nms_scan  as in od_nms (nms.hip)
 // Same total order, same exact selection, same kept indices as the three-call path (tests compare them bit for bit).
 // od_detect_candidates is the same call stopped after refine (boxes, sorted keys, counts): one view of od_tta_merge (tta.hip).
@@ -21,9 +23,8 @@
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int NB = OD_TOPK_NB;
-constexpr int DT_ROWS = 256;      // priors per workgroup (one thread each)
+constexpr int DT_ROWS = OD_DT_ROWS, DT2_RPT = OD_DT2_RPT;  // priors per workgroup in pass 1 / per thread in pass 2
 constexpr int DT_CAND_CAP = 1024; // d0-bin candidates a workgroup compacts in LDS before falling back to global atomics
 
 // grid (ceil(P / 256), B).  LDS: rows [256][C] f32 (confidences are computed in place over the class logits) + hist[4096].
@@ -82,8 +83,6 @@ __global__ __launch_bounds__(256) void od_detect_pass1(const float* __restrict__
   }
 }
 
-constexpr int DT2_RPT = 4;  // priors per thread in pass 2 (1024 per workgroup)
-
 // grid (ceil(P / 1024), B).  LDS: per-thread row scratch [256][C] + l_out [K] + l_cand [DT_CAND_CAP] keys.
 __global__ __launch_bounds__(256) void od_detect_pass2(const float* __restrict__ pred, const float* __restrict__ rowmax,
                                                        const int* __restrict__ hist, TopkState* __restrict__ st,
@@ -108,34 +107,20 @@ __global__ __launch_bounds__(256) void od_detect_pass2(const float* __restrict__
     st[b].krem = d0 < 0 ? 0 : K - above;
   }
   const int p_base = blockIdx.x * (DT_ROWS * DT2_RPT);
-  // the priors whose best score reaches the d0 bin (a few per cent at most) are first COMPACTED into an LDS list and then
-  // taken one per thread: walking them where they sit ran every wave through the row code at a few per cent lane occupancy
-  float mxv[DT2_RPT];
-#pragma unroll
-  for (int u = 0; u < DT2_RPT; ++u) {
-    const int p = p_base + u * DT_ROWS + tid;
-    mxv[u] = p < P ? rowmax[(long long)b * P + p] : 0.f;
-  }
-#pragma unroll
-  for (int u = 0; u < DT2_RPT; ++u) {
-    const unsigned sb = od_score_bits(mxv[u], thr);
-    if (sb && od_digit0(sb, dbase, dshift) >= d0) hot_list[atomicAdd(&n_hot, 1)] = p_base + u * DT_ROWS + tid;
-  }
-  __syncthreads();
-  const int nh = n_hot;
+  const int nh = od_compact_hot_priors(rowmax + (long long)b * P, P, p_base, thr, dbase, dshift, d0, hot_list, &n_hot);
   for (int e = tid; e < nh; e += 256) {
     const int p = hot_list[e];
     float* row = rows + tid * C;
     const float* src = pred + ((long long)b * P + p) * C;
     for (int c = 0; c < 2 + NC; ++c) row[c] = src[c];
-    od_row_conf(row, NC, row + 2);  // the same code as pass 1: bit-identical confidences
+    od_row_conf(row, NC, row + 2);  // as in pass 1: bit-identical confidences
     for (int c = 0; c < NC; ++c) {
       const unsigned sbc = od_score_bits(row[2 + c], thr);
       if (!sbc) continue;
       const int dg = od_digit0(sbc, dbase, dshift);
       if (dg < d0) continue;
       const unsigned flat = (unsigned)(p * NC + c);
-      const u64 key = ((u64)sbc << 32) | (u64)(0xFFFFFFFFu - flat);
+      const u64 key = od_make_key(sbc, flat);
       if (dg > d0) {  // fewer than K of these in the whole image
         l_out[atomicAdd(&n_out, 1)] = key;
       } else {
@@ -150,28 +135,22 @@ __global__ __launch_bounds__(256) void od_detect_pass2(const float* __restrict__
   }
   __syncthreads();
   const int nc = min(n_cand, DT_CAND_CAP);
-  if (tid == 0) {
-    base_out = n_out ? atomicAdd(&st[b].nout, n_out) : 0;
-    base_cand = nc ? atomicAdd(&st[b].ncand, nc) : 0;
-  }
-  __syncthreads();
-  u64* ok = keys + (long long)b * K + base_out;
-  for (int j = tid; j < n_out; j += 256) ok[j] = l_out[j];
+  if (tid == 0) base_cand = nc ? atomicAdd(&st[b].ncand, nc) : 0;
+  od_block_copy_out(l_out, n_out, &st[b].nout, keys + (long long)b * K, &base_out);  // (its barrier publishes base_cand too)
   u64* oc = cand + (long long)b * cand_stride + base_cand;
   for (int j = tid; j < nc; j += 256) oc[j] = l_cand[j];
 }
 
-// One workgroup (1024 threads) per image: refine inside the d0 bin on the sub-key (low dshift bits of score - dbase) << 32 |
-// ~flat (<= 51 bits, digits of 11, 8, 11, 11, 10 bits from the top), then sort + gather for the NMS.
+// One workgroup (1024 threads) per image: the winners pass 2 wrote straight to the output, plus the krem best of the d0-bin
+// candidate list (od_radix_refine), then sort + gather for the NMS.
 __global__ __launch_bounds__(1024) void od_detect_refine_sort(const float* __restrict__ boxes, TopkState* __restrict__ st,
                                                               u64* __restrict__ keys, const u64* __restrict__ cand,
                                                               int* __restrict__ hist, int* __restrict__ counts, int P, int NC,
                                                               int K, int KP, long long cand_stride, u64* __restrict__ skeys,
                                                               f32x4* __restrict__ sbox, int* __restrict__ scls, unsigned dbase,
                                                               int dshift) {
-  __shared__ int lh[NB];
   __shared__ u64 s[1024];
-  __shared__ int sh_digit, sh_above, sh_inbin, n_win;
+  __shared__ int n_win;
   const int b = blockIdx.x, tid = threadIdx.x;
   const TopkState t = st[b];
   const int nout0 = min(t.nout, K);
@@ -181,81 +160,16 @@ __global__ __launch_bounds__(1024) void od_detect_refine_sort(const float* __res
   __syncthreads();
   if (t.d0 >= 0 && t.krem > 0) {
     const u64* ic = cand + (long long)b * cand_stride;
-    const int nc = t.ncand;
-    int krem = t.krem;
-    const unsigned low_mask = (1u << dshift) - 1u;  // score bits below the first digit
-    u64 prefix = 0, pmask = 0;
-    const int shifts[5] = {40, 32, 21, 10, 0};
-    const int widths[5] = {11, 8, 11, 11, 10};
-    bool whole = (nc == krem);  // take the whole bin
-    for (int ps = 0; ps < 5 && !whole; ++ps) {
-      const int sh = shifts[ps], nbins = 1 << widths[ps];
-      for (int i = tid; i < NB; i += 1024) lh[i] = 0;
-      __syncthreads();
-      for (int i = tid; i < nc; i += 1024) {
-        const u64 key = ic[i];
-        const u64 sub = ((u64)(((unsigned)(key >> 32) - dbase) & low_mask) << 32) | (key & 0xFFFFFFFFull);
-        if ((sub & pmask) == prefix) atomicAdd(&lh[(int)((sub >> sh) & (u64)(nbins - 1))], 1);
-      }
-      __syncthreads();
-      if (tid < 64) {
-        int above, in_bin;
-        const int d = od_find_digit(lh, NB, krem, &above, &in_bin);  // bins >= nbins are empty
-        if (tid == 0) {
-          sh_digit = d;
-          sh_above = above;
-          sh_inbin = in_bin;
-        }
-      }
-      __syncthreads();
-      prefix |= (u64)sh_digit << sh;
-      pmask |= (u64)(nbins - 1) << sh;
-      krem -= sh_above;
-      whole = (sh_inbin == krem);
-      __syncthreads();
-    }
-    // winners: sub-key > prefix on the masked bits, or == prefix (then the whole remaining bin is taken)
-    for (int i = tid; i < nc; i += 1024) {
-      const u64 key = ic[i];
-      const u64 sub = ((u64)(((unsigned)(key >> 32) - dbase) & low_mask) << 32) | (key & 0xFFFFFFFFull);
-      if ((sub & pmask) >= prefix) {
-        const int slot = nout0 + atomicAdd(&n_win, 1);
-        if (slot < K) s[slot] = key;
-      }
-    }
+    od_radix_refine(
+        t.ncand, t.ncand, t.krem, dbase, dshift, [&](int i) { return ic[i]; },
+        [&](u64 key) {
+          const int slot = nout0 + atomicAdd(&n_win, 1);
+          if (slot < K) s[slot] = key;
+        });
     __syncthreads();
   }
-  const int n = min(nout0 + n_win, K);
-  // bitonic sort, descending = (conf desc, flat asc)
-  for (int k = 2; k <= KP; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const int ixj = tid ^ j;
-      if (tid < KP && ixj > tid) {
-        const u64 a = s[tid], c = s[ixj];
-        const bool desc = (tid & k) == 0;
-        if (desc ? (a < c) : (a > c)) {
-          s[tid] = c;
-          s[ixj] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (tid < KP) {
-    const u64 key = s[tid];
-    skeys[(long long)b * KP + tid] = key;
-    if (tid < K) keys[(long long)b * K + tid] = key;  // the API's key set: sorted here, unused slots 0
-    if (tid < n) {
-      const unsigned flat = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-      const unsigned p = flat / (unsigned)NC;
-      const unsigned c = flat - p * (unsigned)NC;
-      sbox[(long long)b * KP + tid] = *(const f32x4*)(boxes + ((long long)b * P + p) * 4);
-      scls[(long long)b * KP + tid] = (int)c;
-    }
-  }
-  if (tid == 0) counts[b] = n;
-  int* gh = hist + (long long)b * NB;  // leave the histogram zeroed for the next call
-  for (int i = tid; i < NB; i += 1024) gh[i] = 0;
+  od_bitonic_sort_desc(s, KP);
+  od_rank_gather(s, min(nout0 + n_win, K), b, boxes, P, NC, K, KP, skeys, sbox, scls, keys, counts, hist);
 }
 
 // one workgroup per image: row r of out[b] = {flat index (int bits), conf, x1, y1, x2, y2} of kept detection r, the

@@ -6,18 +6,16 @@
 //   pass 2  (od_detect_pass2_wide)  winners (digit > d0) straight to the output as in od_detect_pass2; the d0-bin candidates
 //           are only counted, and every prior that may hold one is recorded as a HotRow (index + row stats, <= P per image)
 //           instead of listing the d0-bin keys themselves (up to P * NC per image)
-//   refine  (od_detect_refine_rows)  one workgroup per image: the d0-bin keys are re-derived from the HotRows for every radix
-//           pass, then the sort / gather of od_detect_refine_sort
-// The workspace is O(B * P) for any NC (det_layout in detect.hip).  Kept in a TU of its own so that the NC <= 76 kernels of
-// detect.hip compile exactly as before.  Compiled with -ffp-contract=off like detect.hip.
+//   refine  (od_detect_refine_rows)  one workgroup per image: od_detect_refine_sort with the d0-bin keys re-derived from the
+//           HotRows for every radix pass
+// Pass 2's compaction and copy-out, the radix refine, the sort and the gather are topk_common.h's: one copy for both dispatches.
+// The workspace is O(B * P) for any NC (det_layout in detect.hip).  Compiled with -ffp-contract=off like detect.hip.
 #include "post_common.h"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int NB = OD_TOPK_NB;
-constexpr int DT_ROWS = 256;  // priors per workgroup (one thread each)
-constexpr int DT2_RPT = 4;    // priors per thread in pass 2 (1024 per workgroup)
+constexpr int DT_ROWS = OD_DT_ROWS, DT2_RPT = OD_DT2_RPT;  // priors per workgroup in pass 1 / per thread in pass 2
 
 // grid (ceil(P / 256), B).  Static LDS: the column tile + hist[4096].  conf_out: optional dense [B,P,NC] confidences.
 __global__ __launch_bounds__(256) void od_detect_pass1_wide(const float* __restrict__ pred, const float* __restrict__ priors,
@@ -98,15 +96,7 @@ __global__ __launch_bounds__(256) void od_detect_pass2_wide(const float* __restr
     st[b].krem = d0 < 0 ? 0 : K - above;
   }
   const int p_base = blockIdx.x * (DT_ROWS * DT2_RPT);
-#pragma unroll
-  for (int u = 0; u < DT2_RPT; ++u) {
-    const int p = p_base + u * DT_ROWS + tid;
-    const float mxv = p < P ? rowmax[(long long)b * P + p] : 0.f;
-    const unsigned sb = od_score_bits(mxv, thr);
-    if (sb && od_digit0(sb, dbase, dshift) >= d0) hot_list[atomicAdd(&n_hot, 1)] = p;
-  }
-  __syncthreads();
-  const int nh = n_hot;
+  const int nh = od_compact_hot_priors(rowmax + (long long)b * P, P, p_base, thr, dbase, dshift, d0, hot_list, &n_hot);
   if (tid == 0) base_hot = nh ? atomicAdd(&nhot[b], nh) : 0;
   __syncthreads();
   HotRow* hb = hot + (long long)b * P + base_hot;
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(256) void od_detect_pass2_wide(const float* __restr
       if (!sbc) continue;
       const int dg = od_digit0(sbc, dbase, dshift);
       if (dg > d0) {
-        l_out[atomicAdd(&n_out, 1)] = ((u64)sbc << 32) | (u64)(0xFFFFFFFFu - (unsigned)(p * NC + c));
+        l_out[atomicAdd(&n_out, 1)] = od_make_key(sbc, (unsigned)(p * NC + c));
       } else if (dg == d0) {
         ++my_cand;
       }
@@ -129,52 +119,8 @@ __global__ __launch_bounds__(256) void od_detect_pass2_wide(const float* __restr
   }
   if (my_cand) atomicAdd(&n_cand, my_cand);
   __syncthreads();
-  if (tid == 0) {
-    base_out = n_out ? atomicAdd(&st[b].nout, n_out) : 0;
-    if (n_cand) atomicAdd(&st[b].ncand, n_cand);
-  }
-  __syncthreads();
-  u64* ok = keys + (long long)b * K + base_out;
-  for (int j = tid; j < n_out; j += 256) ok[j] = l_out[j];
-}
-
-// The end of od_detect_refine_sort (the same code): bitonic sort of the s[0..KP) keys, the API's
-// sorted key set, gather of the first n keys' boxes / classes for the NMS, counts; re-zeroes the image's histogram.
-__device__ __forceinline__ void od_detect_sort_gather(u64* s, const int n, const float* __restrict__ boxes,
-                                                      u64* __restrict__ keys, int* __restrict__ hist, int* __restrict__ counts,
-                                                      int P, int NC, int K, int KP, u64* __restrict__ skeys,
-                                                      f32x4* __restrict__ sbox, int* __restrict__ scls) {
-  const int b = blockIdx.x, tid = threadIdx.x;
-  // bitonic sort, descending = (conf desc, flat asc)
-  for (int k = 2; k <= KP; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const int ixj = tid ^ j;
-      if (tid < KP && ixj > tid) {
-        const u64 a = s[tid], c = s[ixj];
-        const bool desc = (tid & k) == 0;
-        if (desc ? (a < c) : (a > c)) {
-          s[tid] = c;
-          s[ixj] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (tid < KP) {
-    const u64 key = s[tid];
-    skeys[(long long)b * KP + tid] = key;
-    if (tid < K) keys[(long long)b * K + tid] = key;  // the API's key set: sorted here, unused slots 0
-    if (tid < n) {
-      const unsigned flat = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-      const unsigned p = flat / (unsigned)NC;
-      const unsigned c = flat - p * (unsigned)NC;
-      sbox[(long long)b * KP + tid] = *(const f32x4*)(boxes + ((long long)b * P + p) * 4);
-      scls[(long long)b * KP + tid] = (int)c;
-    }
-  }
-  if (tid == 0) counts[b] = n;
-  int* gh = hist + (long long)b * NB;  // leave the histogram zeroed for the next call
-  for (int i = tid; i < NB; i += 1024) gh[i] = 0;
+  if (tid == 0 && n_cand) atomicAdd(&st[b].ncand, n_cand);
+  od_block_copy_out(l_out, n_out, &st[b].nout, keys + (long long)b * K, &base_out);
 }
 
 // One workgroup (1024 threads) per image: od_detect_refine_sort with the d0-bin candidates re-derived from the HotRows
@@ -185,9 +131,8 @@ __global__ __launch_bounds__(1024) void od_detect_refine_rows(const float* __res
                                                               int* __restrict__ hist, int* __restrict__ counts, int P, int NC,
                                                               int K, int KP, u64* __restrict__ skeys, f32x4* __restrict__ sbox,
                                                               int* __restrict__ scls, float thr, unsigned dbase, int dshift) {
-  __shared__ int lh[NB];
   __shared__ u64 s[1024];
-  __shared__ int sh_digit, sh_above, sh_inbin, n_win;
+  __shared__ int n_win;
   const int b = blockIdx.x, tid = threadIdx.x, C = NC + 6;
   const TopkState t = st[b];
   const int nout0 = min(t.nout, K);
@@ -198,60 +143,23 @@ __global__ __launch_bounds__(1024) void od_detect_refine_rows(const float* __res
     const HotRow* hr = hot + (long long)b * P;
     const float* pb = pred + (long long)b * P * C;
     const int nel = nhot[b] * NC;  // < 2^31: P * NC is
-    const int nc = t.ncand;
-    int krem = t.krem;
-    const unsigned low_mask = (1u << dshift) - 1u;
-    // the key of (row h, class c) if it lies in the d0 bin, else 0
-    auto d0_key = [&](int i) -> u64 {
-      const int h = i / NC, c = i - h * NC;
-      const HotRow r = hr[h];
-      const unsigned sb = od_score_bits(od_wide_conf(pb[(long long)r.p * C + 2 + c], r.r), thr);
-      if (!sb || od_digit0(sb, dbase, dshift) != t.d0) return 0ull;
-      return ((u64)sb << 32) | (u64)(0xFFFFFFFFu - (unsigned)(r.p * NC + c));
-    };
-    u64 prefix = 0, pmask = 0;
-    const int shifts[5] = {40, 32, 21, 10, 0};
-    const int widths[5] = {11, 8, 11, 11, 10};
-    bool whole = (nc == krem);
-    for (int ps = 0; ps < 5 && !whole; ++ps) {
-      const int sh = shifts[ps], nbins = 1 << widths[ps];
-      for (int i = tid; i < NB; i += 1024) lh[i] = 0;
-      __syncthreads();
-      for (int i = tid; i < nel; i += 1024) {
-        const u64 key = d0_key(i);
-        if (!key) continue;
-        const u64 sub = ((u64)(((unsigned)(key >> 32) - dbase) & low_mask) << 32) | (key & 0xFFFFFFFFull);
-        if ((sub & pmask) == prefix) atomicAdd(&lh[(int)((sub >> sh) & (u64)(nbins - 1))], 1);
-      }
-      __syncthreads();
-      if (tid < 64) {
-        int above, in_bin;
-        const int d = od_find_digit(lh, NB, krem, &above, &in_bin);
-        if (tid == 0) {
-          sh_digit = d;
-          sh_above = above;
-          sh_inbin = in_bin;
-        }
-      }
-      __syncthreads();
-      prefix |= (u64)sh_digit << sh;
-      pmask |= (u64)(nbins - 1) << sh;
-      krem -= sh_above;
-      whole = (sh_inbin == krem);
-      __syncthreads();
-    }
-    for (int i = tid; i < nel; i += 1024) {
-      const u64 key = d0_key(i);
-      if (!key) continue;
-      const u64 sub = ((u64)(((unsigned)(key >> 32) - dbase) & low_mask) << 32) | (key & 0xFFFFFFFFull);
-      if ((sub & pmask) >= prefix) {
-        const int slot = nout0 + atomicAdd(&n_win, 1);
-        if (slot < K) s[slot] = key;
-      }
-    }
+    od_radix_refine(
+        nel, t.ncand, t.krem, dbase, dshift,
+        [&](int i) -> u64 {  // the key of (row h, class c) if it lies in the d0 bin, else 0
+          const int h = i / NC, c = i - h * NC;
+          const HotRow r = hr[h];
+          const unsigned sb = od_score_bits(od_wide_conf(pb[(long long)r.p * C + 2 + c], r.r), thr);
+          if (!sb || od_digit0(sb, dbase, dshift) != t.d0) return 0ull;
+          return od_make_key(sb, (unsigned)(r.p * NC + c));
+        },
+        [&](u64 key) {
+          const int slot = nout0 + atomicAdd(&n_win, 1);
+          if (slot < K) s[slot] = key;
+        });
     __syncthreads();
   }
-  od_detect_sort_gather(s, min(nout0 + n_win, K), boxes, keys, hist, counts, P, NC, K, KP, skeys, sbox, scls);
+  od_bitonic_sort_desc(s, KP);
+  od_rank_gather(s, min(nout0 + n_win, K), b, boxes, P, NC, K, KP, skeys, sbox, scls, keys, counts, hist);
 }
 
 // od_gather_det_pred for NC > 76: the kept row's stats read straight from pred (one detection per thread)

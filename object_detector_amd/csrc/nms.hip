@@ -1,19 +1,18 @@
 // K8: class-aware greedy NMS on the K best candidates of every image (docs/MODEL.md:78-82: among the confident
 // predictions, same-class overlaps keep only the most confident).  Integer / bit work, latency-bound; three launches:
 //   sort : one workgroup per image, bitonic sort of the K 64-bit keys in LDS (descending = (conf desc, flat asc)),
-//          gather of the candidates' boxes / classes into rank order
+//          gather of the candidates' boxes / classes into rank order (od_bitonic_sort_desc / od_rank_gather of
+//          topk_common.h: the sort and gather at the end of od_detect's refine kernels are the same functions)
 //   mask : (K/64 x B) workgroups of 16 waves; lane = row i, each wave walks one 64-column word and builds the suppression bitmask
 //          M[i][w] bit j = (j > i && same class && inter > thr * union) -- one u64 per (row, 64-column block)
 //   scan : the image's mask is staged in LDS (<= 128 KiB), then ONE wavefront runs the greedy scan: each 64x64 diagonal
 //          block is resolved with scalar 64-bit ops on SGPRs (v_readlane; only rows that suppress something take a
 //          step), kept rows OR their mask rows into the running `removed` words, 16 LDS reads in flight per lane
-// The IoU predicate is division-free f32 arithmetic in a fixed order; this TU is compiled with -ffp-contract=off so
-// it is bit-identical to numpy's (oracle/nms.py), which is what makes the kept-index output bit-exact.
+// The IoU predicate (od_iou_exceeds, topk_common.h) is division-free f32 arithmetic in a fixed order; this TU is compiled with
+// -ffp-contract=off so it is bit-identical to numpy's (oracle/nms.py), which is what makes the kept-index output bit-exact.
 #include "post_common.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 __global__ __launch_bounds__(1024) void od_nms_sort(const float* __restrict__ boxes, const u64* __restrict__ keys,
                                                     const int* __restrict__ counts, int P, int NC, int K, int KP,
@@ -23,42 +22,8 @@ __global__ __launch_bounds__(1024) void od_nms_sort(const float* __restrict__ bo
   const int b = blockIdx.x, tid = threadIdx.x;
   if (tid < KP) s[tid] = tid < K ? keys[(long long)b * K + tid] : 0ull;
   __syncthreads();
-  for (int k = 2; k <= KP; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const int ixj = tid ^ j;
-      if (tid < KP && ixj > tid) {
-        const u64 a = s[tid], c = s[ixj];
-        const bool desc = (tid & k) == 0;
-        if (desc ? (a < c) : (a > c)) {
-          s[tid] = c;
-          s[ixj] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  if (tid < KP) {
-    const u64 key = s[tid];
-    skeys[(long long)b * KP + tid] = key;
-    const int n = counts[b];
-    if (tid < n) {
-      const unsigned flat = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-      const unsigned p = flat / (unsigned)NC;
-      const unsigned c = flat - p * (unsigned)NC;
-      sbox[(long long)b * KP + tid] = *(const f32x4*)(boxes + ((long long)b * P + p) * 4);
-      scls[(long long)b * KP + tid] = (int)c;
-    }
-  }
-}
-
-__device__ __forceinline__ bool suppresses(const f32x4 a, float area_a, const f32x4 c, float thr) {
-  const float ix1 = fmaxf(a[0], c[0]), iy1 = fmaxf(a[1], c[1]);
-  const float ix2 = fminf(a[2], c[2]), iy2 = fminf(a[3], c[3]);
-  const float iw = fmaxf(ix2 - ix1, 0.f), ih = fmaxf(iy2 - iy1, 0.f);
-  const float inter = iw * ih;
-  const float area_c = (c[2] - c[0]) * (c[3] - c[1]);
-  const float uni = (area_a + area_c) - inter;
-  return inter > thr * uni;
+  od_bitonic_sort_desc(s, KP);
+  od_rank_gather(s, counts[b], b, boxes, P, NC, K, KP, skeys, sbox, scls, nullptr, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(1024) void od_nms_mask(const f32x4* __restrict__ sbox, const int* __restrict__ scls,
@@ -90,7 +55,7 @@ __global__ __launch_bounds__(1024) void od_nms_mask(const f32x4* __restrict__ sb
       const int j = w * 64 + jj;  // wave-uniform -> LDS broadcast reads
       const f32x4 c = lb[j];
       const int cc = lc[j];
-      const bool hit = rowok && j > i && (strict || cc == ca) && suppresses(a, area_a, c, thr);
+      const bool hit = rowok && j > i && (strict || cc == ca) && od_iou_exceeds(a, area_a, c, thr);
       bits |= (u64)hit << jj;
     }
     mask[((long long)b * KP + i) * W + w] = bits;
@@ -158,7 +123,7 @@ __global__ __launch_bounds__(256) void od_nms_scan(const u64* __restrict__ mask,
     const int pos = base + __popcll(kw & ((1ull << lane) - 1ull));
     if (((kw >> lane) & 1ull) && pos < max_det) {
       const u64 key = skeys[(long long)b * KP + blk * 64 + lane];
-      keep_flat[(long long)b * max_det + pos] = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+      keep_flat[(long long)b * max_det + pos] = (int)od_key_flat(key);
     }
     base += __popcll(kw);
   }

@@ -5,8 +5,6 @@
 
 namespace {
 
-#define decode_one od_decode_one
-
 constexpr int PP_ROWS = 256;  // priors per workgroup
 
 // pred [B*P, C] -> conf [B*P, NC], boxes [B*P, 4];  C = 2 + NC + 4
@@ -38,7 +36,7 @@ __global__ __launch_bounds__(256) void od_head_post(const float* __restrict__ pr
     const int p = (int)(r % P);
     const f32x4 loc = {row[2 + NC], row[3 + NC], row[4 + NC], row[5 + NC]};
     const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
-    *(f32x4*)(boxes + r * 4) = decode_one(loc, pr, loc_scale, clip);
+    *(f32x4*)(boxes + r * 4) = od_decode_one(loc, pr, loc_scale, clip);
   }
   __syncthreads();
   const int nout = nrows * NC;
@@ -84,7 +82,7 @@ __global__ __launch_bounds__(256) void od_head_post_wide(const float* __restrict
     const int p = (int)(r % P);
     const f32x4 loc = {row[2 + NC], row[3 + NC], row[4 + NC], row[5 + NC]};
     const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
-    *(f32x4*)(boxes + r * 4) = decode_one(loc, pr, loc_scale, clip);
+    *(f32x4*)(boxes + r * 4) = od_decode_one(loc, pr, loc_scale, clip);
   }
 }
 
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(256) void od_decode(const float* __restrict__ locs,
   const int p = (int)(r % P);
   const f32x4 loc = *(const f32x4*)(locs + r * 4);
   const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
-  *(f32x4*)(boxes + r * 4) = decode_one(loc, pr, loc_scale, clip);
+  *(f32x4*)(boxes + r * 4) = od_decode_one(loc, pr, loc_scale, clip);
 }
 
 // out[b,y,x,c] = a[b,y,x,c] + up[b,y/2,x/2,c]; 8 channels (16 B) per thread

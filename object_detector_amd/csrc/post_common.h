@@ -1,6 +1,8 @@
-// Shared by post.hip (K5/K6), topk.hip (K7), detect.hip and detect_wide.hip (the fused product path): the confidence arithmetic and the
-// radix-select helpers.  Every TU that includes this is compiled with -ffp-contract=off, so the same source is the same
-// f32 op sequence everywhere (and the one of oracle/postprocess.py): confidences are bit-identical across kernels.
+// Shared by post.hip (K5/K6), topk.hip (K7), nms.hip (K8), detect.hip and detect_wide.hip (the fused product path) and tta.hip:
+// the confidence arithmetic and the histogram searches here; the key format, the radix refine, the sort / gather and the IoU
+// predicate in topk_common.h (included at the end).  Every TU that includes this is compiled with -ffp-contract=off, so the
+// same source is the same f32 op sequence everywhere (and the one of oracle/postprocess.py): confidences are bit-identical
+// across kernels.
 #pragma once
 #include "common.h"
 
@@ -206,6 +208,8 @@ __device__ __forceinline__ int od_find_digit(const int* hist, int nbins, int kre
   *in_bin = ib;
   return digit;
 }
+
+#include "topk_common.h"
 
 // a prior that may hold a d0-bin candidate, as pass 2 of the NC > 76 pipeline records it (detect_wide.hip)
 struct HotRow {

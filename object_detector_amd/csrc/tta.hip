@@ -18,7 +18,6 @@
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int TTA_MAX_VIEWS = 8;
 constexpr int TTA_MAX_K = 1024;
 
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(1024) void od_tta_merge_rank(TtaViews vw, int NC, i
     mykey[v] = 0ull;
     if (v < V && tid < lcnt[v]) {
       mykey[v] = vw.keys[v][(long long)b * K + tid];
-      lconf[v * TTA_MAX_K + tid] = (unsigned)(mykey[v] >> 32);
+      lconf[v * TTA_MAX_K + tid] = od_key_score_bits(mykey[v]);
     }
   }
   __syncthreads();
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(1024) void od_tta_merge_rank(TtaViews vw, int NC, i
 #pragma unroll
   for (int v = 0; v < TTA_MAX_VIEWS; ++v) {
     if (v >= V || tid >= lcnt[v]) continue;
-    const unsigned cb = (unsigned)(mykey[v] >> 32);
+    const unsigned cb = od_key_score_bits(mykey[v]);
     int rank = tid;
     for (int u = 0; u < V; ++u) {
       if (u == v) continue;
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(1024) void od_tta_merge_rank(TtaViews vw, int NC, i
       rank += lo;
     }
     if (rank >= K) continue;
-    const unsigned flat = 0xFFFFFFFFu - (unsigned)(mykey[v] & 0xFFFFFFFFull);
+    const unsigned flat = od_key_flat(mykey[v]);
     unsigned p = flat / (unsigned)NC;
     const unsigned c = flat - p * (unsigned)NC;
     p = min(p, (unsigned)(vw.P[v] - 1));  // a malformed key must not read outside the view's box table
@@ -129,23 +128,12 @@ __global__ __launch_bounds__(1024) void od_tta_merge_rank(TtaViews vw, int NC, i
       bx[2] = x2;
     }
     const long long o = (long long)b * KP + rank;
-    skeys[o] = ((u64)cb << 32) | (u64)(0xFFFFFFFFu - (unsigned)(rank * NC + (int)c));
+    skeys[o] = od_make_key(cb, (unsigned)(rank * NC + (int)c));
     sbox[o] = bx;
     scls[o] = (int)c;
     msrc[o * 2] = v;
     msrc[o * 2 + 1] = (int)flat;
   }
-}
-
-// od_nms_mask's predicate (nms.hip, oracle/nms.py): inter > thr * ((area_a + area_c) - inter)
-__device__ __forceinline__ bool tta_overlaps(const f32x4 a, float area_a, const f32x4 c, float thr) {
-  const float ix1 = fmaxf(a[0], c[0]), iy1 = fmaxf(a[1], c[1]);
-  const float ix2 = fminf(a[2], c[2]), iy2 = fminf(a[3], c[3]);
-  const float iw = fmaxf(ix2 - ix1, 0.f), ih = fmaxf(iy2 - iy1, 0.f);
-  const float inter = iw * ih;
-  const float area_c = (c[2] - c[0]) * (c[3] - c[1]);
-  const float uni = (area_a + area_c) - inter;
-  return inter > thr * uni;
 }
 
 // grid B, 1024 threads.  Kept detections are taken 256 at a time (max_det <= 256: one round).  Phase 1, voting only: the 16
@@ -172,7 +160,7 @@ __global__ __launch_bounds__(1024) void od_tta_vote_gather(const u64* __restrict
   for (int i = tid; i < n; i += 1024) {
     lb[i] = sbox[(long long)b * KP + i];
     lc[i] = scls[(long long)b * KP + i];
-    lw[i] = __uint_as_float((unsigned)(skeys[(long long)b * KP + i] >> 32));
+    lw[i] = __uint_as_float(od_key_score_bits(skeys[(long long)b * KP + i]));
   }
   float* o = out + (size_t)b * (1 + 6 * (size_t)max_det);
   if (tid == 0) o[0] = __int_as_float(nk);
@@ -189,7 +177,7 @@ __global__ __launch_bounds__(1024) void od_tta_vote_gather(const u64* __restrict
         const float area_a = (a[2] - a[0]) * (a[3] - a[1]);
         for (int w = 0; w < W; ++w) {
           const int j = w * 64 + lane;
-          const bool hit = j < n && (j == i || (lc[j] == ci && tta_overlaps(a, area_a, lb[j], vote_iou)));
+          const bool hit = j < n && (j == i || (lc[j] == ci && od_iou_exceeds(a, area_a, lb[j], vote_iou)));
           const u64 m = __ballot(hit);
           if (lane == 0) lmask[q * TTA_MW + w] = m;
         }

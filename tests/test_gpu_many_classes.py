@@ -54,34 +54,72 @@ def _fused_vs_unfused(cuda, pp, pred, thr, K, max_det):
     return conf, boxes, kc.cpu().numpy()
 
 
-# P = 130 / 258 do not fill a workgroup; P = 1030 / 514 / 258 with odd NC give P * (NC + 6) % 4 != 0 (rows 4-byte aligned)
-@pytest.mark.parametrize("NC,K,P,B", [(77, 300, 1030, 2), (80, 1024, 130, 3), (91, 1, 514, 2), (200, 1024, 2052, 2),
-                                      (365, 300, 258, 2), (1000, 1024, 600, 2)], ids=str)
-def test_detect_many_classes_equals_the_three_call_path(cuda, NC, K, P, B):
+def _tied_at_kth(conf, K, thr):
+    """(candidates whose score equals the K-th best, slots left for them) of one image's confidences."""
+    c = conf.reshape(-1)
+    c = np.sort(c[c > thr])[::-1]
+    assert len(c) > K
+    return int((c == c[K - 1]).sum()), K - int((c > c[K - 1]).sum())
+
+
+def _ties_pred(rng, B, P, NC):
+    """Equal class logits, and the objectness logit drawn from 37 levels: an image has at most 37 distinct confidences
+    (obj / NC, as test_topk_exact's "ties"), every row holds NC equal scores, so the flat index decides the top-K."""
+    pred = rng.normal(0, 2, (B, P, NC + 6)).astype(np.float32)
+    pred[..., :2 + NC] = 0.0
+    pred[..., 1] = np.linspace(-1.0, 3.0, 37, dtype=np.float32)[rng.integers(0, 37, (B, P))]
+    return pred
+
+
+# P = 130 / 258 do not fill a workgroup; P = 1030 / 514 / 258 with odd NC give P * (NC + 6) % 4 != 0 (rows 4-byte aligned).
+# The "ties" cases have N = P * NC = 2 mod 4 as well (the three-call path's scalar-load passes) and a K-th score shared by more
+# candidates than there are slots left, so the radix refine behind those passes has to run down to the index digits.
+_RANDOM_CASES = [(77, 300, 1030, 2), (80, 1024, 130, 3), (91, 1, 514, 2), (200, 1024, 2052, 2), (365, 300, 258, 2),
+                 (1000, 1024, 600, 2)]
+_TIES_CASES = [(91, 300, 514, 2), (77, 300, 1030, 2)]
+
+
+@pytest.mark.parametrize("NC,K,P,B,ties",
+                         [pytest.param(*c, False, id="-".join(map(str, c))) for c in _RANDOM_CASES]
+                         + [pytest.param(*c, True, id="-".join(map(str, c)) + "-ties") for c in _TIES_CASES])
+def test_detect_many_classes_equals_the_three_call_path(cuda, NC, K, P, B, ties):
     from object_detector_amd.postprocess import Postprocessor
     rng = np.random.default_rng(NC * 1000 + K)
     priors = _priors(P, rng)
     max_det = min(50, K)
     pp = Postprocessor(B, P, NC, priors, device=cuda, topk=K, max_det=max_det)
     assert pp.fused
-    pred = rng.normal(0, 2, (B, P, NC + 6)).astype(np.float32)
-    for thr in (0.0, 0.05):
+    if ties:
+        pred, thrs = _ties_pred(rng, B, P, NC), (0.0, 0.005)  # scores are obj / NC: 0.0030 .. 0.0124
+        assert (P * NC) % 4 == 2
+        host_conf, _ = opp.head_postprocess(pred, priors, num_classes=NC)
+        for thr in thrs:
+            for b in range(B):  # from the inputs alone: the refine loop must run
+                tied, slots = _tied_at_kth(host_conf[b], K, thr)
+                assert tied > slots > 0, (thr, b, tied, slots)
+    else:
+        pred, thrs = rng.normal(0, 2, (B, P, NC + 6)).astype(np.float32), (0.0, 0.05)
+    for thr in thrs:
         conf, boxes, _ = _fused_vs_unfused(cuda, pp, pred, thr, K, max_det)
     rconf, rboxes = opp.head_postprocess(pred, priors, num_classes=NC)
     assert (boxes == rboxes).all()  # bit-exact decode
     np.testing.assert_allclose(conf, rconf, rtol=2e-6, atol=1e-7)
 
 
-@pytest.mark.parametrize("mode", ["all_equal", "few", "none"])
-def test_detect_many_classes_degenerate(cuda, mode):
+# the last case: all scores equal with N = P * NC = 2 mod 4 (the scalar-load passes of the three-call path)
+@pytest.mark.parametrize("mode,NC,P", [pytest.param("all_equal", 200, 1030, id="all_equal"), pytest.param("few", 200, 1030, id="few"),
+                                       pytest.param("none", 200, 1030, id="none"),
+                                       pytest.param("all_equal", 91, 514, id="all_equal-91-514")])
+def test_detect_many_classes_degenerate(cuda, mode, NC, P):
     from object_detector_amd.postprocess import Postprocessor
-    NC, P, B, K = 200, 1030, 2, 1024
+    B, K = 2, 1024
     rng = np.random.default_rng(5)
     priors = _priors(P, rng)
     pp = Postprocessor(B, P, NC, priors, device=cuda, topk=K, max_det=200)
     if mode == "all_equal":  # every one of the P * NC scores is the same: the exact top-K is the K lowest flat indices
         pred = np.zeros((B, P, NC + 6), np.float32)
         thr = 0.0
+        assert P * NC > K  # more candidates tied at the K-th score than slots: the refine loop must run
     else:  # objectness ~0 everywhere but on three priors; "none": a threshold no score reaches
         pred = rng.normal(0, 2, (B, P, NC + 6)).astype(np.float32)
         pred[:, :, 0], pred[:, :, 1] = 12.0, -12.0
