@@ -333,7 +333,8 @@ int od_loss_fwd_bwd(od_ctx* ctx, const float* pred, const float* y, float* grad,
  * 84-90).  Activations / gradients f16 NHWC (gradients loss-scaled), statistics and parameters f32.
  *   backward-data  = od_conv2d_fwd on dZ with the w_bwd pack of od_pack_weights (stride 1), or with
  *                    od_conv_desc.transposed = 1 (stride 2); the epilogue's residual input accumulates gradients
- *   backward-weight= od_conv2d_bwd_weight: dw f32 [Cout_pad][Kpad] += dZ^T . shifted(X)   (atomic f32 adds; zero it first)
+ *   backward-weight= od_conv2d_bwd_weight: dw f32 [Cout][k*k*Cin] (dense, the layout of the f32 master weights)
+ *                    += dZ^T . shifted(X)   (atomic f32 adds; zero it first)
  * ---------------------------------------------------------------------------------------------- */
 /* backward-data as ONE call (SURVEY.md §8b names it as an export): dx[B, Ho*stride, Wo*stride, Cin] f16
  * (= dx_accumulate + ..., when dx_accumulate != NULL; it may alias dx) from dz [B,Ho,Wo,Cout] f16 and the w_bwd pack of
@@ -395,6 +396,13 @@ typedef struct od_wgrad_red {
   int32_t pad_;
 } od_wgrad_red;
 int od_conv2d_bwd_weight_splits(od_ctx* ctx, int B, int H, int W, int Cin, int Cout, int ksize, int stride);
+/* The kernel a layer's weight gradient runs on, decided by the same plan that the launch and the split count come from:
+ * "od_conv_wgrad" (128 x 128 tile), "od_conv_wgrad_w8" (256 x 256), "od_conv_wgrad_thin<1>" / "od_conv_wgrad_thin<2>"
+ * (32 -> 64 channels, 3x3, stride 1 / 2; slab form only).  slabs != 0: od_conv2d_bwd_weight_slabs, 0: the atomic-add
+ * od_conv2d_bwd_weight.  NULL for arguments the launch would reject.  The training-side counterpart of
+ * od_plan_op_kernel_name; the string is static. */
+const char* od_conv2d_bwd_weight_kernel_name(od_ctx* ctx, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
+                                             int slabs);
 int od_conv2d_bwd_weight_slabs(od_ctx* ctx, const void* x, const void* dz, float* slabs, int B, int H, int W, int Cin,
                                int Cout, int ksize, int stride, void* stream);
 int od_wgrad_reduce_multi(od_ctx* ctx, const od_wgrad_red* table, int nlayers, float* grads, void* stream);

@@ -123,6 +123,20 @@ int od_bottleneck_prepare(od_ctx* ctx, const od_bneck_desc* d, od_launches* L);
 int od_stem_prepare(od_ctx* ctx, const od_stem_desc* d, od_launches* L);
 int od_wide_prepare(od_ctx* ctx, const od_wide_desc* d, od_launches* L);
 
-// weight-gradient launcher (conv_wgrad.hip): per-split f32 slabs [split][Cout][k*k*Cin]; *nsplit receives the split count
-int od_wgrad_slabs_impl(od_ctx* ctx, const void* x, const void* dz, float* slabs, int B, int H, int W, int Cin, int Cout,
-                        int ksize, int stride, void* stream, int* nsplit);
+// weight gradient (conv_wgrad.hip): wgrad_plan validates a layer and decides, once, which kernel it takes and how its pixels
+// are split; the launchers fill the kernel's parameters from the plan and decide nothing.
+struct WgradPlan {
+  enum Kind { T128, W8, THIN } kind;  // od_conv_wgrad / od_conv_wgrad_w8 / od_conv_wgrad_thin<stride>
+  const void* fn;
+  const char* name;
+  int threads;
+  size_t lds;  // dynamic LDS
+  int grid;
+  int split, chunks_per_split;  // slabs written / 32-pixel chunks per workgroup (thin: one slab per workgroup)
+  int rtiles, ctiles;
+  int Ho, Wo, M;
+  int B, H, W, Cin, Cout, ksize, stride;  // the layer it was made for
+};
+int wgrad_plan(od_ctx* ctx, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int slabs, WgradPlan* pl);
+// launches the plan's kernel (a plan made with slabs = 1) into per-split f32 slabs [pl.split][Cout][k*k*Cin]
+int od_wgrad_slabs_impl(od_ctx* ctx, const WgradPlan& pl, const void* x, const void* dz, float* slabs, void* stream);

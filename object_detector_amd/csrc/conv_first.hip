@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "conv_common.h"
+#include "wgrad_common.h"
 
 namespace {
 
@@ -165,8 +166,6 @@ __global__ __launch_bounds__(256) void od_conv_first_wgrad_finish(const float* _
 // workgroup are added in order through LDS, one [32][32] slab per workgroup, od_conv_first_wgrad_finish2 adds the slabs in
 // a fixed order.  224 -> 95 us at 32 x 320^2 (the widening pass + the generic kernel at 14 % tile use + finish before; the
 // byte loads, 16 vector-memory instructions per chunk and wave, are what bounds it now).
-typedef __fp16 h4v __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
 __global__ __launch_bounds__(256) void od_conv_first_wgrad_stream(const uint8_t* __restrict__ x, const f16* __restrict__ dz,
                                                                   float* __restrict__ slabs, int H, int W,
                                                                   int chunks_per_row, int nchunks) {
@@ -232,17 +231,8 @@ __global__ __launch_bounds__(256) void od_conv_first_wgrad_stream(const uint8_t*
     f16x8 af[2];
     const char* cb = mybuf + buf * 2048;
 #pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      h4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4v*)(cb + (8 * lq + tq) * 64 + f * 32 + tp * 8));
-      h4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4v*)(cb + (8 * lq + 4 + tq) * 64 + f * 32 + tp * 8));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        af[f][e] = (f16)lo[e];
-        af[f][4 + e] = (f16)hi[e];
-      }
-    }
+    for (int f = 0; f < 2; ++f)
+      af[f] = od_tr_frag(cb + (8 * lq + tq) * 64 + f * 32 + tp * 8, cb + (8 * lq + 4 + tq) * 64 + f * 32 + tp * 8);
     const int next = chunk + nw;
     if (next < nchunks) issue(next, buf ^ 1);  // (the transposed reads above are complete before their values are used below;
                                                //  the DMA targets the OTHER buffer)
@@ -295,25 +285,34 @@ static int first_wgrad_stream_wgs(const od_ctx* ctx, int B, int H, int W) {
   return (int)wgs;
 }
 
+// widened-copy path: the f16 x 8-channel image, then the plan's slabs [split][32][72]
+static size_t first_wgrad_copy_bytes(const WgradPlan& pl) {
+  return (size_t)pl.B * pl.H * pl.W * 16 + (size_t)pl.split * 32 * 72 * sizeof(float);
+}
+
 extern "C" size_t od_conv_first_bwd_weight_workspace_bytes(od_ctx* ctx, int B, int H, int W) {
   if (!ctx || B <= 0 || H <= 0 || W <= 0) return 0;
   if (first_wgrad_use_stream(B, H, W)) return (size_t)first_wgrad_stream_wgs(ctx, B, H, W) * 1024 * sizeof(float);
-  const size_t x8 = (size_t)B * H * W * 16;
-  const int split = od_conv2d_bwd_weight_splits(ctx, B, H, W, 8, 32, 3, 1);
-  return x8 + (size_t)split * 32 * 72 * sizeof(float);
+  WgradPlan pl;
+  return wgrad_plan(ctx, B, H, W, 8, 32, 3, 1, 1, &pl) == OD_OK ? first_wgrad_copy_bytes(pl) : 0;
 }
 
 extern "C" int od_conv_first_bwd_weight(od_ctx* ctx, const uint8_t* x, const void* dz, float* dw, int B, int H, int W,
                                         int Cout, float in_scale, void* workspace, size_t workspace_bytes, void* stream) {
   OD_REQUIRE(ctx && x && dz && dw && workspace && Cout == 32 && B > 0 && H > 0 && W > 0,
              "od_conv_first_bwd_weight: bad argument (Cout must be 32)");
-  if (workspace_bytes < od_conv_first_bwd_weight_workspace_bytes(ctx, B, H, W)) {
+  const bool stream_form = first_wgrad_use_stream(B, H, W);
+  WgradPlan pl;  // widened-copy path: the ONE plan that sizes the slabs and is launched
+  if (!stream_form)
+    if (int rc = wgrad_plan(ctx, B, H, W, 8, 32, 3, 1, 1, &pl)) return rc;
+  const size_t need = stream_form ? od_conv_first_bwd_weight_workspace_bytes(ctx, B, H, W) : first_wgrad_copy_bytes(pl);
+  if (workspace_bytes < need) {
     od_set_error("od_conv_first_bwd_weight: workspace too small");
     return OD_ERR_WORKSPACE;
   }
   OD_REQUIRE(((uintptr_t)workspace & 15) == 0, "od_conv_first_bwd_weight: workspace must be 16-byte aligned");
   const long long npix = (long long)B * H * W;
-  if (first_wgrad_use_stream(B, H, W)) {
+  if (stream_form) {
     const int wgs = first_wgrad_stream_wgs(ctx, B, H, W);
     hipLaunchKernelGGL(od_conv_first_wgrad_stream, dim3(wgs), dim3(256), 0, (hipStream_t)stream, x, (const f16*)dz,
                        (float*)workspace, H, W, W / 32, (int)(npix / 32));
@@ -329,9 +328,8 @@ extern "C" int od_conv_first_bwd_weight(od_ctx* ctx, const uint8_t* x, const voi
   if (blocks > 256 * 16) blocks = 256 * 16;
   hipLaunchKernelGGL(od_u8_to_f16x8, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, x8, npix);
   OD_CHECK_LAUNCH();
-  int nsplit = 0;
-  if (int rc = od_wgrad_slabs_impl(ctx, x8, dz, slabs, B, H, W, 8, 32, 3, 1, stream, &nsplit)) return rc;
-  hipLaunchKernelGGL(od_conv_first_wgrad_finish, dim3(32 * 27 / 4), dim3(256), 0, (hipStream_t)stream, slabs, nsplit, dw,
+  if (int rc = od_wgrad_slabs_impl(ctx, pl, x8, dz, slabs, stream)) return rc;
+  hipLaunchKernelGGL(od_conv_first_wgrad_finish, dim3(32 * 27 / 4), dim3(256), 0, (hipStream_t)stream, slabs, pl.split, dw,
                      in_scale);
   OD_CHECK_LAUNCH();
   return OD_OK;

@@ -13,10 +13,9 @@
 #include <stdlib.h>
 
 #include "conv_common.h"
+#include "wgrad_common.h"
 
 namespace {
-
-typedef __fp16 h4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
 struct WgradKP {
   const f16* x;    // [B,H,W,Cin]
@@ -31,14 +30,8 @@ struct WgradKP {
 
 constexpr int KC = 32;          // pixels per K chunk (one MFMA k step)
 constexpr int TILE = 128;       // out tile edge
-constexpr int ROWB = 256;       // LDS row bytes (128 f16)
-constexpr int OPER_BYTES = KC * ROWB;  // 8 KiB per operand per stage
-#ifndef OD_WG_NSTAGE
-#define OD_WG_NSTAGE 3
-#endif
-constexpr int NSTAGE = OD_WG_NSTAGE;       // LDS ring: chunk c+3 streams in while chunk c is multiplied (64 KiB, 2 workgroups per CU)
-
-__device__ __forceinline__ int swz_key(int r) { return ((r & 3) | (((r >> 3) & 1) << 2)) << 1; }
+constexpr int OPER_BYTES = KC * OD_WG_ROWB;  // 8 KiB per operand per stage ([32 pixels][128 channels], wgrad_common.h)
+constexpr int NSTAGE = 3;       // LDS ring: chunk c+2 streams in while chunk c is multiplied (48 KiB, 2 workgroups per CU)
 
 __global__ __launch_bounds__(256, 2) void od_conv_wgrad(WgradKP p) {
   __shared__ __attribute__((aligned(16))) char smem[NSTAGE * 2 * OPER_BYTES];  // [stage][D | X]
@@ -61,32 +54,17 @@ __global__ __launch_bounds__(256, 2) void od_conv_wgrad(WgradKP p) {
   const int prow[2] = {4 * wave + (lane >> 4), 4 * (wave + 4) + (lane >> 4)};
   int lchunk[2];
 #pragma unroll
-  for (int h = 0; h < 2; ++h) lchunk[h] = (lane & 15) ^ swz_key(prow[h]);
+  for (int h = 0; h < 2; ++h) lchunk[h] = (lane & 15) ^ od_wg_swz_key(prow[h]);
   // X operand: this lane's columns (same for both rows when the keys agree; computed per row)
-  int xtap_dy[2], xtap_dx[2], xci[2];
-  bool xcol_ok[2], dcol_ok[2];
+  od_wg_col xcol[2];
+  bool dcol_ok[2];
+  // pixel of this lane's two tile rows in the NEXT chunk to be staged
+  od_wg_pixel_cursor px[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int j = n0 + lchunk[h] * 8;
-    const int tap = j / p.Cin;
-    xci[h] = j - tap * p.Cin;
-    xtap_dy[h] = tap / p.ks;
-    xtap_dx[h] = tap - xtap_dy[h] * p.ks;
-    xcol_ok[h] = j < p.Ktot;
+    xcol[h] = od_wg_col_decode(n0 + lchunk[h] * 8, p.Cin, p.ks, p.Ktot);
     dcol_ok[h] = (co0 + lchunk[h] * 8) < p.Cout;
-  }
-
-  // pixel coordinates of this lane's two tile rows for the NEXT chunk to be staged, advanced by KC per chunk (no division
-  // in the loop: Wo >= 10 here, so a 32-pixel step wraps at most a few rows)
-  int sm[2], sb[2], sho[2], swo[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    sm[h] = chunk0 * KC + prow[h];
-    const unsigned b = (unsigned)sm[h] / (unsigned)p.HoWo;
-    const unsigned pix = (unsigned)sm[h] - b * (unsigned)p.HoWo;
-    sb[h] = (int)b;
-    sho[h] = (int)(pix / (unsigned)p.Wo);
-    swo[h] = (int)(pix - (unsigned)sho[h] * (unsigned)p.Wo);
+    px[h].init(chunk0 * KC + prow[h], p.HoWo, p.Wo);
   }
   auto stage = [&](int buf) {  // stages are issued strictly in chunk order
     char* dbuf = smem + buf * 2 * OPER_BYTES;
@@ -94,23 +72,14 @@ __global__ __launch_bounds__(256, 2) void od_conv_wgrad(WgradKP p) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int q = wave + 4 * h;
-      const int m = sm[h];
-      const bool mok = m < p.M;
-      const f16* dsrc = (mok && dcol_ok[h]) ? p.dz + ((long long)m * p.Cout + co0 + lchunk[h] * 8) : p.zero;
+      const bool mok = px[h].m < p.M;
+      const f16* dsrc = (mok && dcol_ok[h]) ? p.dz + ((long long)px[h].m * p.Cout + co0 + lchunk[h] * 8) : p.zero;
       glds16(dsrc, dbuf + q * 1024);
-      const int hi = sho[h] * p.stride + xtap_dy[h] - p.pad, wi = swo[h] * p.stride + xtap_dx[h] - p.pad;
-      const bool xok = mok && xcol_ok[h] && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-      const f16* xsrc = xok ? p.x + ((((long long)sb[h] * p.H + hi) * p.W + wi) * p.Cin + xci[h]) : p.zero;
+      const int hi = px[h].ho * p.stride + xcol[h].dy - p.pad, wi = px[h].wo * p.stride + xcol[h].dx - p.pad;
+      const bool xok = mok && xcol[h].ok && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
+      const f16* xsrc = xok ? p.x + ((((long long)px[h].b * p.H + hi) * p.W + wi) * p.Cin + xcol[h].ci) : p.zero;
       glds16(xsrc, xbuf + q * 1024);
-      sm[h] += KC;
-      swo[h] += KC;
-      while (swo[h] >= p.Wo) {
-        swo[h] -= p.Wo;
-        if (++sho[h] == p.Ho) {
-          sho[h] = 0;
-          ++sb[h];
-        }
-      }
+      px[h].advance(KC, p.Ho, p.Wo);
     }
   };
 
@@ -121,33 +90,16 @@ __global__ __launch_bounds__(256, 2) void od_conv_wgrad(WgradKP p) {
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // transposed-read addressing: lane 4q+p of a 16-lane group supplies row q, 4 columns starting at 4p
-  const int tq = l15 >> 2, tp = l15 & 3;
-  int roff[2];  // byte offset of (row, swizzle) for the two 4-row blocks of this lane's 8 pixels
-  int rkey[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int r = 8 * lq + 4 * h + tq;
-    roff[h] = r * ROWB;
-    rkey[h] = swz_key(r);
-  }
+  od_wg_tile_reader rd;
+  rd.init(lane);
 
-  // ring: chunks are staged NSTAGE-1 ahead; a counted vmcnt retires chunk c and leaves the later ones in flight (4 DMAs per
-  // chunk per wave), one raw s_barrier per chunk (every wave's piece of chunk c landed; chunk c-1's buffer is free)
+  // ring: chunks are staged NSTAGE-1 ahead, 4 DMAs per chunk per wave (od_wg_ring_wait)
 #pragma unroll
   for (int s0 = 0; s0 < NSTAGE - 1; ++s0)
     if (s0 < nch) stage(s0);
   int buf = 0, sbuf = NSTAGE - 1;  // buffer of chunk c / of the next chunk to stage
   for (int c = 0; c < nch; ++c, buf = (buf + 1 == NSTAGE ? 0 : buf + 1)) {
-    // chunks c+1 .. c+NSTAGE-2 may stay in flight
-    if (NSTAGE >= 4 && c + 2 < nch) {
-      wait_vmcnt<8>();
-    } else if (NSTAGE >= 3 && c + 1 < nch) {
-      wait_vmcnt<4>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
+    od_wg_ring_wait<4, NSTAGE>(c, nch);
     if (c + NSTAGE - 1 < nch) {
       stage(sbuf);
       sbuf = sbuf + 1 == NSTAGE ? 0 : sbuf + 1;
@@ -156,31 +108,9 @@ __global__ __launch_bounds__(256, 2) void od_conv_wgrad(WgradKP p) {
     const char* xbuf = dbuf + OPER_BYTES;
     f16x8 af[4], bf[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int u = (wr * 64 + i * 16) / 4 + tp;  // 8-byte unit inside the row (16 channels = 4 units)
-      h4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4*)(dbuf + roff[0] + (((u >> 1) ^ rkey[0]) * 16) + (u & 1) * 8));
-      h4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4*)(dbuf + roff[1] + (((u >> 1) ^ rkey[1]) * 16) + (u & 1) * 8));
+    for (int i = 0; i < 4; ++i) af[i] = rd.frag(dbuf, wr * 64 + i * 16);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        af[i][e] = (f16)lo[e];
-        af[i][4 + e] = (f16)hi[e];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int u = (wc * 64 + j * 16) / 4 + tp;
-      h4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4*)(xbuf + roff[0] + (((u >> 1) ^ rkey[0]) * 16) + (u & 1) * 8));
-      h4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4*)(xbuf + roff[1] + (((u >> 1) ^ rkey[1]) * 16) + (u & 1) * 8));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        bf[j][e] = (f16)lo[e];
-        bf[j][4 + e] = (f16)hi[e];
-      }
-    }
+    for (int j = 0; j < 4; ++j) bf[j] = rd.frag(xbuf, wc * 64 + j * 16);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -239,51 +169,32 @@ __global__ __launch_bounds__(512, 2) void od_conv_wgrad_w8(WgradKP p) {
 
   // ---- DMA mapping: wave w fills rows 4w .. 4w+3 of each of the four half-tiles (one 1-KiB instruction each)
   const int prow = 4 * wave + (lane >> 4);
-  const int lchunk = (lane & 15) ^ swz_key(prow);
-  int xtap_dy[2], xtap_dx[2], xci[2];
-  bool xcol_ok[2], dcol_ok[2];
+  const int lchunk = (lane & 15) ^ od_wg_swz_key(prow);
+  od_wg_col xcol[2];
+  bool dcol_ok[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
-    const int j = n0 + h * 128 + lchunk * 8;
-    const int tap = j / p.Cin;
-    xci[h] = j - tap * p.Cin;
-    xtap_dy[h] = tap / p.ks;
-    xtap_dx[h] = tap - xtap_dy[h] * p.ks;
-    xcol_ok[h] = j < p.Ktot;
+    xcol[h] = od_wg_col_decode(n0 + h * 128 + lchunk * 8, p.Cin, p.ks, p.Ktot);
     dcol_ok[h] = (co0 + h * 128 + lchunk * 8) < p.Cout;
   }
-  int sm = chunk0 * KC + prow, sb, sho, swo;
-  {
-    const unsigned b = (unsigned)sm / (unsigned)p.HoWo;
-    const unsigned pix = (unsigned)sm - b * (unsigned)p.HoWo;
-    sb = (int)b;
-    sho = (int)(pix / (unsigned)p.Wo);
-    swo = (int)(pix - (unsigned)sho * (unsigned)p.Wo);
-  }
+  od_wg_pixel_cursor px;  // this lane's tile row in the NEXT chunk to be staged
+  px.init(chunk0 * KC + prow, p.HoWo, p.Wo);
   auto stage = [&](int buf) {  // stages are issued strictly in chunk order
     char* base = smem8 + buf * W8_STAGE_BYTES + wave * 1024;
-    const bool mok = sm < p.M;
+    const bool mok = px.m < p.M;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const f16* dsrc = (mok && dcol_ok[h]) ? p.dz + ((long long)sm * p.Cout + co0 + h * 128 + lchunk * 8) : p.zero;
+      const f16* dsrc = (mok && dcol_ok[h]) ? p.dz + ((long long)px.m * p.Cout + co0 + h * 128 + lchunk * 8) : p.zero;
       glds16(dsrc, base + h * OPER_BYTES);
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      const int hi = sho * p.stride + xtap_dy[h] - p.pad, wi = swo * p.stride + xtap_dx[h] - p.pad;
-      const bool xok = mok && xcol_ok[h] && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-      const f16* xsrc = xok ? p.x + ((((long long)sb * p.H + hi) * p.W + wi) * p.Cin + xci[h]) : p.zero;
+      const int hi = px.ho * p.stride + xcol[h].dy - p.pad, wi = px.wo * p.stride + xcol[h].dx - p.pad;
+      const bool xok = mok && xcol[h].ok && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
+      const f16* xsrc = xok ? p.x + ((((long long)px.b * p.H + hi) * p.W + wi) * p.Cin + xcol[h].ci) : p.zero;
       glds16(xsrc, base + (2 + h) * OPER_BYTES);
     }
-    sm += KC;
-    swo += KC;
-    while (swo >= p.Wo) {
-      swo -= p.Wo;
-      if (++sho == p.Ho) {
-        sho = 0;
-        ++sb;
-      }
-    }
+    px.advance(KC, p.Ho, p.Wo);
   };
 
   // ---- MFMA side ---------------------------------------------------------------------------------------------------
@@ -294,43 +205,15 @@ __global__ __launch_bounds__(512, 2) void od_conv_wgrad_w8(WgradKP p) {
   for (int j = 0; j < 8; ++j)
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int tq = l15 >> 2, tp = l15 & 3;
-  int roff[2], rkey[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int r = 8 * lq + 4 * h + tq;
-    roff[h] = r * ROWB;
-    rkey[h] = swz_key(r);
-  }
-  auto frag = [&](const char* tile, int ch) -> f16x8 {  // 16 channels starting at `ch` of a half-tile, this lane's 8 pixels
-    const int u = ch / 4 + tp;
-    h4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-        (__attribute__((address_space(3))) h4*)(tile + roff[0] + (((u >> 1) ^ rkey[0]) * 16) + (u & 1) * 8));
-    h4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-        (__attribute__((address_space(3))) h4*)(tile + roff[1] + (((u >> 1) ^ rkey[1]) * 16) + (u & 1) * 8));
-    f16x8 f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      f[e] = (f16)lo[e];
-      f[4 + e] = (f16)hi[e];
-    }
-    return f;
-  };
+  od_wg_tile_reader rd;
+  rd.init(lane);
 
 #pragma unroll
   for (int s0 = 0; s0 < W8_NSTAGE - 1; ++s0)
     if (s0 < nch) stage(s0);
   int buf = 0, sbuf = W8_NSTAGE - 1;
   for (int c = 0; c < nch; ++c, buf = (buf + 1 == W8_NSTAGE ? 0 : buf + 1)) {
-    // 4 DMAs per chunk per wave; chunks c+1, c+2 may stay in flight
-    if (c + 2 < nch) {
-      wait_vmcnt<8>();
-    } else if (c + 1 < nch) {
-      wait_vmcnt<4>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();  // every wave's rows of chunk c have landed; chunk c-1's buffer is free
+    od_wg_ring_wait<4, W8_NSTAGE>(c, nch);  // 4 DMAs per chunk per wave
     if (c + W8_NSTAGE - 1 < nch) {
       stage(sbuf);
       sbuf = sbuf + 1 == W8_NSTAGE ? 0 : sbuf + 1;
@@ -340,10 +223,10 @@ __global__ __launch_bounds__(512, 2) void od_conv_wgrad_w8(WgradKP p) {
     const char* xtile = st + (2 + wc) * OPER_BYTES;
     f16x8 df[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) df[i] = frag(dtile, d_ch0 + i * 16);
+    for (int i = 0; i < 4; ++i) df[i] = rd.frag(dtile, d_ch0 + i * 16);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const f16x8 xf = frag(xtile, j * 16);
+      const f16x8 xf = rd.frag(xtile, j * 16);
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf, df[i], acc[j][i], 0, 0, 0);
     }
@@ -434,13 +317,7 @@ __global__ __launch_bounds__(256, 2) void od_conv_wgrad_thin(WgradKP p, int chun
   if (nmine > 0) stage(first, 0);
   if (nmine > 1) stage(first + step, 1);
   for (int it = 0; it < nmine; ++it) {
-    // chunk `it` landed: at most the ND pieces of chunk it+1 stay in flight
-    if (it + 1 < nmine) {
-      wait_vmcnt<Cf::ND>();
-    } else {
-      wait_vmcnt<0>();
-    }
-    __builtin_amdgcn_s_barrier();
+    od_wg_ring_wait<Cf::ND, 3>(it, nmine);  // chunk `it` landed: at most the ND pieces of chunk it+1 stay in flight
     if (it + 2 < nmine) stage(first + (it + 2) * step, (it + 2) % 3);
     const char* db = tsm + (it % 3) * Cf::BUF;  // dZ: [32 pixels][64 channels], 128-B rows
     const char* xb = db + 4096;                 // X: 3 segments of XSLOTS pixels, 64-B rows
@@ -448,15 +325,7 @@ __global__ __launch_bounds__(256, 2) void od_conv_wgrad_thin(WgradKP p, int chun
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int unit = (2 * wr + i) * 4 + tp;  // 8-byte unit inside the 128-B row: 16 channels = 4 units
-      h4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4*)(db + (8 * lq + tq) * 128 + unit * 8));
-      h4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4*)(db + (8 * lq + 4 + tq) * 128 + unit * 8));
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        af[i][e] = (f16)lo[e];
-        af[i][4 + e] = (f16)hi[e];
-      }
+      af[i] = od_tr_frag(db + (8 * lq + tq) * 128 + unit * 8, db + (8 * lq + 4 + tq) * 128 + unit * 8);
     }
 #pragma unroll
     for (int c = 0; c < 9; ++c) {
@@ -464,16 +333,8 @@ __global__ __launch_bounds__(256, 2) void od_conv_wgrad_thin(WgradKP p, int chun
       const int tap = cf >> 1, half = cf & 1;
       const int dy = tap / 3, dx = tap - dy * 3;
       const char* seg = xb + dy * (Cf::XSLOTS * 64);
-      h4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4*)(seg + (S * (8 * lq + tq) + dx) * 64 + (half * 4 + tp) * 8));
-      h4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) h4*)(seg + (S * (8 * lq + 4 + tq) + dx) * 64 + (half * 4 + tp) * 8));
-      f16x8 bf;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        bf[e] = (f16)lo[e];
-        bf[4 + e] = (f16)hi[e];
-      }
+      const f16x8 bf = od_tr_frag(seg + (S * (8 * lq + tq) + dx) * 64 + (half * 4 + tp) * 8,
+                                  seg + (S * (8 * lq + 4 + tq) + dx) * 64 + (half * 4 + tp) * 8);
 #pragma unroll
       for (int i = 0; i < 2; ++i) acc[i][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], bf, acc[i][c], 0, 0, 0);
     }
@@ -499,14 +360,14 @@ static int wgrad_w8_split(int cus, int nchunks, int Cout, int Ktot, int* chunks_
   if (split < 1) split = 1;
   if (split > nchunks / 12) split = nchunks / 12 > 0 ? nchunks / 12 : 1;
   const int cps = od_ceil_div(nchunks, split);
-  if (chunks_per_split) *chunks_per_split = cps;
+  *chunks_per_split = cps;
   return od_ceil_div(nchunks, cps);
 }
 
 // which kernel a layer takes: the 256-wide tile when it covers the [Cout][Ktot] matrix without much padding AND its one
 // round of workgroups fills most of the chip (measured per shape, profiles/r02/wgrad_bench.txt: the 1x1 layers and the
 // 10x10 maps with few tiles run 62-72 workgroups of it and are faster on the 128-wide kernel's 480+)
-static bool wgrad_use_w8(int cus, int M, int Cout, int Ktot) {
+static bool wgrad_use_w8(int cus, int nchunks, int Cout, int Ktot, int* split, int* chunks_per_split) {
   constexpr int min_wgs = 160;
   // pixel chunks per workgroup below which the 128 x 128 kernel is taken.  Standalone the 256-wide kernel wins from ~24
   // chunks; INSIDE the two-stream step it holds a whole CU (128 KiB of LDS, 256 VGPRs x 8 waves) while the other stream's
@@ -516,8 +377,11 @@ static bool wgrad_use_w8(int cus, int M, int Cout, int Ktot) {
   const long long tiles = (long long)od_ceil_div(Cout, W8_TILE) * od_ceil_div(Ktot, W8_TILE);
   const double eff = (double)Cout * Ktot / (double)(tiles * W8_TILE * W8_TILE);
   int cps = 0;
-  const int split = wgrad_w8_split(cus, od_ceil_div(M, KC), Cout, Ktot, &cps);
-  return eff >= 0.74 && tiles * split >= min_wgs && cps >= min_cps;
+  const int sp = wgrad_w8_split(cus, nchunks, Cout, Ktot, &cps);
+  if (!(eff >= 0.74 && tiles * sp >= min_wgs && cps >= min_cps)) return false;
+  *split = sp;
+  *chunks_per_split = cps;
+  return true;
 }
 
 // the thin kernel's shapes (slab output only): 3x3, 32 -> 64 channels, output rows that are whole 32-pixel chunks
@@ -529,10 +393,8 @@ static int wgrad_thin_grid(const od_ctx* ctx, long long nchunks) {
   return (int)(g < nchunks ? g : nchunks);
 }
 
-static int wgrad_split(const od_ctx* ctx, int M, int Cout, int Ktot, int* chunks_per_split) {
-  const int nchunks = od_ceil_div(M, KC);
-  const int cus = ctx->num_cu;
-  if (wgrad_use_w8(cus, M, Cout, Ktot)) return wgrad_w8_split(cus, nchunks, Cout, Ktot, chunks_per_split);
+// pixel split of the 128 x 128 kernel
+static int wgrad_128_split(int cus, int nchunks, int Cout, int Ktot, int* chunks_per_split) {
   const int rtiles = od_ceil_div(Cout, TILE), ctiles = od_ceil_div(Ktot, TILE);
   // workgroups per CU the pixel split aims at (every workgroup emits a full 64 KiB f32 tile, so more splits = more
   // partial-sum traffic); measured on the batch-32 step: 4 -> 18.2 ms, 2 -> 17.5 ms, 1 -> 18.7 ms
@@ -541,92 +403,113 @@ static int wgrad_split(const od_ctx* ctx, int M, int Cout, int Ktot, int* chunks
   if (split > nchunks) split = nchunks;
   if (split < 1) split = 1;
   const int cps = od_ceil_div(nchunks, split);
-  if (chunks_per_split) *chunks_per_split = cps;
+  *chunks_per_split = cps;
   return od_ceil_div(nchunks, cps);
 }
 
-static int wgrad_impl(od_ctx* ctx, const void* x, const void* dz, float* dw, float* slabs, int B, int H, int W, int Cin,
-                      int Cout, int ksize, int stride, void* stream, int* nsplit) {
-  OD_REQUIRE(ctx && x && dz && (dw || slabs), "od_conv2d_bwd_weight: null argument");
+// THE decision: validates the layer, picks the kernel and the pixel split.  Every entry point below and the first layer's
+// widened-copy path (conv_first.hip) size their slabs from the plan they launch.  slabs = 0: the atomic-add form
+// (od_conv2d_bwd_weight), which the thin kernel does not have.
+int wgrad_plan(od_ctx* ctx, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int slabs, WgradPlan* pl) {
+  OD_REQUIRE(ctx, "od_conv2d_bwd_weight: null argument");
   OD_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "od_conv2d_bwd_weight: bad ksize/stride");
   OD_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 8 == 0,
              "od_conv2d_bwd_weight: Cin/Cout must be multiples of 8");
+  const int pad = ksize / 2, Ktot = ksize * ksize * Cin;
+  WgradPlan q = {};
+  q.B = B, q.H = H, q.W = W, q.Cin = Cin, q.Cout = Cout, q.ksize = ksize, q.stride = stride;
+  q.Ho = (H + 2 * pad - ksize) / stride + 1;
+  q.Wo = (W + 2 * pad - ksize) / stride + 1;
+  const long long M64 = (long long)B * q.Ho * q.Wo;
+  OD_REQUIRE(M64 * Cout < (1LL << 31) && (long long)B * H * W * Cin < (1LL << 31), "od_conv2d_bwd_weight: too large");
+  q.M = (int)M64;
+  const int cus = ctx->num_cu, nchunks = od_ceil_div(q.M, KC);
+  if (slabs && wgrad_thin_ok(Cin, Cout, ksize, stride, H, W, q.Ho, q.Wo)) {
+    q.kind = WgradPlan::THIN;
+    q.fn = stride == 1 ? (const void*)&od_conv_wgrad_thin<1> : (const void*)&od_conv_wgrad_thin<2>;
+    q.name = stride == 1 ? "od_conv_wgrad_thin<1>" : "od_conv_wgrad_thin<2>";
+    q.threads = 256;
+    q.lds = stride == 1 ? (size_t)ThinCfg<1>::LDS : (size_t)ThinCfg<2>::LDS;
+    q.rtiles = q.ctiles = 1;
+    q.grid = q.split = wgrad_thin_grid(ctx, q.M / 32);  // one slab per workgroup
+  } else if (wgrad_use_w8(cus, nchunks, Cout, Ktot, &q.split, &q.chunks_per_split)) {
+    q.kind = WgradPlan::W8;
+    q.fn = (const void*)&od_conv_wgrad_w8;
+    q.name = "od_conv_wgrad_w8";
+    q.threads = 512;
+    q.lds = W8_LDS;
+    q.rtiles = od_ceil_div(Cout, W8_TILE);
+    q.ctiles = od_ceil_div(Ktot, W8_TILE);
+    q.grid = q.rtiles * q.ctiles * q.split;
+  } else {
+    q.kind = WgradPlan::T128;
+    q.fn = (const void*)&od_conv_wgrad;
+    q.name = "od_conv_wgrad";
+    q.threads = 256;
+    q.lds = 0;  // static
+    q.split = wgrad_128_split(cus, nchunks, Cout, Ktot, &q.chunks_per_split);
+    q.rtiles = od_ceil_div(Cout, TILE);
+    q.ctiles = od_ceil_div(Ktot, TILE);
+    q.grid = q.rtiles * q.ctiles * q.split;
+  }
+  *pl = q;
+  return OD_OK;
+}
+
+// fills the kernel's parameters from the plan and launches it; decides nothing
+static int wgrad_launch(od_ctx* ctx, const WgradPlan& pl, const void* x, const void* dz, float* dw, float* slabs,
+                        void* stream) {
   WgradKP p;
   p.x = (const f16*)x;
   p.dz = (const f16*)dz;
   p.dw = dw;
   p.slabs = slabs;
   p.zero = (const f16*)ctx->zero_page;
-  p.H = H;
-  p.W = W;
-  p.Cin = Cin;
-  p.ks = ksize;
-  p.stride = stride;
-  p.pad = ksize / 2;
-  p.Ho = (H + 2 * p.pad - ksize) / stride + 1;
-  p.Wo = (W + 2 * p.pad - ksize) / stride + 1;
-  p.Cout = Cout;
-  p.Ktot = ksize * ksize * Cin;
-  p.Kstride = p.Ktot;
-  const long long M64 = (long long)B * p.Ho * p.Wo;
-  OD_REQUIRE(M64 * Cout < (1LL << 31) && (long long)B * H * W * Cin < (1LL << 31), "od_conv2d_bwd_weight: too large");
-  p.M = (int)M64;
-  p.HoWo = p.Ho * p.Wo;
-  if (slabs && wgrad_thin_ok(Cin, Cout, ksize, stride, H, W, p.Ho, p.Wo)) {
-    const int nchunks = p.M / 32;
-    const int grid = wgrad_thin_grid(ctx, nchunks);
-    p.split = grid;
-    if (nsplit) *nsplit = grid;
-    const void* fn = stride == 1 ? (const void*)&od_conv_wgrad_thin<1> : (const void*)&od_conv_wgrad_thin<2>;
-    const size_t lds = stride == 1 ? (size_t)ThinCfg<1>::LDS : (size_t)ThinCfg<2>::LDS;
-    if (int rc = od_ensure_lds(ctx, fn, lds)) return rc;
-    int cpr = p.Wo / 32, nch = nchunks;
-    void* args[] = {&p, &cpr, &nch};
-    OD_CHECK_HIP(hipLaunchKernel(fn, dim3(grid), dim3(256), args, lds, (hipStream_t)stream));
-    return OD_OK;
-  }
-  p.split = wgrad_split(ctx, p.M, Cout, p.Ktot, &p.chunks_per_split);
-  if (nsplit) *nsplit = p.split;
-  if (wgrad_use_w8(ctx->num_cu, p.M, Cout, p.Ktot)) {
-    p.rtiles = od_ceil_div(Cout, W8_TILE);
-    p.ctiles = od_ceil_div(p.Ktot, W8_TILE);
-    if (int rc = od_ensure_lds(ctx, (const void*)&od_conv_wgrad_w8, (size_t)W8_LDS)) return rc;
-    hipLaunchKernelGGL(od_conv_wgrad_w8, dim3(p.rtiles * p.ctiles * p.split), dim3(512), W8_LDS, (hipStream_t)stream, p);
-    OD_CHECK_LAUNCH();
-    return OD_OK;
-  }
-  p.rtiles = od_ceil_div(Cout, TILE);
-  p.ctiles = od_ceil_div(p.Ktot, TILE);
-  hipLaunchKernelGGL(od_conv_wgrad, dim3(p.rtiles * p.ctiles * p.split), dim3(256), 0, (hipStream_t)stream, p);
-  OD_CHECK_LAUNCH();
+  p.H = pl.H, p.W = pl.W, p.Cin = pl.Cin, p.Ho = pl.Ho, p.Wo = pl.Wo, p.Cout = pl.Cout;
+  p.ks = pl.ksize, p.stride = pl.stride, p.pad = pl.ksize / 2;
+  p.Ktot = p.Kstride = pl.ksize * pl.ksize * pl.Cin;
+  p.M = pl.M, p.HoWo = pl.Ho * pl.Wo;
+  p.rtiles = pl.rtiles, p.ctiles = pl.ctiles, p.split = pl.split, p.chunks_per_split = pl.chunks_per_split;
+  if (pl.lds)
+    if (int rc = od_ensure_lds(ctx, pl.fn, pl.lds)) return rc;
+  int cpr = pl.Wo / 32, nch = pl.M / 32;  // the thin kernel's two further arguments: 32-pixel chunks per row / in all
+  void* args[] = {&p, &cpr, &nch};        // (the other kernels take p alone)
+  OD_CHECK_HIP(hipLaunchKernel(pl.fn, dim3(pl.grid), dim3(pl.threads), args, pl.lds, (hipStream_t)stream));
   return OD_OK;
 }
 
 // for conv_first.hip (the first layer's weight gradient runs on this kernel over an f16 x 8-channel copy of the image)
-int od_wgrad_slabs_impl(od_ctx* ctx, const void* x, const void* dz, float* slabs, int B, int H, int W, int Cin, int Cout,
-                        int ksize, int stride, void* stream, int* nsplit) {
-  return wgrad_impl(ctx, x, dz, nullptr, slabs, B, H, W, Cin, Cout, ksize, stride, stream, nsplit);
+int od_wgrad_slabs_impl(od_ctx* ctx, const WgradPlan& pl, const void* x, const void* dz, float* slabs, void* stream) {
+  OD_REQUIRE(ctx && x && dz && slabs, "od_conv2d_bwd_weight: null argument");
+  return wgrad_launch(ctx, pl, x, dz, nullptr, slabs, stream);
 }
 
 extern "C" int od_conv2d_bwd_weight(od_ctx* ctx, const void* x, const void* dz, float* dw, int B, int H, int W, int Cin,
                                     int Cout, int ksize, int stride, void* stream) {
-  return wgrad_impl(ctx, x, dz, dw, nullptr, B, H, W, Cin, Cout, ksize, stride, stream, nullptr);
+  OD_REQUIRE(ctx && x && dz && dw, "od_conv2d_bwd_weight: null argument");
+  WgradPlan pl;
+  if (int rc = wgrad_plan(ctx, B, H, W, Cin, Cout, ksize, stride, 0, &pl)) return rc;
+  return wgrad_launch(ctx, pl, x, dz, dw, nullptr, stream);
 }
 
 extern "C" int od_conv2d_bwd_weight_splits(od_ctx* ctx, int B, int H, int W, int Cin, int Cout, int ksize, int stride) {
-  if (!ctx || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (ksize != 1 && ksize != 3) || (stride != 1 && stride != 2))
-    return 0;
-  const int pad = ksize / 2;
-  const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
-  const long long M = (long long)B * Ho * Wo;
-  if (wgrad_thin_ok(Cin, Cout, ksize, stride, H, W, Ho, Wo)) return wgrad_thin_grid(ctx, M / 32);  // slabs of od_conv2d_bwd_weight_slabs
-  return wgrad_split(ctx, (int)M, Cout, ksize * ksize * Cin, nullptr);
+  WgradPlan pl;
+  return wgrad_plan(ctx, B, H, W, Cin, Cout, ksize, stride, 1, &pl) == OD_OK ? pl.split : 0;
+}
+
+extern "C" const char* od_conv2d_bwd_weight_kernel_name(od_ctx* ctx, int B, int H, int W, int Cin, int Cout, int ksize,
+                                                        int stride, int slabs) {
+  WgradPlan pl;
+  return wgrad_plan(ctx, B, H, W, Cin, Cout, ksize, stride, slabs, &pl) == OD_OK ? pl.name : nullptr;
 }
 
 extern "C" int od_conv2d_bwd_weight_slabs(od_ctx* ctx, const void* x, const void* dz, float* slabs, int B, int H, int W,
                                           int Cin, int Cout, int ksize, int stride, void* stream) {
   OD_REQUIRE(slabs, "od_conv2d_bwd_weight_slabs: null slabs");
-  return wgrad_impl(ctx, x, dz, nullptr, slabs, B, H, W, Cin, Cout, ksize, stride, stream, nullptr);
+  OD_REQUIRE(ctx && x && dz, "od_conv2d_bwd_weight: null argument");
+  WgradPlan pl;
+  if (int rc = wgrad_plan(ctx, B, H, W, Cin, Cout, ksize, stride, 1, &pl)) return rc;
+  return wgrad_launch(ctx, pl, x, dz, nullptr, slabs, stream);
 }
 
 namespace {

@@ -52,6 +52,17 @@ FIRST_CASES = params_of(tc.test_conv_first_matches_oracle)
 STEM_CASES = [(s, a) for s in params_of(ts.test_stem_matches_oracle, "shape") for a in params_of(ts.test_stem_matches_oracle, "act")]
 SLAB_CASES = params_of(tk.test_weight_gradient_slab_path_many_splits)
 WGRAD_CASES = list(dict.fromkeys(tk.CONV_CASES + SLAB_CASES))
+# The 8-wave 256 x 256 weight-gradient kernel (od_conv_wgrad_w8) is selected only with >= 60 pixel chunks in each of >= 160
+# workgroups: ~50 GFLOP is the floor on a 256-CU part, so its cases live here (a few ms on the GPU, seconds for the integer
+# reference) and not in the torch-f64 tests.  The smallest shapes the rule admits:
+W8_WGRAD_CASES = [
+    (16, 20, 20, 512, 1024, 3, 1),   # whole tiles, a trainer shape of 16 x 640^2: M = 6400, 3 splits x 72 tiles, 67 chunks each
+    (11, 70, 70, 256, 208, 3, 1),    # ragged Cout, one tap over two half-tiles, ragged last chunk (M = 53900 = 32 q + 12): 28 x 9, 61
+    (5, 148, 148, 128, 1024, 3, 2),  # stride 2, ragged Ktot (4.5 column tiles), M = 27380 = 32 q + 20: 12 splits x 20 tiles, 72
+]
+# (its 1x1 form needs a 250 MB dZ at the smallest admissible shape and no trainer shape selects it: left out)
+W8_WGRAD_KERNEL = {c: "od_conv_wgrad_w8" for c in W8_WGRAD_CASES}
+ALL_WGRAD_KERNELS = {"od_conv_wgrad", "od_conv_wgrad_w8", tk.WGRAD_THIN1, tk.WGRAD_THIN2}
 TCONV_STREAM_CASES = params_of(tk.test_first_downsample_backward_data_streaming_kernel)
 TCONV_RDIRECT_CASES = params_of(tk.test_second_downsample_backward_data_weights_resident_kernel)
 FIRST_WGRAD_CASES = params_of(tk.test_first_layer_weight_gradient)
@@ -454,15 +465,30 @@ def test_forward_overflow_becomes_inf(cuda, case):
 @pytest.mark.parametrize("case", WGRAD_CASES, ids=str)
 def test_weight_gradient(cuda, case):
     """Atomics and slabs + fixed-order reduce, from zero and into a non-zero dw: all == the integer reference."""
-    check_weight_gradient(cuda, case)
+    check_weight_gradient(cuda, case, table=tk.WGRAD_KERNEL)
 
 
-def check_weight_gradient(cuda, case, atomics=True):
+@pytest.mark.parametrize("case", W8_WGRAD_CASES, ids=str)
+def test_weight_gradient_256_wide_kernel(cuda, case):
+    """od_conv_wgrad_w8: its atomic epilogue from zero and into a non-zero dw, and its slab epilogue == the integer reference."""
+    check_weight_gradient(cuda, case, table=W8_WGRAD_KERNEL)
+
+
+def test_every_weight_gradient_kernel_is_exercised(cuda):
+    """The exact case lists reach all four kernels (what the library selects, not what the tables say)."""
+    ctx = _ctx(cuda)
+    reached = {tk.wgrad_kernel(ctx.lib, ctx.handle, c, slabs) for c in WGRAD_CASES + W8_WGRAD_CASES for slabs in (0, 1)}
+    assert reached == ALL_WGRAD_KERNELS, f"never exercised: {sorted(ALL_WGRAD_KERNELS - reached)}, unknown: {sorted(reached - ALL_WGRAD_KERNELS)}"
+
+
+def check_weight_gradient(cuda, case, atomics=True, table=None):
     from object_detector_amd import _lib
     B, H, W, Cin, Cout, k, stride = case
-    g, dw_ref, dw_acc_ref = build_wgrad(case)
     ctx = _ctx(cuda)
     lib, h = ctx.lib, ctx.handle
+    for slabs in ((False, True) if atomics else (True,)) if table else ():  # before anything is built or launched
+        tk.assert_wgrad_kernel(lib, h, case, slabs, table)
+    g, dw_ref, dw_acc_ref = build_wgrad(case)
     x, dz = L.poisoned(g.x, cuda), L.poisoned(g.dz, cuda)
     count = Cout * k * k * Cin
     for init, ref in ((np.zeros_like(g.dw0), dw_ref), (g.dw0, dw_acc_ref)) if atomics else ():

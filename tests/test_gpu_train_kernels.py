@@ -74,8 +74,9 @@ CONV_CASES = [  # B, H, W, Cin, Cout, k, stride
     (2, 32, 32, 64, 128, 3, 2),    # stride 2: whole tiles per parity class (taps skipped per tile)
     (1, 12, 28, 32, 64, 3, 2),     # stride 2, 32 gradient channels out, non-square
     (2, 6, 10, 1024, 512, 1, 1),
-    # shapes that take the 8-wave 256 x 256 weight-gradient kernel (od_conv_wgrad_w8): whole tiles, ragged Ktot (6.75 tiles),
-    # ragged Cout (208), stride 2, one tap spread over two half-tiles (Cin = 256)
+    # 256-wide layers on small maps: whole tiles, ragged Ktot (6.75 tiles of 256), ragged Cout (208), stride 2, one tap over two
+    # 128-column tiles (Cin = 256).  4 to 13 pixel chunks per workgroup: they run on the 128 x 128 weight-gradient kernel
+    # (od_conv_wgrad); od_conv_wgrad_w8 needs >= 60 chunks in >= 160 workgroups (W8_WGRAD_CASES of test_gpu_conv_exact.py)
     (2, 12, 12, 256, 256, 3, 1),
     (2, 8, 8, 192, 256, 3, 1),
     (3, 9, 9, 256, 208, 3, 1),
@@ -84,6 +85,34 @@ CONV_CASES = [  # B, H, W, Cin, Cout, k, stride
     (2, 16, 32, 32, 64, 3, 2),    # backward-data of the first stride-2 conv: the streaming kernel of conv_tconv.hip (one tile row)
     (3, 40, 64, 32, 64, 3, 2),    # 5 x 2 tiles per image, 30 tiles
 ]
+SLAB_CASES = [(8, 40, 40, 128, 256, 3, 1), (4, 20, 20, 256, 512, 3, 1), (32, 10, 10, 512, 1024, 3, 1),
+              (4, 40, 40, 256, 512, 3, 2), (16, 40, 40, 256, 128, 1, 1),
+              # the thin kernel (32 -> 64 channels, rows of whole 32-pixel chunks): stride 1 and 2, one
+              # chunk per workgroup up to several ring turns
+              (2, 8, 32, 32, 64, 3, 1), (3, 12, 64, 32, 64, 3, 1), (2, 16, 64, 32, 64, 3, 2),
+              (5, 40, 128, 32, 64, 3, 2), (16, 160, 160, 32, 64, 3, 1)]
+# The weight-gradient kernel each case is MEANT to reach in the slab form on a 256-CU part (the atomic form of a thin-kernel
+# shape runs od_conv_wgrad: the thin kernel writes slabs only).  Stated, not derived: the tests ask the library through
+# od_conv2d_bwd_weight_kernel_name and fail when a case has drifted to another kernel.
+WGRAD_THIN1, WGRAD_THIN2 = "od_conv_wgrad_thin<1>", "od_conv_wgrad_thin<2>"
+WGRAD_KERNEL = {c: "od_conv_wgrad" for c in CONV_CASES + SLAB_CASES}
+WGRAD_KERNEL.update({(3, 40, 64, 32, 64, 3, 2): WGRAD_THIN2, (2, 8, 32, 32, 64, 3, 1): WGRAD_THIN1,
+                     (3, 12, 64, 32, 64, 3, 1): WGRAD_THIN1, (2, 16, 64, 32, 64, 3, 2): WGRAD_THIN2,
+                     (5, 40, 128, 32, 64, 3, 2): WGRAD_THIN2, (16, 160, 160, 32, 64, 3, 1): WGRAD_THIN1})
+
+
+def wgrad_kernel(lib, h, case, slabs):
+    name = lib.od_conv2d_bwd_weight_kernel_name(h, *case, int(slabs))
+    return None if name is None else name.decode()
+
+
+def assert_wgrad_kernel(lib, h, case, slabs, table=WGRAD_KERNEL):
+    """The library's choice for `case` is the kernel the case was written for."""
+    want = table[case]
+    if not slabs and want in (WGRAD_THIN1, WGRAD_THIN2):
+        want = "od_conv_wgrad"
+    got = wgrad_kernel(lib, h, case, slabs)
+    assert got == want, f"{case} ({'slab' if slabs else 'atomic'} form) is meant for {want}, the library selected {got}"
 
 
 @pytest.mark.parametrize("case", CONV_CASES, ids=[str(c) for c in CONV_CASES])
@@ -134,6 +163,7 @@ def test_conv_backward(cuda, case):
     assert np.array_equal(acc1.cpu().numpy().astype(np.float64), dx2)
     assert (np.abs(dx2 - ref2) <= tol + 2.0 ** -9 * np.abs(ref2) + 1e-3).all()
     # backward-weight (f32, atomics: order noise only)
+    assert_wgrad_kernel(ctx.lib, ctx.handle, case, slabs=False)
     dw = T.conv_bwd_weight(xd, dzd, Cin, Cout, k, stride).cpu().numpy()[:Cout, :k * k * Cin]
     np.testing.assert_allclose(dw, dw_ref, rtol=2e-3, atol=2e-3 * max(1.0, np.abs(dw_ref).max()))
     # accumulation into an existing buffer (shared prediction module)
@@ -186,16 +216,14 @@ def test_bn_fold_bit_exact_vs_numpy(cuda):
         assert np.array_equal(rs, rs2) and np.array_equal(rb, rb2)
 
 
-@pytest.mark.parametrize("case", [(8, 40, 40, 128, 256, 3, 1), (4, 20, 20, 256, 512, 3, 1), (32, 10, 10, 512, 1024, 3, 1),
-                                  (4, 40, 40, 256, 512, 3, 2), (16, 40, 40, 256, 128, 1, 1),
-                                  # the thin kernel (32 -> 64 channels, rows of whole 32-pixel chunks): stride 1 and 2, one
-                                  # chunk per workgroup up to several ring turns
-                                  (2, 8, 32, 32, 64, 3, 1), (3, 12, 64, 32, 64, 3, 1), (2, 16, 64, 32, 64, 3, 2),
-                                  (5, 40, 128, 32, 64, 3, 2), (16, 160, 160, 32, 64, 3, 1)], ids=str)
+@pytest.mark.parametrize("case", SLAB_CASES, ids=str)
 def test_weight_gradient_slab_path_many_splits(cuda, case):
     """The form the trainer uses: per-split f32 slabs (plain stores) + fixed-order reduce, at sizes where the pixel range is
-    split over many workgroups (both kernels: the 256-wide one needs >= 60 chunks per workgroup, e.g. the 16 x 160 x 160 case).  vs torch conv2d weight gradient in
-    f64; two runs are bit-identical (no atomics anywhere)."""
+    split over many workgroups: the 128 x 128 kernel (2 to 200 splits) and the thin kernel (16 to 512 slabs; the
+    16 x 160 x 160 case is the trainer's b.s1.0.b layer), each case on the kernel WGRAD_KERNEL names.  The 256-wide kernel
+    needs >= 60 chunks in each of >= 160 workgroups, ~50 GFLOP: too much for the f64 CPU reference here, its cases are the
+    W8_WGRAD_CASES of test_gpu_conv_exact.py.  vs torch conv2d weight gradient in f64; two runs are bit-identical (no
+    atomics anywhere)."""
     import ctypes as C
     from object_detector_amd import _lib
     from object_detector_amd.net import Context
@@ -212,6 +240,7 @@ def test_weight_gradient_slab_path_many_splits(cuda, case):
     lib, h = ctx.lib, ctx.handle
     s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     xd, dzd = torch.from_numpy(x).to(cuda), torch.from_numpy(dz).to(cuda)
+    assert_wgrad_kernel(lib, h, case, slabs=True)
     sp = lib.od_conv2d_bwd_weight_splits(h, B, H, W, Cin, Cout, k, stride)
     assert sp >= 1
     count = Cout * k * k * Cin

@@ -104,7 +104,7 @@ def test_conditions_backward_data(case):
     E.build_bwd(case)
 
 
-@pytest.mark.parametrize("case", E.WGRAD_CASES, ids=str)
+@pytest.mark.parametrize("case", E.WGRAD_CASES + E.W8_WGRAD_CASES, ids=str)
 def test_conditions_weight_gradient(case):
     E.build_wgrad(case)
 
