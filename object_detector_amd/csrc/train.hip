@@ -518,7 +518,11 @@ __global__ __launch_bounds__(256) void od_pred_grad_level_k(const float* __restr
   const long long total = (long long)B * n_per_img;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const long long b = i / n_per_img, r = i - b * n_per_img;
-    dz[i] = (f16)(g[b * img_stride + off + r] * scale);
+    float v = g[b * img_stride + off + r] * scale;
+    // keep the product an f32 VALU result: fused with the conversion (v_fma_mixlo_f16: a * b + 0) a product of -0 comes out
+    // as +0, and only in the loop's remainder iterations
+    asm volatile("" : "+v"(v));
+    dz[i] = (f16)v;
   }
 }
 
