@@ -381,7 +381,10 @@ int od_pred_grad_to_level(od_ctx* ctx, const float* grad_pred, void* dz, int B, 
 int od_sgd_step(od_ctx* ctx, float* w, float* m, const float* g, long long n, float lr, float momentum,
                 float weight_decay, float inv_loss_scale, void* stream);
 /* master f32 [Cout][k*k*Cin] -> f16 forward pack [Cout_pad][Kpad] and (w_bwd != NULL) backward-data pack
- * [Cin_pad][Kpad_t] (taps flipped, channels swapped); both destinations must be pre-zeroed once (padding) */
+ * [Cin_pad][Kpad_t] (taps flipped, channels swapped); both destinations must be pre-zeroed once (padding).  The
+ * backward-data pack is stored in groups of 8 output channels: w_bwd != NULL needs Cout % 8 == 0 (od_conv2d_fwd, its
+ * consumer, needs that of both channel counts anyway), and w_fwd / w_bwd must be 16-byte aligned (vector stores);
+ * otherwise OD_ERR_INVALID. */
 int od_pack_weights(od_ctx* ctx, const float* w, void* w_fwd, void* w_bwd, int Cout, int Cin, int ksize, void* stream);
 
 /* Deterministic weight gradients: od_conv2d_bwd_weight_slabs writes the per-split partial sums as

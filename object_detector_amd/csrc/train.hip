@@ -7,13 +7,14 @@
 //   od_scale_act       that fused elementwise form (the inference conv epilogue, as its own pass)
 //   od_bn_bwd          da = dy * act'(.) ; dgamma = sum(da*xhat), dbeta = sum(da) ; dz = gamma*rstd*(da - dbeta/N - xhat*dgamma/N)
 //   od_down2_sum_add   gradient of the nearest 2x upsample in the FPN top-down add
-//   od_sgd_step        SGD + momentum + weight decay on f32 masters with per-layer LR multipliers
-//                      (docs/MODEL.md:84-90: shared layers x 1/share-count, base network x 1/100), re-packs the f16 copies
+//   od_add_f16, od_pred_grad_to_level, od_cast_f32_bf16 / od_cast_bf16_f32   small elementwise passes
+//   od_sgd_step[_multi]      SGD + momentum + weight decay on f32 masters: one flat segment, or one launch over a device
+//                      table of segments (each with its own learning rate: the trainer folds the per-layer multipliers of
+//                      docs/MODEL.md:84-90 into it); od_grad_nonfinite / od_copy_if_nonzero guard a step that overflowed
+//   od_pack_weights[_multi]  f32 masters -> the f16 forward and backward-data packs of the convolutions
 //
 // reference: the Keras BatchNormalization / activation / optimizer machinery behind the (unseen) `fit` of
 // tk.dl.od.ObjectDetector; specified here by docs/MODEL.md:19-21,84-90.
-#include <string.h>
-
 #include "common.h"
 
 namespace {
@@ -21,28 +22,62 @@ namespace {
 constexpr int ROW_UNROLL = 4;      // rows in flight per thread in the row-walking kernels
 constexpr int RED_ROWS_MAX = 8192;  // rows per workgroup in the channel reductions (upper bound)
 
-// rows per workgroup: enough workgroups to fill the chip (>= ~2048), a multiple of the row lanes of one workgroup
-static inline int rows_per_wg(long long M, int C) {
+// ---- lane layout of the row-walking kernels over [M, C]: thread = (8-channel group g, row lane rl).  G = C / 8 groups; a
+// workgroup of 256 threads holds `lanes` row lanes of min(G, 256) groups each (threads beyond lanes * G idle) and walks the
+// rows [blockIdx.x * rows_wg, + rows_wg) in steps of `lanes`.  C > 2048 takes passes of 256 groups (g0 = 0, 256, ...).
+__host__ __device__ inline int chan_row_lanes(int C) {
   const int G = C >> 3;
-  const int lanes = 256 / (G < 256 ? G : 256);
-  long long r = (M + 1023) / 1024;  // <= ~1024 partial rows for the final pass
-  r = (r + lanes - 1) / lanes * lanes;
-  if (r < lanes) r = lanes;
-  if (r > RED_ROWS_MAX) r = RED_ROWS_MAX;
-  return (int)r;
+  return 256 / (G < 256 ? G : 256);
+}
+struct chan_lane {
+  int G, lanes, g, rl;  // groups, row lanes, this thread's group and row lane
+  long long r0, r1;     // the workgroup's rows
+  bool active;
+};
+__device__ __forceinline__ chan_lane chan_lane_of(long long M, int C, int rows_wg, int g0 = 0) {
+  const int tid = threadIdx.x, G = C >> 3, lanes = chan_row_lanes(C);
+  const int g = g0 + (lanes > 1 ? tid % G : tid), rl = lanes > 1 ? tid / G : 0;
+  const long long r0 = (long long)blockIdx.x * rows_wg;
+  return {G, lanes, g, rl, r0, min(r0 + rows_wg, M), g < G && rl < lanes};
+}
+// one thread's rows, ROW_UNROLL per trip: every load(u, row) of a trip before its first use(u, row) (one load in flight: 1.5 TB/s)
+template <class Load, class Use>
+__device__ __forceinline__ void walk_rows(const chan_lane& L, Load load, Use use) {
+  for (long long r = L.r0 + L.rl; r < L.r1; r += (long long)ROW_UNROLL * L.lanes) {
+#pragma unroll
+    for (int u = 0; u < ROW_UNROLL; ++u) {
+      const long long ru = r + (long long)u * L.lanes;
+      if (ru >= L.r1) break;
+      load(u, ru);
+    }
+#pragma unroll
+    for (int u = 0; u < ROW_UNROLL; ++u) {
+      const long long ru = r + (long long)u * L.lanes;
+      if (ru >= L.r1) break;
+      use(u, ru);
+    }
+  }
 }
 
-// the channel reductions write one partial row per workgroup and od_chan_final walks those rows: at least 32 KiB of
-// tensor per workgroup, so that a small layer does not produce as many bytes of partials as it has data
-static inline int rows_per_wg_reduce(long long M, int C) {
-  const int G = C >> 3;
-  const int lanes = 256 / (G < 256 ? G : 256);
+// rows per workgroup: <= ~1024 workgroups, a multiple of the row lanes, at least min_bytes_per_wg of tensor: 0 for the apply
+// passes, 32 KiB for the reductions (a small layer must not write as many bytes of partial rows as it has data)
+static inline int rows_per_wg(long long M, int C, int min_bytes_per_wg) {
+  const int lanes = chan_row_lanes(C);
   long long r = (M + 1023) / 1024;
-  const long long rmin = (32768 + 2 * C - 1) / (2 * C);
+  const long long rmin = (min_bytes_per_wg + 2 * C - 1) / (2 * C);
   if (r < rmin) r = rmin;
   r = (r + lanes - 1) / lanes * lanes;
   if (r > RED_ROWS_MAX) r = RED_ROWS_MAX;
   return (int)r;
+}
+
+struct chan_plan {  // the reductions' launch: rw rows per workgroup, nblocks workgroups = partial rows of [2][C] floats
+  int rw, nblocks;
+  size_t partial_bytes;
+};
+static inline chan_plan chan_reduce_plan(long long M, int C) {
+  const int rw = rows_per_wg(M, C, 32768), nblocks = (int)((M + rw - 1) / rw);
+  return {rw, nblocks, (size_t)nblocks * 2 * C * sizeof(float)};
 }
 
 // The activation is a TEMPLATE parameter of the elementwise kernels (round 2): as a run-time enum tested per element the
@@ -80,21 +115,17 @@ template <int MODE, int ACT>
 __global__ __launch_bounds__(256) void od_chan_reduce(const f16* __restrict__ z, const f16* __restrict__ dy,
                                                       const float* __restrict__ scale, const float* __restrict__ shift,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                      long long M, int C, int act, float alpha, int rows_wg,
+                                                      long long M, int C, float alpha, int rows_wg,
                                                       float* __restrict__ partials) {
   extern __shared__ float red[];  // [2][256][8]
-  const int G = C >> 3;                       // channel groups
   const int tid = threadIdx.x;
-  const int lanes = 256 / min(G, 256);        // row lanes per group inside one pass
-  const long long r0 = (long long)blockIdx.x * rows_wg;
-  const long long r1 = min(r0 + rows_wg, M);
-  for (int g0 = 0; g0 < G; g0 += 256) {       // C > 2048 loops (not used by this network)
-    const int g = g0 + (lanes > 1 ? tid % G : tid);
-    const int rl = lanes > 1 ? tid / G : 0;
+  for (int g0 = 0; g0 < (C >> 3); g0 += 256) {  // C > 2048 loops (the bias layer of a many-class head)
+    const chan_lane L = chan_lane_of(M, C, rows_wg, g0);
+    const int G = L.G, lanes = L.lanes, g = L.g, rl = L.rl;
     float s0[8], s1[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) s0[e] = s1[e] = 0.f;
-    if (g < G && rl < lanes) {
+    if (L.active) {
       float sc[8], sh[8], mu[8], rs[8];
       if (MODE == 1) {
 #pragma unroll
@@ -105,43 +136,31 @@ __global__ __launch_bounds__(256) void od_chan_reduce(const f16* __restrict__ z,
           rs[e] = rstd[g * 8 + e];
         }
       }
-      // ROW_UNROLL independent 16-B loads per tensor in flight per thread (one load per trip left the kernel at ~1.5 TB/s)
-      for (long long r = r0 + rl; r < r1; r += (long long)ROW_UNROLL * lanes) {
-        f16x8 zv[ROW_UNROLL], dv[ROW_UNROLL];
+      f16x8 zv[ROW_UNROLL], dv[ROW_UNROLL];
+      const auto load = [&](int u, long long r) {
+        zv[u] = *(const f16x8*)(z + r * C + g * 8);
+        if (MODE == 1) dv[u] = *(const f16x8*)(dy + r * C + g * 8);
+      };
+      const auto use = [&](int u, long long) {
 #pragma unroll
-        for (int u = 0; u < ROW_UNROLL; ++u) {
-          const long long rr = r + (long long)u * lanes;
-          if (rr < r1) {
-            zv[u] = *(const f16x8*)(z + rr * C + g * 8);
-            if (MODE == 1) dv[u] = *(const f16x8*)(dy + rr * C + g * 8);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < ROW_UNROLL; ++u) {
-          if (r + (long long)u * lanes >= r1) break;
+        for (int e = 0; e < 8; ++e) {
+          const float zf = (float)zv[u][e];
           if (MODE == 0) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float v = (float)zv[u][e];
-              s0[e] += v;
-              s1[e] += v * v;
-            }
+            s0[e] += zf;
+            s1[e] += zf * zf;
           } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float zf = (float)zv[u][e];
-              const float da = (float)dv[u][e] * act_grad<ACT>(zf * sc[e] + sh[e], alpha);
-              s0[e] += da;
-              s1[e] += da * ((zf - mu[e]) * rs[e]);
-            }
+            const float da = (float)dv[u][e] * act_grad<ACT>(zf * sc[e] + sh[e], alpha);
+            s0[e] += da;
+            s1[e] += da * ((zf - mu[e]) * rs[e]);
           }
         }
-      }
+      };
+      walk_rows(L, load, use);
     }
     // fixed-order sum over the row lanes of each group: butterfly inside the wave when the G groups tile a wave
     // (power-of-two G < 64), then over the remaining holders (waves / row lanes) through LDS
     int hidx = rl, nh = lanes;
-    bool holder = g < G && rl < lanes;
+    bool holder = L.active;
     if (lanes > 1 && G < 64 && (G & (G - 1)) == 0) {
       for (int off = G; off < 64; off <<= 1) {
 #pragma unroll
@@ -185,21 +204,16 @@ __global__ __launch_bounds__(256) void od_chan_reduce(const f16* __restrict__ z,
   }
 }
 
-// fixed-order final sums; MODE 0 -> mean, rstd, scale, shift (and running stats); MODE 1 -> dgamma, dbeta
-template <int MODE>
-__global__ __launch_bounds__(256) void od_chan_final(const float* __restrict__ partials, int nblocks, int C, float invM,
-                                                     float eps, const float* __restrict__ gamma,
-                                                     const float* __restrict__ beta, float* __restrict__ o0,
-                                                     float* __restrict__ o1, float* __restrict__ o2,
-                                                     float* __restrict__ o3, float* __restrict__ run_mean,
-                                                     float* __restrict__ run_var, float momentum) {
-  // 8 channels per workgroup x 32 partial lanes; fixed summation order (lane-strided partials, then lanes 0..31)
+// Fixed-order sums (a, b) of the two planes of the partial rows: 8 channels per workgroup x 32 partial lanes, lane-strided with
+// 4 loads per sum in flight (one was a ~10 us latency chain), then lanes 0..31.  True for the thread that holds channel c's sums.
+__device__ __forceinline__ bool chan_partials_sum(const float* __restrict__ partials, int nblocks, int C, int& c, float& a,
+                                                  float& b) {
   __shared__ float red[2][32][8];
   const int cl = threadIdx.x & 7, ln = threadIdx.x >> 3;
-  const int c = blockIdx.x * 8 + cl;
-  float a = 0.f, b = 0.f;
+  c = blockIdx.x * 8 + cl;
+  a = 0.f, b = 0.f;
   if (c < C) {
-    for (int i = ln; i < nblocks; i += 128) {  // 4 independent loads per sum in flight (was one: ~10 us of latency chain)
+    for (int i = ln; i < nblocks; i += 128) {
       float av[4], bv[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -217,33 +231,51 @@ __global__ __launch_bounds__(256) void od_chan_final(const float* __restrict__ p
   red[0][ln][cl] = a;
   red[1][ln][cl] = b;
   __syncthreads();
-  if (ln != 0 || c >= C) return;
-  a = 0.f;
-  b = 0.f;
+  if (ln != 0 || c >= C) return false;
+  a = 0.f, b = 0.f;
 #pragma unroll
   for (int l = 0; l < 32; ++l) {
     a += red[0][l][cl];
     b += red[1][l][cl];
   }
-  if (MODE == 0) {
-    const float mu = a * invM;
-    const float var = fmaxf(b * invM - mu * mu, 0.f);
-    const float rs = rsqrtf(var + eps);
-    const float sc = gamma[c] * rs;
-    o0[c] = mu;
-    o1[c] = rs;
-    o2[c] = sc;
-    o3[c] = beta[c] - mu * sc;
-    if (run_mean) {
-      run_mean[c] = momentum * run_mean[c] + (1.f - momentum) * mu;
-      run_var[c] = momentum * run_var[c] + (1.f - momentum) * var;
-    }
-  } else {
-    o0[c] += b;  // dgamma (accumulates: the prediction module is shared by three levels)
-    o1[c] += a;  // dbeta
-    o2[c] = b;   // this call's sums, consumed by the apply pass
-    o3[c] = a;
+  return true;
+}
+
+// (sum z, sum z^2) -> mean, rstd and the folded (scale, shift); running statistics when run_mean is given
+__global__ __launch_bounds__(256) void od_bn_stats_final_k(const float* __restrict__ partials, int nblocks, int C, float invM,
+                                                           float eps, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, float* __restrict__ mean,
+                                                           float* __restrict__ rstd, float* __restrict__ scale,
+                                                           float* __restrict__ shift, float* __restrict__ run_mean,
+                                                           float* __restrict__ run_var, float momentum) {
+  int c;
+  float sum_z, sum_zz;
+  if (!chan_partials_sum(partials, nblocks, C, c, sum_z, sum_zz)) return;
+  const float mu = sum_z * invM;
+  const float var = fmaxf(sum_zz * invM - mu * mu, 0.f);
+  const float rs = rsqrtf(var + eps);
+  const float sc = gamma[c] * rs;
+  mean[c] = mu;
+  rstd[c] = rs;
+  scale[c] = sc;
+  shift[c] = beta[c] - mu * sc;
+  if (run_mean) {
+    run_mean[c] = momentum * run_mean[c] + (1.f - momentum) * mu;
+    run_var[c] = momentum * run_var[c] + (1.f - momentum) * var;
   }
+}
+
+// dgamma / dbeta ACCUMULATE (the prediction module is shared by three levels); sum_dax / sum_da = this call's own sums (apply pass)
+__global__ __launch_bounds__(256) void od_bn_bwd_final_k(const float* __restrict__ partials, int nblocks, int C,
+                                                         float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                         float* __restrict__ sum_dax, float* __restrict__ sum_da) {
+  int c;
+  float da, dax;
+  if (!chan_partials_sum(partials, nblocks, C, c, da, dax)) return;
+  dgamma[c] += dax;
+  dbeta[c] += da;
+  sum_dax[c] = dax;
+  sum_da[c] = da;
 }
 
 // Elementwise passes over [M, C]: thread = (fixed 8-channel group g, row lane); the per-channel constants are loaded
@@ -251,56 +283,47 @@ __global__ __launch_bounds__(256) void od_chan_final(const float* __restrict__ p
 template <int ACT>
 __global__ __launch_bounds__(256) void od_scale_act_k(const f16* __restrict__ z, const float* __restrict__ scale,
                                                       const float* __restrict__ shift, const f16* __restrict__ res,
-                                                      f16* __restrict__ y, long long M, int C, int act, float alpha,
-                                                      int res_up2, int H, int W, int rows_wg) {
-  const int G = C >> 3, tid = threadIdx.x;
-  const int lanes = 256 / min(G, 256);
-  const int g = lanes > 1 ? tid % G : tid, rl = lanes > 1 ? tid / G : 0;
-  if (g >= G || rl >= lanes) return;
+                                                      f16* __restrict__ y, long long M, int C, float alpha, int res_up2,
+                                                      int H, int W, int rows_wg) {
+  const chan_lane L = chan_lane_of(M, C, rows_wg);
+  if (!L.active) return;
+  const int g = L.g;
   float sc[8], sh[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     sc[e] = scale[g * 8 + e];
     sh[e] = shift[g * 8 + e];
   }
-  const long long r0 = (long long)blockIdx.x * rows_wg, r1 = min(r0 + rows_wg, M);
-  for (long long r = r0 + rl; r < r1; r += (long long)ROW_UNROLL * lanes) {
-    f16x8 zv[ROW_UNROLL], rv[ROW_UNROLL];
-#pragma unroll
-    for (int u = 0; u < ROW_UNROLL; ++u) {
-      const long long ru = r + (long long)u * lanes;
-      if (ru >= r1) break;
-      zv[u] = *(const f16x8*)(z + ru * C + g * 8);
-      if (res) {
-        long long rr = ru;
-        if (res_up2) {
-          long long pix = ru;
-          const int x = (int)(pix % W);
-          pix /= W;
-          const int yy = (int)(pix % H);
-          const long long b = pix / H;
-          rr = (b * (H >> 1) + (yy >> 1)) * (W >> 1) + (x >> 1);
-        }
-        rv[u] = *(const f16x8*)(res + rr * C + g * 8);
+  f16x8 zv[ROW_UNROLL], rv[ROW_UNROLL];
+  const auto load = [&](int u, long long r) {
+    zv[u] = *(const f16x8*)(z + r * C + g * 8);
+    if (res) {
+      long long rr = r;
+      if (res_up2) {
+        long long pix = r;
+        const int x = (int)(pix % W);
+        pix /= W;
+        const int yy = (int)(pix % H);
+        const long long b = pix / H;
+        rr = (b * (H >> 1) + (yy >> 1)) * (W >> 1) + (x >> 1);
       }
+      rv[u] = *(const f16x8*)(res + rr * C + g * 8);
     }
+  };
+  const auto use = [&](int u, long long r) {
+    float v[8];
 #pragma unroll
-    for (int u = 0; u < ROW_UNROLL; ++u) {
-      const long long ru = r + (long long)u * lanes;
-      if (ru >= r1) break;
-      float v[8];
+    for (int e = 0; e < 8; ++e) v[e] = act_fwd<ACT>((float)zv[u][e] * sc[e] + sh[e], alpha);
+    if (res) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = act_fwd<ACT>((float)zv[u][e] * sc[e] + sh[e], alpha);
-      if (res) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += (float)rv[u][e];
-      }
-      f16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (f16)v[e];
-      *(f16x8*)(y + ru * C + g * 8) = o;
+      for (int e = 0; e < 8; ++e) v[e] += (float)rv[u][e];
     }
-  }
+    f16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (f16)v[e];
+    *(f16x8*)(y + r * C + g * 8) = o;
+  };
+  walk_rows(L, load, use);
 }
 
 // dz = gamma*rstd*(da - dbeta/N - xhat*dgamma/N), da = dy*act'(scale*z+shift); bn == 0: dz = da (conv bias layer)
@@ -309,18 +332,16 @@ __global__ __launch_bounds__(256) void od_bn_bwd_apply_k(const f16* __restrict__
                                                          const float* __restrict__ scale, const float* __restrict__ shift,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ sum_dax, const float* __restrict__ sum_da,
-                                                         f16* __restrict__ dz, long long M, int C, float invM, int act,
+                                                         f16* __restrict__ dz, long long M, int C, float invM,
                                                          float alpha, int bn, int rows_wg) {
-  const int G = C >> 3, tid = threadIdx.x;
-  const int lanes = 256 / min(G, 256);
-  const int g = lanes > 1 ? tid % G : tid, rl = lanes > 1 ? tid / G : 0;
-  if (g >= G || rl >= lanes) return;
+  const chan_lane L = chan_lane_of(M, C, rows_wg);
+  if (!L.active) return;
+  const int g = L.g;
   float sc[8], sh[8], mu[8], rs[8], k1[8], k2[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int c = g * 8 + e;
-    // all six pointers are valid for bn == 0 too (the host passes stand-ins): unconditional loads, ONE wait --
-    // per-element `bn ? p[c] : 0` compiled to 48 serialised load round trips (a 20 us floor per launch)
+    // unconditional loads, ONE wait: per-element `bn ? p[c] : 0` compiled to 48 serialised round trips (20 us per launch)
     sc[e] = scale[c];
     sh[e] = shift[c];
     mu[e] = mean[c];
@@ -328,32 +349,24 @@ __global__ __launch_bounds__(256) void od_bn_bwd_apply_k(const f16* __restrict__
     k1[e] = sum_da[c] * invM;
     k2[e] = sum_dax[c] * invM;
   }
-  const long long r0 = (long long)blockIdx.x * rows_wg, r1 = min(r0 + rows_wg, M);
-  for (long long r = r0 + rl; r < r1; r += (long long)ROW_UNROLL * lanes) {
-    f16x8 zv[ROW_UNROLL], dv[ROW_UNROLL];
+  f16x8 zv[ROW_UNROLL], dv[ROW_UNROLL];
+  const auto load = [&](int u, long long r) {
+    zv[u] = *(const f16x8*)(z + r * C + g * 8);
+    dv[u] = *(const f16x8*)(dy + r * C + g * 8);
+  };
+  const auto use = [&](int u, long long r) {
+    f16x8 o;
 #pragma unroll
-    for (int u = 0; u < ROW_UNROLL; ++u) {
-      const long long ru = r + (long long)u * lanes;
-      if (ru >= r1) break;
-      zv[u] = *(const f16x8*)(z + ru * C + g * 8);
-      dv[u] = *(const f16x8*)(dy + ru * C + g * 8);
+    for (int e = 0; e < 8; ++e) {
+      const float zf = (float)zv[u][e];
+      const float da = (float)dv[u][e] * act_grad<ACT>(zf * sc[e] + sh[e], alpha);
+      float rr = da;
+      if (bn) rr = sc[e] * (da - k1[e] - ((zf - mu[e]) * rs[e]) * k2[e]);  // scale = gamma*rstd
+      o[e] = (f16)rr;
     }
-#pragma unroll
-    for (int u = 0; u < ROW_UNROLL; ++u) {
-      const long long ru = r + (long long)u * lanes;
-      if (ru >= r1) break;
-      f16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float zf = (float)zv[u][e];
-        const float da = (float)dv[u][e] * act_grad<ACT>(zf * sc[e] + sh[e], alpha);
-        float rr = da;
-        if (bn) rr = sc[e] * (da - k1[e] - ((zf - mu[e]) * rs[e]) * k2[e]);  // scale = gamma*rstd
-        o[e] = (f16)rr;
-      }
-      *(f16x8*)(dz + ru * C + g * 8) = o;
-    }
-  }
+    *(f16x8*)(dz + r * C + g * 8) = o;
+  };
+  walk_rows(L, load, use);
 }
 
 // d_up[b,y,x,c] (+)= sum over the 2x2 block of d[b,2y..,2x..,c]
@@ -399,35 +412,21 @@ __global__ __launch_bounds__(256) void od_add_f16_k(f16* __restrict__ a, const f
   }
 }
 
-// SGD + momentum on a flat f32 segment; optional f16 re-pack of conv weights into the forward layout [Cout_pad][Kpad]
-// and the backward-data layout [Cin_pad][Kpad_t] (taps flipped, in/out channels swapped)
+// w -= lr * (m = momentum * m + g * inv_scale + wd * w)
+__device__ __forceinline__ void sgd_update(float& w, float& m, float g, float lr, float momentum, float wd, float inv_scale) {
+  const float grad = g * inv_scale + wd * w;
+  const float mv = momentum * m + grad;
+  m = mv;
+  w -= lr * mv;
+}
+
 __global__ __launch_bounds__(256) void od_sgd_k(float* __restrict__ w, float* __restrict__ m, const float* __restrict__ g,
                                                 long long n, float lr, float momentum, float wd, float inv_scale) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const float grad = g[i] * inv_scale + wd * w[i];
-    const float mv = momentum * m[i] + grad;
-    m[i] = mv;
-    w[i] -= lr * mv;
-  }
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    sgd_update(w[i], m[i], g[i], lr, momentum, wd, inv_scale);
 }
 
-// master weights f32 [Cout][k*k*Cin] (k index = tap*Cin + cin) -> forward f16 [Cout_pad][Kpad] and, for the backward-data
-// conv, f16 [Cin_pad][Kpad_t] with wt[ci][(k*k-1-tap)*Cout + co] = w[co][tap*Cin + ci]
-__global__ __launch_bounds__(256) void od_pack_w_k(const float* __restrict__ w, f16* __restrict__ wf, f16* __restrict__ wt,
-                                                   int Cout, int Cin, int taps, int Kpad, int Kpad_t) {
-  const long long n = (long long)Cout * taps * Cin;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const int ci = (int)(i % Cin);
-    const long long r = i / Cin;
-    const int tap = (int)(r % taps);
-    const int co = (int)(r / taps);
-    const f16 v = (f16)w[i];
-    wf[(long long)co * Kpad + tap * Cin + ci] = v;
-    if (wt) wt[(long long)ci * Kpad_t + (taps - 1 - tap) * Cout + co] = v;
-  }
-}
-
-// multi-tensor forms: blockIdx.y = tensor, blockIdx.x strides over its elements
+// multi-tensor form: blockIdx.y = segment of the device table, blockIdx.x strides over its elements
 __global__ __launch_bounds__(256) void od_sgd_multi_k(float* __restrict__ w, float* __restrict__ m, const float* __restrict__ g,
                                                       const od_sgd_seg* __restrict__ segs, float momentum, float inv_scale,
                                                       const int32_t* __restrict__ skip) {
@@ -436,32 +435,27 @@ __global__ __launch_bounds__(256) void od_sgd_multi_k(float* __restrict__ w, flo
   float* ws = w + sg.offset;
   float* ms = m + sg.offset;
   const float* gs = g + sg.offset;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < sg.count; i += (long long)gridDim.x * 256) {
-    const float grad = gs[i] * inv_scale + sg.weight_decay * ws[i];
-    const float mv = momentum * ms[i] + grad;
-    ms[i] = mv;
-    ws[i] -= sg.lr * mv;
-  }
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < sg.count; i += (long long)gridDim.x * 256)
+    sgd_update(ws[i], ms[i], gs[i], sg.lr, momentum, sg.weight_decay, inv_scale);
 }
 
-// One 64 (Cout) x 64 (Cin) tile of one tap per trip: coalesced f32 reads, forward-layout rows written straight from the
-// registers (8-B stores), the backward-data layout (in/out channels swapped) through an LDS transpose as 16-B stores of
-// 8 consecutive output channels -- the per-element form scattered 40 M two-byte writes (580 us per step).
-__global__ __launch_bounds__(256) void od_pack_multi_k(const float* __restrict__ wflat, const od_pack_layer* __restrict__ layers) {
+// f16 re-pack of conv weights: master f32 [Cout][k*k*Cin] (k index = tap*Cin + cin) -> forward f16 [Cout_pad][Kpad] and, for
+// the backward-data conv, f16 [Cin_pad][Kpad_t] with wt[ci][(k*k-1-tap)*Cout + co] = w[co][tap*Cin + ci] (taps flipped,
+// channels swapped).  One 64 (Cout) x 64 (Cin) tile of one tap per trip: coalesced f32 reads, forward rows written straight
+// from the registers (8-B stores), the backward layout through an LDS transpose as 16-B stores of 8 consecutive output
+// channels -- a per-element form scattered 40 M two-byte writes (580 us per step).
+__device__ __forceinline__ void pack_layer(const od_pack_layer L, const float* __restrict__ wflat) {
   __shared__ f16 tile[64][68];  // [co][ci]
-  const od_pack_layer L = layers[blockIdx.y];
   const int taps = L.ksize * L.ksize;
   const int Kpad = (taps * L.Cin + 63) / 64 * 64, Kpad_t = (taps * L.Cout + 63) / 64 * 64;
   const float* w = wflat + L.w_offset;
-  f16* wf = (f16*)L.w_fwd;
-  f16* wt = (f16*)L.w_bwd;
+  f16 *wf = (f16*)L.w_fwd, *wt = (f16*)L.w_bwd;
   const int cob = (L.Cout + 63) >> 6, cib = (L.Cin + 63) >> 6;
   const int ntiles = taps * cob * cib;
   const int tid = threadIdx.x;
-  const bool vec = ((L.w_offset | L.Cin) & 3) == 0;
+  const bool vec = ((uintptr_t)w & 15) == 0 && (L.Cin & 3) == 0;  // every row of 4 input channels is one 16-B load
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const int ib = t % cib;
-    const int r = t / cib;
+    const int ib = t % cib, r = t / cib;
     const int ob = r % cob, tap = r / cob;
     const int co0 = ob * 64, ci0 = ib * 64;
 #pragma unroll
@@ -510,6 +504,15 @@ __global__ __launch_bounds__(256) void od_pack_multi_k(const float* __restrict__
   }
 }
 
+// blockIdx.y = layer of the device table, blockIdx.x strides over its tiles
+__global__ __launch_bounds__(256) void od_pack_multi_k(const float* __restrict__ wflat, const od_pack_layer* __restrict__ layers) {
+  pack_layer(layers[blockIdx.y], wflat);
+}
+__global__ __launch_bounds__(256) void od_pack_one_k(const float* __restrict__ w, f16* __restrict__ wf, f16* __restrict__ wt,
+                                                     int Cout, int Cin, int ksize) {
+  pack_layer(od_pack_layer{0, wf, wt, Cout, Cin, ksize, 0}, w);
+}
+
 // loss gradient w.r.t. pred (f32 [B,P,C], rows of one pyramid level) -> loss-scaled f16 NHWC gradient of that level's
 // prediction conv output [B, rows*C] (rows = H*W*8 priors, C = 2+NC+4 -> H*W x 8*C channels)
 __global__ __launch_bounds__(256) void od_pred_grad_level_k(const float* __restrict__ g, f16* __restrict__ dz, int B,
@@ -555,30 +558,7 @@ extern "C" int od_bn_fold(od_ctx* ctx, const float* gamma, const float* beta, co
 
 extern "C" size_t od_bn_workspace_bytes(long long M, int C) {
   if (M <= 0 || C <= 0 || C % 8) return 0;
-  const int rw = rows_per_wg_reduce(M, C);
-  return (size_t)((M + rw - 1) / rw) * 2 * C * sizeof(float);
-}
-
-extern "C" int od_bn_stats(od_ctx* ctx, const void* z, long long M, int C, const float* gamma, const float* beta,
-                           float eps, float* mean, float* rstd, float* scale, float* shift, float* run_mean,
-                           float* run_var, float momentum, void* workspace, size_t workspace_bytes, void* stream) {
-  OD_REQUIRE(ctx && z && gamma && beta && mean && rstd && scale && shift && workspace, "od_bn_stats: null argument");
-  OD_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= 2048, "od_bn_stats: C must be a multiple of 8, <= 2048");
-  const int rw = rows_per_wg_reduce(M, C);
-  const int nblocks = (int)((M + rw - 1) / rw);
-  if (workspace_bytes < od_bn_workspace_bytes(M, C)) {
-    od_set_error("od_bn_stats: workspace too small");
-    return OD_ERR_WORKSPACE;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  hipLaunchKernelGGL((od_chan_reduce<0, OD_ACT_LINEAR>), dim3(nblocks), dim3(256), 2 * 256 * 8 * sizeof(float), s, (const f16*)z,
-                     (const f16*)nullptr, nullptr, nullptr, nullptr, nullptr, M, C, 0, 0.f, rw, part);
-  OD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(od_chan_final<0>, dim3(od_ceil_div(C, 8)), dim3(256), 0, s, part, nblocks, C, 1.f / (float)M, eps,
-                     gamma, beta, mean, rstd, scale, shift, run_mean, run_var, momentum);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
+  return chan_reduce_plan(M, C).partial_bytes;
 }
 
 extern "C" int od_bn_stats_from_partials(od_ctx* ctx, const float* partials, int rows, long long M, int C, const float* gamma,
@@ -586,10 +566,29 @@ extern "C" int od_bn_stats_from_partials(od_ctx* ctx, const float* partials, int
                                          float* run_mean, float* run_var, float momentum, void* stream) {
   OD_REQUIRE(ctx && partials && gamma && beta && mean && rstd && scale && shift, "od_bn_stats_from_partials: null argument");
   OD_REQUIRE(rows > 0 && M > 0 && C > 0 && C % 8 == 0, "od_bn_stats_from_partials: bad dims");
-  hipLaunchKernelGGL(od_chan_final<0>, dim3(od_ceil_div(C, 8)), dim3(256), 0, (hipStream_t)stream, partials, rows, C,
+  hipLaunchKernelGGL(od_bn_stats_final_k, dim3(od_ceil_div(C, 8)), dim3(256), 0, (hipStream_t)stream, partials, rows, C,
                      1.f / (float)M, eps, gamma, beta, mean, rstd, scale, shift, run_mean, run_var, momentum);
   OD_CHECK_LAUNCH();
   return OD_OK;
+}
+
+extern "C" int od_bn_stats(od_ctx* ctx, const void* z, long long M, int C, const float* gamma, const float* beta,
+                           float eps, float* mean, float* rstd, float* scale, float* shift, float* run_mean,
+                           float* run_var, float momentum, void* workspace, size_t workspace_bytes, void* stream) {
+  OD_REQUIRE(ctx && z && gamma && beta && mean && rstd && scale && shift && workspace, "od_bn_stats: null argument");
+  OD_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= 2048, "od_bn_stats: C must be a multiple of 8, <= 2048");
+  const chan_plan p = chan_reduce_plan(M, C);
+  if (workspace_bytes < p.partial_bytes) {
+    od_set_error("od_bn_stats: workspace too small");
+    return OD_ERR_WORKSPACE;
+  }
+  float* part = (float*)workspace;
+  hipLaunchKernelGGL((od_chan_reduce<0, OD_ACT_LINEAR>), dim3(p.nblocks), dim3(256), 2 * 256 * 8 * sizeof(float),
+                     (hipStream_t)stream, (const f16*)z, (const f16*)nullptr, nullptr, nullptr, nullptr, nullptr, M, C, 0.f,
+                     p.rw, part);
+  OD_CHECK_LAUNCH();
+  return od_bn_stats_from_partials(ctx, part, p.nblocks, M, C, gamma, beta, eps, mean, rstd, scale, shift, run_mean, run_var,
+                                   momentum, stream);
 }
 
 extern "C" int od_scale_act(od_ctx* ctx, const void* z, const float* scale, const float* shift, const void* res,
@@ -599,11 +598,11 @@ extern "C" int od_scale_act(od_ctx* ctx, const void* z, const float* scale, cons
   OD_REQUIRE(res_mode == OD_RES_NONE || res, "od_scale_act: res_mode set but res is null");
   OD_REQUIRE(C <= 2048, "od_scale_act: C <= 2048");
   const long long M = (long long)B * H * W;
-  const int rw = rows_per_wg(M, C);
+  const int rw = rows_per_wg(M, C, 0);
   OD_ACT_SWITCH(act, hipLaunchKernelGGL(od_scale_act_k<A>, dim3((unsigned)((M + rw - 1) / rw)), dim3(256), 0, (hipStream_t)stream,
                                         (const f16*)z, scale, shift,
-                                        res_mode == OD_RES_NONE ? (const f16*)nullptr : (const f16*)res, (f16*)y, M, C, act,
-                                        alpha, res_mode == OD_RES_UP2, H, W, rw));
+                                        res_mode == OD_RES_NONE ? (const f16*)nullptr : (const f16*)res, (f16*)y, M, C, alpha,
+                                        res_mode == OD_RES_UP2, H, W, rw));
   OD_CHECK_LAUNCH();
   return OD_OK;
 }
@@ -618,32 +617,33 @@ extern "C" int od_bn_bwd(od_ctx* ctx, const void* z, const void* dy, const float
   // conv of a many-class head (Cout = 8 * (NC + 6)), whose dz is dy itself: the reductions loop over any C, the apply is a copy
   const bool wide = C > 2048;
   OD_REQUIRE(!wide || (!bn && act == OD_ACT_LINEAR), "od_bn_bwd: C > 2048 only without BatchNorm and activation");
-  const int rw = rows_per_wg_reduce(M, C), rw_apply = rows_per_wg(M, C);
-  const int nblocks = (int)((M + rw - 1) / rw);
-  const size_t need = od_bn_workspace_bytes(M, C) + 2 * (size_t)C * sizeof(float);
+  const chan_plan p = chan_reduce_plan(M, C);
+  const size_t need = p.partial_bytes + 2 * (size_t)C * sizeof(float);
   if (workspace_bytes < need) {
     od_set_error("od_bn_bwd: workspace %zu < %zu", workspace_bytes, need);
     return OD_ERR_WORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
   float* part = (float*)workspace;
-  float* sums = part + (size_t)nblocks * 2 * C;  // [2][C]: this call's sum(da*xhat), sum(da)
-  // without BN the "mean/rstd" are not used by the sums we need (dbeta only); pass scale/shift twice to keep pointers valid
-  OD_ACT_SWITCH(act, hipLaunchKernelGGL((od_chan_reduce<1, A>), dim3(nblocks), dim3(256), 2 * 256 * 8 * sizeof(float), s,
-                                        (const f16*)z, (const f16*)dy, scale, shift, bn ? mean : shift, bn ? rstd : scale, M,
-                                        C, act, alpha, rw, part));
+  float *sum_dax = part + (size_t)p.nblocks * 2 * C, *sum_da = sum_dax + C;  // this call's sum(da*xhat), sum(da)
+  // without BN neither the sum we need (dbeta) nor dz = da uses mean / rstd, but both kernels load every per-channel
+  // pointer unconditionally (see od_bn_bwd_apply_k): shift / scale stand in so that the pointers stay valid
+  const float *mean_or = bn ? mean : shift, *rstd_or = bn ? rstd : scale;
+  OD_ACT_SWITCH(act, hipLaunchKernelGGL((od_chan_reduce<1, A>), dim3(p.nblocks), dim3(256), 2 * 256 * 8 * sizeof(float), s,
+                                        (const f16*)z, (const f16*)dy, scale, shift, mean_or, rstd_or, M, C, alpha, p.rw,
+                                        part));
   OD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(od_chan_final<1>, dim3(od_ceil_div(C, 8)), dim3(256), 0, s, part, nblocks, C, 0.f, 0.f,
-                     (const float*)nullptr, (const float*)nullptr, dgamma, dbeta, sums, sums + C, (float*)nullptr,
-                     (float*)nullptr, 0.f);
+  hipLaunchKernelGGL(od_bn_bwd_final_k, dim3(od_ceil_div(C, 8)), dim3(256), 0, s, part, p.nblocks, C, dgamma, dbeta, sum_dax,
+                     sum_da);
   OD_CHECK_LAUNCH();
   if (wide) {  // linear, no BatchNorm: dz = (f16)(dy * 1) = dy
     if (dz != dy) OD_CHECK_HIP(hipMemcpyAsync(dz, dy, (size_t)M * C * sizeof(f16), hipMemcpyDeviceToDevice, s));
     return OD_OK;
   }
-  OD_ACT_SWITCH(act, hipLaunchKernelGGL(od_bn_bwd_apply_k<A>, dim3((unsigned)((M + rw_apply - 1) / rw_apply)), dim3(256), 0, s,
-                                        (const f16*)z, (const f16*)dy, scale, shift, bn ? mean : shift, bn ? rstd : scale,
-                                        sums, sums + C, (f16*)dz, M, C, 1.f / (float)M, act, alpha, bn, rw_apply));
+  const int rw = rows_per_wg(M, C, 0);
+  OD_ACT_SWITCH(act, hipLaunchKernelGGL(od_bn_bwd_apply_k<A>, dim3((unsigned)((M + rw - 1) / rw)), dim3(256), 0, s,
+                                        (const f16*)z, (const f16*)dy, scale, shift, mean_or, rstd_or, sum_dax, sum_da,
+                                        (f16*)dz, M, C, 1.f / (float)M, alpha, bn, rw));
   OD_CHECK_LAUNCH();
   return OD_OK;
 }
@@ -758,8 +758,8 @@ extern "C" int od_cast_bf16_f32(od_ctx* ctx, const void* src, float* dst, long l
 
 extern "C" int od_pack_weights_multi(od_ctx* ctx, const float* w, const od_pack_layer* layers, int nlayers, void* stream) {
   OD_REQUIRE(ctx && w && layers && nlayers > 0 && nlayers <= 65535, "od_pack_weights_multi: bad argument");
-  // 1024 x 256 threads per layer: the largest layers (4.7 M weights, transposed 2-byte scatter for the backward pack) need the
-  // parallelism; the blocks of small layers exit after one test
+  // 288 workgroups per layer: the largest layers (4.7 M weights = 1152 tiles) need the parallelism; the blocks of small
+  // layers exit after one test
   hipLaunchKernelGGL(od_pack_multi_k, dim3(288, nlayers), dim3(256), 0, (hipStream_t)stream, w, layers);
   OD_CHECK_LAUNCH();
   return OD_OK;
@@ -768,11 +768,10 @@ extern "C" int od_pack_weights_multi(od_ctx* ctx, const float* w, const od_pack_
 extern "C" int od_pack_weights(od_ctx* ctx, const float* w, void* w_fwd, void* w_bwd, int Cout, int Cin, int ksize,
                                void* stream) {
   OD_REQUIRE(ctx && w && w_fwd && Cout > 0 && Cin > 0 && (ksize == 1 || ksize == 3), "od_pack_weights: bad argument");
-  const int taps = ksize * ksize;
-  const int Kpad = od_round_up(taps * Cin, 64), Kpad_t = od_round_up(taps * Cout, 64);
-  const long long n = (long long)Cout * taps * Cin;
-  hipLaunchKernelGGL(od_pack_w_k, dim3(grid_for((n + 7) / 8)), dim3(256), 0, (hipStream_t)stream, w, (f16*)w_fwd,
-                     (f16*)w_bwd, Cout, Cin, taps, Kpad, Kpad_t);
+  OD_REQUIRE(!w_bwd || Cout % 8 == 0, "od_pack_weights: the backward-data pack needs Cout to be a multiple of 8");
+  OD_REQUIRE((((uintptr_t)w_fwd | (uintptr_t)w_bwd) & 15) == 0, "od_pack_weights: w_fwd / w_bwd must be 16-byte aligned");
+  hipLaunchKernelGGL(od_pack_one_k, dim3(288), dim3(256), 0, (hipStream_t)stream, w, (f16*)w_fwd, (f16*)w_bwd, Cout, Cin,
+                     ksize);
   OD_CHECK_LAUNCH();
   return OD_OK;
 }

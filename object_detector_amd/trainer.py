@@ -602,18 +602,6 @@ class Trainer:
         learning rate too high for the batch size), which no loss scale can cure and a skipped step never changes."""
         return self._consecutive_skips >= self.max_consecutive_skips
 
-    def sgd_per_tensor(self):
-        """Per-tensor form of sgd() (kept for the equality test of the multi-tensor kernels).  UNGUARDED: no non-finite
-        check, no loss-scale update, no restore of the running statistics -- training loops use sgd()."""
-        inv = dp_effective_scale(self.loss_scale, self.world)  # grads are averaged over ranks
-        for (name, kind), (o, n) in self.seg.items():
-            lr = self.lr * lr_multiplier(name, self.lr_multipliers)
-            wd = self.weight_decay if kind == "w" else 0.0
-            _lib.check(self.lib.od_sgd_step(self.ctx.handle, self.params.data_ptr() + 4 * o, self.mom.data_ptr() + 4 * o,
-                                            self.grads.data_ptr() + 4 * o, n, lr, self.momentum, wd, inv, _stream_ptr()),
-                       "od_sgd_step")
-        self._repack_per_layer()
-
     def step(self, x_u8, annotations=None, y_target=None):
         """One training step.  annotations: list[ObjectsAnnotation] (encoded on the device) or y_target [B,P,C]."""
         self._poll_nonfinite()
