@@ -25,7 +25,7 @@
 // (reference voc_validate.py:27; docs/MODEL.md:15-17).
 #include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv_direct.h"
 
 namespace {
 
@@ -46,35 +46,12 @@ struct BneckKP {
   int tiles_x, tiles_y;
 };
 
-template <int CPR>
-static __device__ __forceinline__ int bn_swz(int row) {
-  return CPR == 16 ? ((row & 7) << 1) : (CPR == 8 ? (row & 7) : 3 * ((row >> 2) & 1));
-}
-
-// The activation is a TEMPLATE parameter of the kernels: as a run-time enum tested per element (round 1) the compiler kept
-// the dispatch as control flow inside the unrolled epilogues -- 328 branches and 40 v_exp_f32 in od_bneck<64>, the ELU path
-// with its divergent v > 0 test laid out for every element even when the network only ever asks for LeakyReLU.
-template <int ACT>
-static __device__ __forceinline__ float bn_act(float v, float alpha) {
-  if (ACT == OD_ACT_LEAKY) return od_leaky(v, alpha);
-  if (ACT == OD_ACT_ELU) return v > 0.f ? v : alpha * od_expm1_fast(v);
-  return v;
-}
-
-// buffer-addressed LDS-DMA (resource in SGPRs, per-lane byte offset, scalar byte offset); kept in a plain __device__
-// function: the host pass of hipcc (ROCm 7.2) silently drops a kernel TEMPLATE whose body names the buffer builtins
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t bn_make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-static __device__ __forceinline__ void bn_buffer_dma(__amdgpu_buffer_rsrc_t rs, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
-
 template <int C>
 struct BneckCfg {
   static constexpr int CM = C / 2;
   static constexpr int RBX = 2 * C, RBT = C;          // row bytes of the x window / w1 and of the t window / w3 taps
   static constexpr int CPX = RBX / 16, CPT = RBT / 16;
+  static constexpr od_swz KX = od_swz_block(CPX), KT = od_swz_block(CPT);  // swizzle keys of the two row lengths
   static constexpr int WW = 18, NWP = WW * WW, NWF = 21;  // window: 324 pixels = 21 m-fragments (last one ragged)
   static constexpr int XW_BYTES = NWF * 16 * RBX;
   static constexpr int TW_BYTES = NWP * RBT;
@@ -111,6 +88,7 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
   constexpr bool LOADERS = (C == 64);
   constexpr int CM = Cf::CM, RBX = Cf::RBX, RBT = Cf::RBT, CPX = Cf::CPX, CPT = Cf::CPT, WW = Cf::WW, NWP = Cf::NWP;
   constexpr int NF1 = Cf::NF1, KS1 = Cf::KS1, KS3 = Cf::KS3, NFW = Cf::NFW;
+  constexpr od_swz KX = Cf::KX, KT = Cf::KT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x;
@@ -131,14 +109,12 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
     const int q = r * XWT + xtid;
     const int wp = q / CPX, pc = q - wp * CPX;
     const int wy = wp / WW, wx = wp - wy * WW;
-    xw_rel[r] = ((wy - 1) * p.W + (wx - 1)) * C + (pc ^ bn_swz<CPX>(wp)) * 8;
+    xw_rel[r] = ((wy - 1) * p.W + (wx - 1)) * C + (pc ^ od_swz_key<KX>(wp)) * 8;
     xw_wyx[r] = (q >= 0 && q < NWP * CPX && xtid >= 0) ? ((wy << 8) | wx) : -1;
   }
   auto issue_xwin = [&](int tile, int buf) {
-    const int b = tile / tpi;
-    const int trem = tile - b * tpi;
-    const int tyi = trem / p.tiles_x, txi = trem - tyi * p.tiles_x;
-    const int y0 = tyi * 16, x0 = txi * 16;
+    const od_tile_pos t = od_tile_decode(tile, tpi, p.tiles_x);
+    const int b = t.img, y0 = t.ty * 16, x0 = t.tx * 16;
     const f16* org = p.x + ((long long)(b * p.H + y0) * p.W + x0) * C;
 #pragma unroll
     for (int r = 0; r < XWR; ++r) {
@@ -157,17 +133,17 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
   for (int r = 0; r < TAPR; ++r) {
     const int q = r * 512 + tid;
     const int n = q / CPT, pc = q - n * CPT;
-    tap_voff[r] = q < C * CPT ? (n * p.k3stride + (pc ^ bn_swz<CPT>(n)) * 8) * 2 : (int)0x80000000;
+    tap_voff[r] = q < C * CPT ? (n * p.k3stride + (pc ^ od_swz_key<KT>(n)) * 8) * 2 : (int)0x80000000;
   }
-  const __amdgpu_buffer_rsrc_t rs_w3 = bn_make_rsrc(p.w3, 256u * (unsigned)p.k3stride * 2u);
+  const __amdgpu_buffer_rsrc_t rs_w3 = od_buffer_rsrc(p.w3, 256u * (unsigned)p.k3stride * 2u);
   auto load_tap = [&](int tap, int dst_off) {
 #pragma unroll
     for (int r = 0; r < TAPR; ++r) {
       char* dst = smem + dst_off + (r * 512 + wave * 64) * 16;
       if ((r + 1) * 512 <= C * CPT) {  // compile-time: every lane of every wave takes part
-        bn_buffer_dma(rs_w3, tap_voff[r], tap * CM * 2, dst);
+        od_buffer_dma16(rs_w3, tap_voff[r], tap * CM * 2, dst);
       } else if (r * 512 + wave * 64 < C * CPT) {  // ragged last round: whole waves drop out (C * CPT % 64 == 0)
-        bn_buffer_dma(rs_w3, tap_voff[r], tap * CM * 2, dst);
+        od_buffer_dma16(rs_w3, tap_voff[r], tap * CM * 2, dst);
       }
     }
   };
@@ -198,7 +174,7 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
   for (int q = tid; q < CM * CPX + 63; q += 512) {
     if (q < CM * CPX) {
       const int n = q / CPX, pc = q - n * CPX;
-      const int lc = pc ^ bn_swz<CPX>(n);
+      const int lc = pc ^ od_swz_key<KX>(n);
       glds16(p.w1 + (long long)n * p.k1stride + lc * 8, smem + Cf::OFF_W1 + (q - lane) * 16);
     }
   }
@@ -218,16 +194,14 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
 #pragma unroll
     for (int ks = 0; ks < KS3; ++ks) {
       const int row = (wn * NFW + j) * 16 + l15;
-      boff[j][ks] = row * RBT + (((ks * 4 + lq) ^ bn_swz<CPT>(row)) * 16);
+      boff[j][ks] = row * RBT + (((ks * 4 + lq) ^ od_swz_key<KT>(row)) * 16);
     }
 
   int cur = 0;
 #pragma unroll 1
   for (; tile < ntiles; tile += (int)gridDim.x) {
-    const int b = tile / tpi;
-    const int trem = tile - b * tpi;
-    const int tyi = trem / p.tiles_x, txi = trem - tyi * p.tiles_x;
-    const int y0 = tyi * 16, x0 = txi * 16;
+    const od_tile_pos t = od_tile_decode(tile, tpi, p.tiles_x);
+    const int b = t.img, y0 = t.ty * 16, x0 = t.tx * 16;
     const char* xw = smem + Cf::OFF_XW + cur * Cf::XW_BYTES;
 
     // ---- producer: t window ---------------------------------------------------------------------------------
@@ -239,7 +213,7 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
   #pragma unroll
       for (int ks = 0; ks < KS1; ++ks) {
         const int row = j * 16 + l15;
-        wb1[j][ks] = *(const f16x8*)(smem + Cf::OFF_W1 + row * RBX + (((ks * 4 + lq) ^ bn_swz<CPX>(row)) * 16));
+        wb1[j][ks] = *(const f16x8*)(smem + Cf::OFF_W1 + row * RBX + (((ks * 4 + lq) ^ od_swz_key<KX>(row)) * 16));
       }
     float sc1[NF1][4], bi1[NF1][4];
   #pragma unroll
@@ -259,7 +233,7 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
         for (int j = 0; j < NF1; ++j) acc1[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) {
-          const f16x8 xa = *(const f16x8*)(xw + wp * RBX + (((ks * 4 + lq) ^ bn_swz<CPX>(wp)) * 16));
+          const f16x8 xa = *(const f16x8*)(xw + wp * RBX + (((ks * 4 + lq) ^ od_swz_key<KX>(wp)) * 16));
   #pragma unroll
           for (int j = 0; j < NF1; ++j) acc1[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb1[j][ks], xa, acc1[j], 0, 0, 0);
         }
@@ -271,11 +245,11 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
             f16x4 h;
   #pragma unroll
             for (int e = 0; e < 4; ++e) {
-              const float v = bn_act<ACT>(acc1[j][e] * sc1[j][e] + bi1[j][e], p.alpha);
+              const float v = od_act<ACT>(acc1[j][e] * sc1[j][e] + bi1[j][e], p.alpha);
               h[e] = inside ? (f16)v : (f16)0.f;
             }
             const int lc = j * 2 + (lq >> 1);
-            *(f16x4*)(smem + Cf::OFF_TW + wp * RBT + ((lc ^ bn_swz<CPT>(wp)) * 16) + (lq & 1) * 8) = h;
+            *(f16x4*)(smem + Cf::OFF_TW + wp * RBT + ((lc ^ od_swz_key<KT>(wp)) * 16) + (lq & 1) * 8) = h;
           }
         }
       }
@@ -287,11 +261,11 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
     if (!Cf::RESIDENT) {
 #pragma unroll
       for (int pr = 0; pr < NFW / 2; ++pr) {
-        const int ch = (wn * NFW + 2 * pr + (lq & 1)) * 16 + (lq >> 1) * 8;
+        const int ch = OD_LANE_CH8_AT(lq, wn * NFW + 2 * pr);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int wrow = (wm * 4 + i + 1) * WW + 1 + l15;
-          resv[pr][i] = *(const f16x8*)(xw + wrow * RBX + (((ch >> 3) ^ bn_swz<CPX>(wrow)) * 16));
+          resv[pr][i] = *(const f16x8*)(xw + wrow * RBX + (((ch >> 3) ^ od_swz_key<KX>(wrow)) * 16));
         }
       }
     }
@@ -320,7 +294,7 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
         const int wrow = (wm * 4 + k) * WW + dx + l15;
 #pragma unroll
         for (int ks = 0; ks < KS3; ++ks)
-          xa[k][ks] = *(const f16x8*)(smem + Cf::OFF_TW + wrow * RBT + (((ks * 4 + lq) ^ bn_swz<CPT>(wrow)) * 16));
+          xa[k][ks] = *(const f16x8*)(smem + Cf::OFF_TW + wrow * RBT + (((ks * 4 + lq) ^ od_swz_key<KT>(wrow)) * 16));
       }
     };
     auto do_tap = [&](int dy, int wbase) {
@@ -384,7 +358,7 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
     // ---- epilogue: 8 consecutive channels per lane (permlane16 swap of a fragment pair) + residual ----------------
 #pragma unroll
     for (int pr = 0; pr < NFW / 2; ++pr) {
-      const int ch = (wn * NFW + 2 * pr + (lq & 1)) * 16 + (lq >> 1) * 8;
+      const int ch = OD_LANE_CH8_AT(lq, wn * NFW + 2 * pr);
       float sc[8], bi[8];
       {
         const f32x4 s0 = *(const f32x4*)(p.s3 + ch), s1 = *(const f32x4*)(p.s3 + ch + 4);
@@ -403,21 +377,15 @@ __global__ __launch_bounds__(C == 64 ? 768 : 512, C == 64 ? 3 : 2) void od_bneck
         f16x8 r;
         if (Cf::RESIDENT) {
           const int wrow = (ty + 1) * WW + 1 + l15;  // centre pixel of the x window
-          r = *(const f16x8*)(xw + wrow * RBX + (((ch >> 3) ^ bn_swz<CPX>(wrow)) * 16));
+          r = *(const f16x8*)(xw + wrow * RBX + (((ch >> 3) ^ od_swz_key<KX>(wrow)) * 16));
         } else {
           r = resv[pr][i];
         }
         float v[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float a = acc[i][2 * pr][e], bq = acc[i][2 * pr + 1][e];
-          od_permlane16_swap(a, bq);
-          v[e] = a;
-          v[4 + e] = bq;
-        }
+        od_pair_row8(acc[i][2 * pr], acc[i][2 * pr + 1], v);
         f16x8 h;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) h[e] = (f16)(bn_act<ACT>(v[e] * sc[e] + bi[e], p.alpha) + (float)r[e]);
+        for (int e = 0; e < 8; ++e) h[e] = (f16)(od_act<ACT>(v[e] * sc[e] + bi[e], p.alpha) + (float)r[e]);
         *(f16x8*)(p.out + ((long long)(b * p.H + y0 + ty) * p.W + x0 + l15) * C + ch) = h;
       }
     }
@@ -466,21 +434,14 @@ int od_bottleneck_prepare(od_ctx* ctx, const od_bneck_desc* d, od_launches* L) {
   p.tiles_x = d->W / 16;
   p.tiles_y = d->H / 16;
   static_assert(OD_ACT_LINEAR == 0 && OD_ACT_LEAKY == 1 && OD_ACT_ELU == 2, "kernel table order");
-#define OD_BN(C, ACT) {(const void*)&od_bneck<C, ACT>, "od_bneck<" #C ", " #ACT ">"}
-  static const struct {
-    const void* fn;
-    const char* name;
-  } kernels[2][3] = {{OD_BN(64, 0), OD_BN(64, 1), OD_BN(64, 2)}, {OD_BN(128, 0), OD_BN(128, 1), OD_BN(128, 2)}};
+#define OD_BN(C, ACT) \
+  {(const void*)&od_bneck<C, ACT>, "od_bneck<" #C ", " #ACT ">", 0, 0, 0, C == 64 ? 768 : 512, (size_t)BneckCfg<C>::LDS_BYTES}
+  static const ConvKernelInfo kernels[2][3] = {{OD_BN(64, 0), OD_BN(64, 1), OD_BN(64, 2)}, {OD_BN(128, 0), OD_BN(128, 1), OD_BN(128, 2)}};
 #undef OD_BN
-  const auto& k = kernels[d->C == 128][d->act];
-  const int lds = d->C == 64 ? BneckCfg<64>::LDS_BYTES : BneckCfg<128>::LDS_BYTES;
-  if (int rc = od_ensure_lds(ctx, k.fn, (size_t)lds)) return rc;
   const int ntiles = d->B * p.tiles_x * p.tiles_y;
   // C = 64: persistent workgroups (one per CU) walk the tiles; C = 128: one workgroup per tile
-  const int cus = ctx->num_cu;
-  const int grid = d->C == 64 ? (ntiles < cus ? ntiles : cus) : ntiles;
-  return od_add_launch(L, {k.name, od_issue_kp_int<BneckKP>, k.fn, dim3((unsigned)grid), dim3(d->C == 64 ? 768 : 512), (size_t)lds},
-                       od_kp_int<BneckKP>{p, ntiles});
+  const int grid = d->C == 64 ? od_persistent_grid(1, ctx->num_cu, ntiles) : ntiles;
+  return od_direct_launch(ctx, L, kernels[d->C == 128][d->act], grid, p, ntiles);
 }
 
 extern "C" int od_bottleneck_fwd(od_ctx* ctx, const od_bneck_desc* d, void* stream) {

@@ -15,7 +15,7 @@
 // voc_validate.py:27; docs/MODEL.md:15-17) and the same layers' forward in training.
 #include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv_direct.h"
 
 namespace {
 
@@ -32,13 +32,6 @@ struct RdKP {
   int segs_per_row, nitems;
 };
 
-// 16-byte chunk swizzle of a weight row: 128-B and longer rows XOR the low 3 chunk bits with the row's low 3 bits, 64-B rows
-// (4 chunks) with bits 1-2 of the row; every fragment read (16 consecutive rows, one chunk column) is then conflict-free
-template <int CH>
-__device__ __forceinline__ int rd_swz(int chunk, int row) {
-  return CH >= 8 ? ((chunk & ~7) | ((chunk ^ row) & 7)) : (chunk ^ ((row >> 1) & 3));
-}
-
 // KS = 3: the 3x3 layer described above.  KS = 1: the pointwise layers of the 160x160 / 80x80 maps in training (weights
 // <= 16 KiB, a pixel is loaded exactly once): pure streams that the table kernels run at 60-75 % of what HBM gives.
 template <int KC, int NC, int S, int KS>
@@ -49,24 +42,14 @@ __global__ __launch_bounds__(512, 2) void od_conv_rdirect(RdKP p) {
   constexpr int NF = NC / 16;              // output-channel fragments
   constexpr int TAPS = KS * KS, PAD = KS / 2;
   constexpr int WROWS = TAPS * NC;
+  constexpr od_swz KEY = od_swz_stream(CH);
   extern __shared__ __attribute__((aligned(16))) char wlds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lq = lane >> 4;
 
-  // ---- all weights -> LDS: row r = tap*NC + n, chunk c stored at c ^ (r & 7) (low 3 bits) -----------------------------
-  {
-    constexpr int LPR = CH;                 // lanes per row in a 1-KiB piece
-    constexpr int RPP = 64 / LPR;           // rows per piece
-    constexpr int PIECES = (WROWS + RPP - 1) / RPP;  // 144 (3x3, KC = 64, NC = 128)
-    for (int q = wave; q < PIECES; q += 8) {
-      int r = q * RPP + lane / LPR;
-      if (r >= WROWS) r = WROWS - 1;  // (a last, partial piece re-writes the last row with itself)
-      const int tap = r / NC, n = r - tap * NC;
-      const int lc = rd_swz<CH>(lane % LPR, r);
-      glds16(p.w + ((long long)n * p.Kstride + tap * KC + lc * 8), wlds + q * 1024);
-    }
-  }
+  // all weights -> LDS (144 pieces for 3x3, KC = 64, NC = 128; the pointwise forms may end in a partial piece)
+  for (int q = wave; q < od_weight_pieces<WROWS, ROWB>(); q += 8) od_weight_piece_to_lds<WROWS, ROWB, NC, KEY>(p.w, p.Kstride, wlds, q, lane);
 
   // this lane's operand loads of one item: pixel (oy*S + dy - 1, (ox0 + l15)*S + dx - 1), channels kh*32 + lq*8 .. +7
   auto load_item = [&](int item, f16x8 (&xs)[TAPS][KH]) {
@@ -91,7 +74,7 @@ __global__ __launch_bounds__(512, 2) void od_conv_rdirect(RdKP p) {
     }
   };
 
-  const int n8 = (lq & 1) * 16 + (lq >> 1) * 8;  // this lane's 8 channels inside a 32-channel store group
+  const int n8 = OD_LANE_CH8(lq);  // this lane's 8 channels inside a 32-channel store group
   const int gw = blockIdx.x * 8 + wave, nw = gridDim.x * 8;
   f16x8 xa[TAPS][KH], xb[TAPS][KH];
   int item = gw;
@@ -109,7 +92,7 @@ __global__ __launch_bounds__(512, 2) void od_conv_rdirect(RdKP p) {
   // chunk kh*4 + lq
   int fwk[KH];
 #pragma unroll
-  for (int kh = 0; kh < KH; ++kh) fwk[kh] = l15 * ROWB + rd_swz<CH>(kh * 4 + lq, l15) * 16;
+  for (int kh = 0; kh < KH; ++kh) fwk[kh] = l15 * ROWB + od_swz_chunk<KEY>(kh * 4 + lq, l15) * 16;
 
   auto compute_store = [&](int it, f16x8 (&xs)[TAPS][KH]) {
     f32x4 acc[NF];
@@ -136,27 +119,9 @@ __global__ __launch_bounds__(512, 2) void od_conv_rdirect(RdKP p) {
 #pragma unroll
     for (int s = 0; s < NC / 32; ++s) {
       float o[8];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float a = acc[2 * s][e], b = acc[2 * s + 1][e];
-        od_permlane16_swap(a, b);
-        o[e] = a;
-        o[4 + e] = b;
-      }
-      const f32x4 s0 = *(const f32x4*)(sb + s * 32 + n8), s1 = *(const f32x4*)(sb + s * 32 + n8 + 4);
-      const f32x4 b0 = *(const f32x4*)(sb + NC + s * 32 + n8), b1 = *(const f32x4*)(sb + NC + s * 32 + n8 + 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[e] = o[e] * s0[e] + b0[e];
-        o[4 + e] = o[4 + e] * s1[e] + b1[e];
-      }
-      if (p.act == OD_ACT_LEAKY) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = od_leaky(o[e], p.alpha);
-      } else if (p.act == OD_ACT_ELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = o[e] > 0.f ? o[e] : p.alpha * od_expm1_fast(o[e]);
-      }
+      od_pair_row8(acc[2 * s], acc[2 * s + 1], o);
+      od_scale_bias8(o, sb + s * 32 + n8, sb + NC + s * 32 + n8);
+      od_act_rt(o, p.act, p.alpha);
       if (p.res) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] += (float)rv[s][e];
@@ -188,19 +153,12 @@ __global__ __launch_bounds__(512, 2) void od_conv_rdirect(RdKP p) {
 template <int KC, int NC>
 __global__ __launch_bounds__(512, 2) void od_tconv_rdirect(RdKP p) {
   constexpr int ROWB = KC * 2, CH = ROWB / 16, KH = KC / 32, NF = NC / 16, WROWS = 9 * NC;
+  constexpr od_swz KEY = od_swz_stream(CH);
   extern __shared__ __attribute__((aligned(16))) char wlds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lq = lane >> 4;
-  {
-    constexpr int LPR = CH, RPP = 64 / LPR, PIECES = WROWS / RPP;
-    for (int q = wave; q < PIECES; q += 8) {
-      const int r = q * RPP + lane / LPR;
-      const int tap = r / NC, n = r - tap * NC;
-      const int lc = rd_swz<CH>(lane % LPR, r);
-      glds16(p.w + ((long long)n * p.Kstride + tap * KC + lc * 8), wlds + q * 1024);
-    }
-  }
+  for (int q = wave; q < od_weight_pieces<WROWS, ROWB>(); q += 8) od_weight_piece_to_lds<WROWS, ROWB, NC, KEY>(p.w, p.Kstride, wlds, q, lane);
   // here p.H / p.W are the dZ map (Hs, Ws), p.Ho / p.Wo the output map (2Hs, 2Ws); an item = (dZ row, 16-pixel segment)
   auto load_item = [&](int item, f16x8 (&xs)[4][KH]) {
     const int row = item / p.segs_per_row, j0 = (item - row * p.segs_per_row) * 16;
@@ -220,7 +178,7 @@ __global__ __launch_bounds__(512, 2) void od_tconv_rdirect(RdKP p) {
         }
       }
   };
-  const int n8 = (lq & 1) * 16 + (lq >> 1) * 8;
+  const int n8 = OD_LANE_CH8(lq);
   const int gw = blockIdx.x * 8 + wave, nw = gridDim.x * 8;
   f16x8 xa[4][KH], xb[4][KH];
   int item = gw;
@@ -234,7 +192,7 @@ __global__ __launch_bounds__(512, 2) void od_tconv_rdirect(RdKP p) {
   __syncthreads();
   int fwk[KH];
 #pragma unroll
-  for (int kh = 0; kh < KH; ++kh) fwk[kh] = l15 * ROWB + rd_swz<CH>(kh * 4 + lq, l15) * 16;
+  for (int kh = 0; kh < KH; ++kh) fwk[kh] = l15 * ROWB + od_swz_chunk<KEY>(kh * 4 + lq, l15) * 16;
 
   auto compute_store = [&](int it, f16x8 (&xs)[4][KH]) {
     const int row = it / p.segs_per_row, j0 = (it - row * p.segs_per_row) * 16;
@@ -264,31 +222,13 @@ __global__ __launch_bounds__(512, 2) void od_tconv_rdirect(RdKP p) {
 #pragma unroll
       for (int s = 0; s < NC / 32; ++s) {
         float o[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float a = acc[2 * s][e], bq = acc[2 * s + 1][e];
-          od_permlane16_swap(a, bq);
-          o[e] = a;
-          o[4 + e] = bq;
-        }
-        const f32x4 s0 = *(const f32x4*)(sb + s * 32 + n8), s1 = *(const f32x4*)(sb + s * 32 + n8 + 4);
-        const f32x4 b0 = *(const f32x4*)(sb + NC + s * 32 + n8), b1 = *(const f32x4*)(sb + NC + s * 32 + n8 + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          o[e] = o[e] * s0[e] + b0[e];
-          o[4 + e] = o[4 + e] * s1[e] + b1[e];
-        }
-        if (p.act == OD_ACT_LEAKY) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = od_leaky(o[e], p.alpha);
-        } else if (p.act == OD_ACT_ELU) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = o[e] > 0.f ? o[e] : p.alpha * od_expm1_fast(o[e]);
-        }
+        od_pair_row8(acc[2 * s], acc[2 * s + 1], o);
+        od_scale_bias8(o, sb + s * 32 + n8, sb + NC + s * 32 + n8);
+        od_act_rt(o, p.act, p.alpha);
         if (p.res) {
-          const f16x8 rv = *(const f16x8*)(p.res + ooff + s * 32);
+          const f16x8 rvv = *(const f16x8*)(p.res + ooff + s * 32);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] += (float)rv[e];
+          for (int e = 0; e < 8; ++e) o[e] += (float)rvv[e];
         }
         f16x8 h;
 #pragma unroll
@@ -309,28 +249,19 @@ __global__ __launch_bounds__(512, 2) void od_tconv_rdirect(RdKP p) {
   }
 }
 
-struct RdEntry {
-  int kc, nc, stride, ks;
-  const void* fn;
-  const char* name;
-  size_t lds;
-};
-#define OD_RD1(KC, NC) \
-  { KC, NC, 1, 1, (const void*)&od_conv_rdirect<KC, NC, 1, 1>, "od_conv_rdirect<" #KC ", " #NC ", 1, 1>", (size_t)NC * KC * 2 + 1024 }
-const RdEntry g_rd[] = {
-    {64, 128, 2, 3, (const void*)&od_conv_rdirect<64, 128, 2, 3>, "od_conv_rdirect<64, 128, 2, 3>", (size_t)9 * 128 * 128 + 1024},
+// (LDS: the weights and 1 KiB of scale / bias)
+#define OD_RD(KC, NC, S, KS) \
+  { KC, NC, S, KS, {(const void*)&od_conv_rdirect<KC, NC, S, KS>, "od_conv_rdirect<" #KC ", " #NC ", " #S ", " #KS ">", 0, 0, 0, 512, (size_t)KS * KS * NC * KC * 2 + 1024} }
+#define OD_RD1(KC, NC) OD_RD(KC, NC, 1, 1)
+const DirectKernel g_rd[] = {
+    OD_RD(64, 128, 2, 3),
     OD_RD1(64, 32), OD_RD1(32, 64), OD_RD1(128, 64), OD_RD1(64, 128),  // the pointwise layers of stages 1-2 (training)
     // (stride 1 -- b.s2.*.b in training -- is instantiable but not offered: there every pixel is loaded nine times and the
     //  kernel is L1-bound, 60-63 us against 58-59 us on the table kernel; stride 2 loads a pixel 2.25 times: 76 -> 54 us)
 };
-const RdEntry g_rdt = {128, 64, 2, 3, (const void*)&od_tconv_rdirect<128, 64>, "od_tconv_rdirect<128, 64>",
-                       (size_t)9 * 64 * 256 + 1024};
-const RdEntry* rd_find(const od_conv_desc* d) {
-  if (d->transposed) return (d->Cin == 128 && d->Cout == 64 && d->ksize == 3 && d->stride == 2) ? &g_rdt : nullptr;
-  for (const RdEntry& e : g_rd)
-    if (e.kc == d->Cin && e.nc == d->Cout && e.stride == d->stride && e.ks == d->ksize) return &e;
-  return nullptr;
-}
+const DirectKernel g_rdt[] = {
+    {128, 64, 2, 3, {(const void*)&od_tconv_rdirect<128, 64>, "od_tconv_rdirect<128, 64>", 0, 0, 0, 512, (size_t)9 * 64 * 256 + 1024}}};
+const DirectKernel* rd_find(const od_conv_desc* d) { return d->transposed ? od_direct_find(g_rdt, d) : od_direct_find(g_rd, d); }
 
 }  // namespace
 
@@ -348,7 +279,7 @@ bool od_conv_rdirect_supported(const od_conv_desc* d) {
 }
 
 int od_conv_rdirect_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) {
-  const RdEntry* e = rd_find(d);
+  const DirectKernel* e = rd_find(d);
   if (!e) return OD_ERR_INVALID;
   RdKP p;
   p.x = (const f16*)d->x;
@@ -366,9 +297,7 @@ int od_conv_rdirect_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) 
   p.alpha = d->alpha;
   p.segs_per_row = (d->transposed ? d->W : p.Wo) / 16;
   p.nitems = d->B * (d->transposed ? d->H : p.Ho) * p.segs_per_row;
-  const int cus = ctx->num_cu;
-  int grid = d->ksize == 1 ? 2 * cus : cus;  // (the 3x3 form holds 147 KiB of LDS: one workgroup per CU)
-  if (grid * 8 > p.nitems) grid = od_ceil_div(p.nitems, 8);
-  if (int rc = od_ensure_lds(ctx, e->fn, e->lds)) return rc;
-  return od_add_launch(L, {e->name, od_issue_kp, e->fn, dim3(grid), dim3(512), e->lds}, p);
+  // one workgroup per CU for the 3x3 forms (147 KiB of LDS), two for the pointwise forms; a wave needs an item
+  const int grid = od_persistent_grid(d->ksize == 1 ? 2 : 1, ctx->num_cu, od_ceil_div(p.nitems, 8));
+  return od_direct_launch(ctx, L, e->k, grid, p);
 }

@@ -23,7 +23,7 @@
 // Same rounding points as od_conv_first_fwd + od_conv2d_fwd.
 // Replaces the preprocess + first two Conv2D/BatchNormalization/LeakyReLU layers of `ObjectDetector.predict`
 // (reference voc_validate.py:27; docs/MODEL.md:15-17).
-#include "conv_common.h"
+#include "conv_direct.h"
 
 namespace {
 
@@ -58,22 +58,7 @@ constexpr int S_OFF_U = 0, S_OFF_T = 2 * S_UBYTES, S_OFF_W3 = S_OFF_T + S_TBYTES
 constexpr int S_LDS = S_OFF_W3 + 9 * S_W3TAP;  // 118656
 constexpr int S_UROUNDS = (S_UW * S_UW * 3 + 511) / 512;  // byte loads per thread per window
 
-static __device__ __forceinline__ int s_swz(int row) { return 3 * ((row >> 2) & 1); }
-
-// compile-time activation: see conv_bneck.hip bn_act (405 branches and 48 v_exp_f32 in the run-time-enum form of od_stem)
-template <int ACT>
-static __device__ __forceinline__ float s_act(float v, float alpha) {
-  if (ACT == OD_ACT_LEAKY) return od_leaky(v, alpha);
-  if (ACT == OD_ACT_ELU) return v > 0.f ? v : alpha * od_expm1_fast(v);
-  return v;
-}
-
-static __device__ __forceinline__ __amdgpu_buffer_rsrc_t s_make_rsrc(const void* base, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)bytes, 0x00020000);
-}
-static __device__ __forceinline__ void s_buffer_dma(__amdgpu_buffer_rsrc_t rs, int voff, int soff, char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
-}
+constexpr od_swz S_KEY = od_swz_block(4);  // 64-byte rows: the first-layer window and the 3x3 weight taps
 
 template <int ACT = OD_ACT_LEAKY>
 __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
@@ -90,12 +75,12 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
   // ---- once per workgroup --------------------------------------------------------------------------------------
   // 3x3 weights: 9 taps x 64 rows x 64 B, chunk-swizzled, buffer-addressed LDS-DMA (whole waves drop out: 256 chunks)
   {
-    const __amdgpu_buffer_rsrc_t rs_w3 = s_make_rsrc(p.w3, 256u * (unsigned)p.k3stride * 2u);
+    const __amdgpu_buffer_rsrc_t rs_w3 = od_buffer_rsrc(p.w3, 256u * (unsigned)p.k3stride * 2u);
     const int n = tid >> 2, pc = tid & 3;
-    const int voff = (n * p.k3stride + (pc ^ s_swz(n)) * 8) * 2;
+    const int voff = (n * p.k3stride + (pc ^ od_swz_key<S_KEY>(n)) * 8) * 2;
     if (tid < 256) {
 #pragma unroll 1
-      for (int tap = 0; tap < 9; ++tap) s_buffer_dma(rs_w3, voff, tap * 64, smem + S_OFF_W3 + tap * S_W3TAP + wave * 1024);
+      for (int tap = 0; tap < 9; ++tap) od_buffer_dma16(rs_w3, voff, tap * 64, smem + S_OFF_W3 + tap * S_W3TAP + wave * 1024);
     }
   }
   // input windows: the 4th f16 of every pixel stays the zero that k = tap*4 + 3 of the A fragment reads
@@ -113,10 +98,8 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
   }
   uint8_t ubuf[S_UROUNDS];
   auto fetch_u = [&](int t) {  // global -> registers
-    const int b = t / tpi;
-    const int trem = t - b * tpi;
-    const int tyi = trem / p.tiles_x, txi = trem - tyi * p.tiles_x;
-    const int gy0 = tyi * 32 - 2, gx0 = txi * 32 - 2;
+    const od_tile_pos tp = od_tile_decode(t, tpi, p.tiles_x);
+    const int b = tp.img, gy0 = tp.ty * 32 - 2, gx0 = tp.tx * 32 - 2;
     const uint8_t* xb = p.x + (long long)b * p.H * p.W * 3;
 #pragma unroll
     for (int r = 0; r < S_UROUNDS; ++r) {
@@ -162,7 +145,7 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int row = (wn * 2 + j) * 16 + l15;
-    boff[j] = row * 64 + ((lq ^ s_swz(row)) * 16);
+    boff[j] = row * 64 + ((lq ^ od_swz_key<S_KEY>(row)) * 16);
   }
 
   __syncthreads();  // zero fill done before the first window bytes land
@@ -174,10 +157,8 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
   int cur = 0;
 #pragma unroll 1
   for (; tile < ntiles; tile += (int)gridDim.x) {
-    const int b = tile / tpi;
-    const int trem = tile - b * tpi;
-    const int tyi = trem / p.tiles_x, txi = trem - tyi * p.tiles_x;
-    const int y0 = tyi * 16, x0 = txi * 16;  // output tile origin
+    const od_tile_pos tp = od_tile_decode(tile, tpi, p.tiles_x);
+    const int b = tp.img, y0 = tp.ty * 16, x0 = tp.tx * 16;  // output tile origin
     const char* uw = smem + S_OFF_U + cur * S_UBYTES;
 
     // ---- producer: the 33x33 window of first-layer pixels ----------------------------------------------------------
@@ -212,13 +193,13 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
         f16x8 h;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float v0 = s_act<ACT>(a0[e] * sc0[e] + bi0[e], p.alpha);
-          const float v1 = s_act<ACT>(a1[e] * sc0[4 + e] + bi0[4 + e], p.alpha);
+          const float v0 = od_act<ACT>(a0[e] * sc0[e] + bi0[e], p.alpha);
+          const float v1 = od_act<ACT>(a1[e] * sc0[4 + e] + bi0[4 + e], p.alpha);
           h[e] = inside ? (f16)v0 : (f16)0.f;
           h[4 + e] = inside ? (f16)v1 : (f16)0.f;
         }
         const int trow = wy * S_TROW + (wx & 1) * 17 + (wx >> 1);  // de-interleaved columns
-        *(f16x8*)(smem + S_OFF_T + trow * 64 + ((lq ^ s_swz(trow)) * 16)) = h;
+        *(f16x8*)(smem + S_OFF_T + trow * 64 + ((lq ^ od_swz_key<S_KEY>(trow)) * 16)) = h;
       }
     };
 #pragma unroll 1
@@ -251,7 +232,7 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
 #pragma unroll
       for (int k = 0; k < 9; ++k) {
         const int trow = (8 * wm + k) * S_TROW + (dx & 1) * 17 + (dx >> 1) + l15;
-        xa[k] = *(const f16x8*)(smem + S_OFF_T + trow * 64 + ((lq ^ s_swz(trow)) * 16));
+        xa[k] = *(const f16x8*)(smem + S_OFF_T + trow * 64 + ((lq ^ od_swz_key<S_KEY>(trow)) * 16));
       }
 #pragma unroll
       for (int dy = 0; dy < 3; ++dy) {
@@ -269,7 +250,7 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
     // ---- epilogue ---------------------------------------------------------------------------------------------
     od_mfma_results_ready();
     {
-      const int ch = (wn * 2 + (lq & 1)) * 16 + (lq >> 1) * 8;
+      const int ch = OD_LANE_CH8_AT(lq, wn * 2);
       float sc[8], bi[8];
       const f32x4 q0 = *(const f32x4*)(p.s3 + ch), q1 = *(const f32x4*)(p.s3 + ch + 4);
       const f32x4 r0 = *(const f32x4*)(p.b3 + ch), r1 = *(const f32x4*)(p.b3 + ch + 4);
@@ -285,16 +266,10 @@ __global__ __launch_bounds__(512, 2) void od_stem_k(StemKP p, int ntiles) {
       for (int i = 0; i < 4; ++i) {
         const int ty = wm * 4 + i;
         float v[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float a = acc[i][0][e], bq = acc[i][1][e];
-          od_permlane16_swap(a, bq);
-          v[e] = a;
-          v[4 + e] = bq;
-        }
+        od_pair_row8(acc[i][0], acc[i][1], v);
         f16x8 h;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) h[e] = (f16)s_act<ACT>(v[e] * sc[e] + bi[e], p.alpha);
+        for (int e = 0; e < 8; ++e) h[e] = (f16)od_act<ACT>(v[e] * sc[e] + bi[e], p.alpha);
         *(f16x8*)(p.out + ((long long)(b * Ho + y0 + ty) * Wo + x0 + l15) * 64 + ch) = h;
       }
     }
@@ -333,19 +308,11 @@ int od_stem_prepare(od_ctx* ctx, const od_stem_desc* d, od_launches* L) {
   p.tiles_x = d->W / 32;
   p.tiles_y = d->H / 32;
   const int ntiles = d->B * p.tiles_x * p.tiles_y;
-  const int cus = ctx->num_cu;
-  const int grid = ntiles < cus ? ntiles : cus;
   static_assert(OD_ACT_LINEAR == 0 && OD_ACT_LEAKY == 1 && OD_ACT_ELU == 2, "kernel table order");
-#define OD_STEM(ACT) {(const void*)&od_stem_k<ACT>, "od_stem_k<" #ACT ">"}
-  static const struct {
-    const void* fn;
-    const char* name;
-  } kernels[3] = {OD_STEM(0), OD_STEM(1), OD_STEM(2)};
+#define OD_STEM(ACT) {(const void*)&od_stem_k<ACT>, "od_stem_k<" #ACT ">", 0, 0, 0, 512, (size_t)S_LDS}
+  static const ConvKernelInfo kernels[3] = {OD_STEM(0), OD_STEM(1), OD_STEM(2)};
 #undef OD_STEM
-  const auto& k = kernels[d->act];
-  if (int rc = od_ensure_lds(ctx, k.fn, (size_t)S_LDS)) return rc;
-  return od_add_launch(L, {k.name, od_issue_kp_int<StemKP>, k.fn, dim3((unsigned)grid), dim3(512), (size_t)S_LDS},
-                       od_kp_int<StemKP>{p, ntiles});
+  return od_direct_launch(ctx, L, kernels[d->act], od_persistent_grid(1, ctx->num_cu, ntiles), p, ntiles);  // one workgroup per CU
 }
 
 extern "C" int od_stem_fwd(od_ctx* ctx, const od_stem_desc* d, void* stream) {

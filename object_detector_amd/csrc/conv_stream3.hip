@@ -11,7 +11,7 @@
 //
 // Replaces the Conv2D (+ BatchNormalization + activation) layers `b.down1`, `b.s1.0.b` of the reference's network
 // (docs/MODEL.md:15-17) in the layer-by-layer plans, and their input-gradient halves in training.
-#include "conv_common.h"
+#include "conv_direct.h"
 
 namespace {
 
@@ -43,14 +43,8 @@ struct S3Cfg {
   // window ring: three buffers (two tiles ahead) where two workgroups still fit a CU's 160 KiB, else two (one ahead)
   static constexpr int NBUF = (WBYTES + 3 * SLOTS * PXB) * 2 <= 160 * 1024 ? 3 : 2;
   static constexpr int LDS = WBYTES + NBUF * SLOTS * PXB;
+  static constexpr od_swz KEY = od_swz_stream(CH);                  // pixel rows and weight rows alike
 };
-
-// 16-byte chunk swizzle inside a pixel row: 128-B rows (8 chunks) XOR the row's low 3 bits, 64-B rows (4 chunks) XOR bits
-// 1-2 of the row (two rows share a 128-B bank line) -- the 16 consecutive rows a fragment read touches then cover all banks
-template <int CH>
-__device__ __forceinline__ int s3_key(int row) {
-  return CH == 8 ? (row & 7) : ((row >> 1) & 3);
-}
 
 template <int KC, int NC, int S>
 __global__ __launch_bounds__(256, 2) void od_conv_stream3(Stream3KP p) {
@@ -66,25 +60,19 @@ __global__ __launch_bounds__(256, 2) void od_conv_stream3(Stream3KP p) {
 
   // ---- weights: WPIECES pieces of 1 KiB = PPP rows each; row = tap*NC + n ---------------------------------------------
 #pragma unroll
-  for (int k = 0; k < Cf::WPIECES / 4; ++k) {
-    const int q = wave * (Cf::WPIECES / 4) + k;
-    const int row = q * PPP + lane / LPP;
-    const int tap = row / NC, n = row - tap * NC;
-    const int lc = (lane % LPP) ^ s3_key<Cf::CH>(row);
-    glds16(p.w + ((long long)n * p.Kstride + tap * KC + lc * 8), wlds + q * 1024);
-  }
+  for (int k = 0; k < Cf::WPIECES / 4; ++k)
+    od_weight_piece_to_lds<9 * NC, Cf::PXB, NC, Cf::KEY>(p.w, p.Kstride, wlds, wave * (Cf::WPIECES / 4) + k, lane);
 
   auto stage = [&](int tile, int buf) {
-    const int img = tile / p.tiles_per_img, t2 = tile - img * p.tiles_per_img;
-    const int ty = t2 / p.tiles_x, tx = t2 - ty * p.tiles_x;
-    const int y0 = ty * 4 * S - 1, x0 = tx * 16 * S - 1;  // window origin in the input (pad 1)
+    const od_tile_pos t = od_tile_decode(tile, p.tiles_per_img, p.tiles_x);
+    const int img = t.img, y0 = t.ty * 4 * S - 1, x0 = t.tx * 16 * S - 1;  // window origin in the input (pad 1)
 #pragma unroll
     for (int k = 0; k < Cf::ND; ++k) {
       const int piece = wave + 4 * k;
       const int q = piece * PPP + lane / LPP;  // pixel slot
       const int r = q / Cf::WIN_W, c = q - r * Cf::WIN_W;
       const int yy = y0 + r, xx = x0 + c;
-      const int lc = (lane % LPP) ^ s3_key<Cf::CH>(q);
+      const int lc = (lane % LPP) ^ od_swz_key<Cf::KEY>(q);
       const bool ok = q < Cf::WIN_H * Cf::WIN_W && (unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W;
       const f16* src = ok ? p.x + ((((long long)img * p.H + yy) * p.W + xx) * KC + lc * 8) : p.zero;
       glds16(src, tlds + buf * (Cf::SLOTS * Cf::PXB) + piece * 1024);
@@ -92,13 +80,13 @@ __global__ __launch_bounds__(256, 2) void od_conv_stream3(Stream3KP p) {
   };
 
   const int first = blockIdx.x, step = gridDim.x;
-  const int nmine = first < p.ntiles ? (p.ntiles - first + step - 1) / step : 0;
+  const int nmine = od_tiles_of(first, step, p.ntiles);
   constexpr int NBUF = Cf::NBUF, AHEAD = NBUF - 1;
   if (nmine > 0) stage(first, 0);
   if (AHEAD > 1 && nmine > 1) stage(first + step, 1);
 
   // epilogue constants: store instruction s covers channels s*32 .. s*32+31; this lane's 8 channels inside it
-  const int n8 = (lq & 1) * 16 + (lq >> 1) * 8;
+  const int n8 = OD_LANE_CH8(lq);
   float sc[Cf::NS][8], bi[Cf::NS][8];
 #pragma unroll
   for (int s = 0; s < Cf::NS; ++s)
@@ -111,23 +99,12 @@ __global__ __launch_bounds__(256, 2) void od_conv_stream3(Stream3KP p) {
   for (int it = 0; it < nmine; ++it) {
     const int tile = first + it * step;
     const int buf = it % NBUF;
-    // vector memory retires in order.  Three buffers: behind the DMAs of tile `it` this wave has issued stores(it-2) [NS],
-    // the DMAs of tile it+1 [ND, if there is one] and stores(it-1) [NS]; two buffers: only stores(it-1).
-    if (it < AHEAD) {
-      wait_vmcnt<0>();
-    } else if (AHEAD == 1) {
-      wait_vmcnt<Cf::NS>();
-    } else if (it + 1 < nmine) {
-      wait_vmcnt<2 * Cf::NS + Cf::ND>();
-    } else {
-      wait_vmcnt<2 * Cf::NS>();
-    }
+    od_ring_wait<NBUF, Cf::NS, Cf::ND>(it, nmine);
     __builtin_amdgcn_s_barrier();
     if (it + AHEAD < nmine) stage(tile + AHEAD * step, (it + AHEAD) % NBUF);
 
-    const int img = tile / p.tiles_per_img, t2 = tile - img * p.tiles_per_img;
-    const int ty = t2 / p.tiles_x, tx = t2 - ty * p.tiles_x;
-    const int oy = ty * 4 + wave, ox0 = tx * 16;
+    const od_tile_pos t = od_tile_decode(tile, p.tiles_per_img, p.tiles_x);
+    const int img = t.img, oy = t.ty * 4 + wave, ox0 = t.tx * 16;
     const char* tb = tlds + buf * (Cf::SLOTS * Cf::PXB);
 
     f32x4 acc[NC / 16];
@@ -141,11 +118,11 @@ __global__ __launch_bounds__(256, 2) void od_conv_stream3(Stream3KP p) {
         const int tap = dy * 3 + dx;
 #pragma unroll
         for (int kh = 0; kh < KC / 32; ++kh) {
-          const f16x8 xv = *(const f16x8*)(tb + q * Cf::PXB + (((kh * 4 + lq) ^ s3_key<Cf::CH>(q)) * 16));
+          const f16x8 xv = *(const f16x8*)(tb + q * Cf::PXB + (((kh * 4 + lq) ^ od_swz_key<Cf::KEY>(q)) * 16));
 #pragma unroll
           for (int f = 0; f < NC / 16; ++f) {
             const int row = tap * NC + f * 16 + l15;
-            const f16x8 wv = *(const f16x8*)(wlds + row * Cf::PXB + (((kh * 4 + lq) ^ s3_key<Cf::CH>(row)) * 16));
+            const f16x8 wv = *(const f16x8*)(wlds + row * Cf::PXB + (((kh * 4 + lq) ^ od_swz_key<Cf::KEY>(row)) * 16));
             acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wv, xv, acc[f], 0, 0, 0);
           }
         }
@@ -154,22 +131,10 @@ __global__ __launch_bounds__(256, 2) void od_conv_stream3(Stream3KP p) {
 #pragma unroll
     for (int s = 0; s < Cf::NS; ++s) {
       float o[8];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float a = acc[2 * s][e], b = acc[2 * s + 1][e];
-        od_permlane16_swap(a, b);
-        o[e] = a;
-        o[4 + e] = b;
-      }
+      od_pair_row8(acc[2 * s], acc[2 * s + 1], o);
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] = o[e] * sc[s][e] + bi[s][e];
-      if (p.act == OD_ACT_LEAKY) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = od_leaky(o[e], p.alpha);
-      } else if (p.act == OD_ACT_ELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = o[e] > 0.f ? o[e] : p.alpha * od_expm1_fast(o[e]);
-      }
+      od_act_rt(o, p.act, p.alpha);
       f16x8 h;
 #pragma unroll
       for (int e = 0; e < 8; ++e) h[e] = (f16)o[e];
@@ -178,23 +143,9 @@ __global__ __launch_bounds__(256, 2) void od_conv_stream3(Stream3KP p) {
   }
 }
 
-struct S3Entry {
-  int kc, nc, stride;
-  const void* fn;
-  const char* name;
-  size_t lds;
-};
-const S3Entry g_s3[] = {
-    {64, 32, 1, (const void*)&od_conv_stream3<64, 32, 1>, "od_conv_stream3<64, 32, 1>", (size_t)S3Cfg<64, 32, 1>::LDS},
-    {32, 64, 1, (const void*)&od_conv_stream3<32, 64, 1>, "od_conv_stream3<32, 64, 1>", (size_t)S3Cfg<32, 64, 1>::LDS},
-    {32, 64, 2, (const void*)&od_conv_stream3<32, 64, 2>, "od_conv_stream3<32, 64, 2>", (size_t)S3Cfg<32, 64, 2>::LDS},
-};
-
-const S3Entry* s3_find(const od_conv_desc* d) {
-  for (const S3Entry& e : g_s3)
-    if (e.kc == d->Cin && e.nc == d->Cout && e.stride == d->stride) return &e;
-  return nullptr;
-}
+#define OD_S3(KC, NC, S) \
+  { KC, NC, S, 3, {(const void*)&od_conv_stream3<KC, NC, S>, "od_conv_stream3<" #KC ", " #NC ", " #S ">", 0, 0, 0, 256, (size_t)S3Cfg<KC, NC, S>::LDS} }
+const DirectKernel g_s3[] = {OD_S3(64, 32, 1), OD_S3(32, 64, 1), OD_S3(32, 64, 2)};
 
 }  // namespace
 
@@ -203,11 +154,11 @@ bool od_conv_stream3_supported(const od_conv_desc* d) {
       d->out_pix_stride != 0 || d->bn_partials || d->w2 || d->H % d->stride || d->W % d->stride)
     return false;
   const int Ho = d->H / d->stride, Wo = d->W / d->stride;
-  return s3_find(d) != nullptr && Ho % 4 == 0 && Wo % 16 == 0 && (long long)d->B * d->H * d->W * d->Cin < (1LL << 31);
+  return od_direct_find(g_s3, d) != nullptr && Ho % 4 == 0 && Wo % 16 == 0 && (long long)d->B * d->H * d->W * d->Cin < (1LL << 31);
 }
 
 int od_conv_stream3_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) {
-  const S3Entry* e = s3_find(d);
+  const DirectKernel* e = od_direct_find(g_s3, d);
   if (!e) return OD_ERR_INVALID;
   Stream3KP p;
   p.x = (const f16*)d->x;
@@ -226,9 +177,5 @@ int od_conv_stream3_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) 
   p.tiles_x = p.Wo / 16;
   p.tiles_per_img = (p.Ho / 4) * p.tiles_x;
   p.ntiles = d->B * p.tiles_per_img;
-  const int cus = ctx->num_cu;
-  int grid = 2 * cus;
-  if (grid > p.ntiles) grid = p.ntiles;
-  if (int rc = od_ensure_lds(ctx, e->fn, e->lds)) return rc;
-  return od_add_launch(L, {e->name, od_issue_kp, e->fn, dim3(grid), dim3(256), e->lds}, p);
+  return od_direct_launch(ctx, L, e->k, od_persistent_grid(2, ctx->num_cu, p.ntiles), p);
 }

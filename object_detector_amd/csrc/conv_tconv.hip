@@ -17,7 +17,7 @@
 //
 // Replaces the input-gradient half of the Keras Conv2D backward pass of `b.down1` in the reference's (unseen) training
 // loop (docs/MODEL.md:15-17 names the backbone).
-#include "conv_common.h"
+#include "conv_direct.h"
 
 namespace {
 
@@ -27,6 +27,8 @@ constexpr int T_ROWB = 128;                      // 64 f16 per pixel
 constexpr int T_NBUF = 3;
 constexpr int T_WBYTES = 9 * 32 * T_ROWB;        // weights: row = tap * 32 + n
 constexpr int T_LDS = T_WBYTES + T_NBUF * T_PIX * T_ROWB;
+constexpr od_swz T_KEY = od_swz_stream(T_ROWB / 16);  // dZ pixel rows and weight rows alike
+constexpr int T_NS = 4, T_ND = 3;               // per wave and tile: output stores (one per parity class), LDS-DMA pieces
 
 struct TconvKP {
   const f16* dz;    // [B, Hs, Ws, 64]
@@ -48,29 +50,19 @@ __global__ __launch_bounds__(256, 2) void od_tconv_64_32(TconvKP p) {
   const int l15 = lane & 15, lq = lane >> 4;
 
   // ---- weights: 36 pieces of 8 rows x 128 B; piece q -> rows 8q .. 8q+7 (row = tap*32 + n) -------------------------
-  {
-    const int r8 = lane >> 3;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      const int q = wave * 9 + k;
-      const int row = q * 8 + r8;
-      const int tap = row >> 5, n = row & 31;
-      const int lc = (lane & 7) ^ (row & 7);
-      glds16(p.wt + ((long long)n * p.Kstride + tap * 64 + lc * 8), wlds + q * 1024);
-    }
-  }
+  for (int k = 0; k < 9; ++k) od_weight_piece_to_lds<9 * 32, T_ROWB, 32, T_KEY, unsigned>(p.wt, p.Kstride, wlds, wave * 9 + k, lane);
 
   // ---- tile staging: 12 pieces of 8 pixel rows; wave w issues pieces w, w+4, w+8 ------------------------------------
   auto stage = [&](int tile, int buf) {
-    const int img = tile / p.tiles_per_img, t2 = tile - img * p.tiles_per_img;
-    const int ty = t2 / p.tiles_x, tx = t2 - ty * p.tiles_x;
-    const int u0 = ty * T_R, v0 = tx * T_C;
+    const od_tile_pos t = od_tile_decode(tile, p.tiles_per_img, p.tiles_x);
+    const int img = t.img, u0 = t.ty * T_R, v0 = t.tx * T_C;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < T_ND; ++k) {
       const int q = (wave + 4 * k) * 8 + (lane >> 3);  // pixel slot
       const int r = q / 17, c = q - r * 17;
       const int u = u0 + r, v = v0 + c;
-      const int lc = (lane & 7) ^ (q & 7);
+      const int lc = (lane & 7) ^ od_swz_key<T_KEY>(q);
       const bool ok = q < 85 && u < p.Hs && v < p.Ws;
       const f16* src = ok ? p.dz + ((((long long)img * p.Hs + u) * p.Ws + v) * 64 + lc * 8) : p.zero;
       glds16(src, tlds + buf * (T_PIX * T_ROWB) + (wave + 4 * k) * 1024);
@@ -78,40 +70,32 @@ __global__ __launch_bounds__(256, 2) void od_tconv_64_32(TconvKP p) {
   };
 
   const int first = blockIdx.x, step = gridDim.x;
-  int nmine = first < p.ntiles ? (p.ntiles - first + step - 1) / step : 0;
+  const int nmine = od_tiles_of(first, step, p.ntiles);
   if (nmine > 0) stage(first, 0);
   if (nmine > 1) stage(first + step, 1);
 
   // this lane's 8 output channels after the permlane pairing, and their scale / bias
-  const int n8 = (lq & 1) * 16 + (lq >> 1) * 8;
+  const int n8 = OD_LANE_CH8(lq);
   float sc[8], bi[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     sc[e] = p.scale[n8 + e];
     bi[e] = p.bias[n8 + e];
   }
-  // weight fragment base: row = tap*32 + f*16 + l15, chunk (kh*4 + lq) ^ (l15 & 7)
-  const int fw = l15 * T_ROWB + ((lq ^ (l15 & 7)) * 16);
+  // weight fragment base: row = tap*32 + f*16 + l15, chunk (kh*4 + lq) ^ key(l15); the key moves chunk bits 0-2 only, so k
+  // half kh is bit 6 of the byte offset: fw ^ (kh * 64)
+  const int fw = l15 * T_ROWB + ((lq ^ od_swz_key<T_KEY>(l15)) * 16);
   const int Ho = 2 * p.Hs, Wo = 2 * p.Ws;
 
   for (int it = 0; it < nmine; ++it) {
     const int tile = first + it * step;
     const int buf = it % T_NBUF;
-    // The DMAs of tile `it` were issued two iterations ago; vector memory retires in order, and behind them this wave has
-    // issued stores(it-2) [4], the DMAs of tile it+1 [3, if there is one] and stores(it-1) [4]: those may stay in flight.
-    if (it < 2) {
-      wait_vmcnt<0>();  // weights + the prologue's two tiles
-    } else if (it + 1 < nmine) {
-      wait_vmcnt<11>();
-    } else {
-      wait_vmcnt<8>();
-    }
+    od_ring_wait<T_NBUF, T_NS, T_ND>(it, nmine);  // (it < 2: weights + the prologue's two tiles)
     __builtin_amdgcn_s_barrier();
     if (it + 2 < nmine) stage(tile + 2 * step, (it + 2) % T_NBUF);
 
-    const int img = tile / p.tiles_per_img, t2 = tile - img * p.tiles_per_img;
-    const int tyy = t2 / p.tiles_x, txx = t2 - tyy * p.tiles_x;
-    const int u = tyy * T_R + wave, v0 = txx * T_C;
+    const od_tile_pos t = od_tile_decode(tile, p.tiles_per_img, p.tiles_x);
+    const int img = t.img, u = t.ty * T_R + wave, v0 = t.tx * T_C;
     const char* tb = tlds + buf * (T_PIX * T_ROWB);
 
     // source fragments: (dy, dx) in {0,1}^2 -> pixel slot (wave + dy)*17 + l15 + dx, two k halves
@@ -123,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void od_tconv_64_32(TconvKP p) {
         const int q = (wave + dy) * 17 + l15 + dx;
 #pragma unroll
         for (int kh = 0; kh < 2; ++kh)
-          xs[dy][dx][kh] = *(const f16x8*)(tb + q * T_ROWB + ((((kh * 4 + lq) ^ (q & 7))) * 16));
+          xs[dy][dx][kh] = *(const f16x8*)(tb + q * T_ROWB + (((kh * 4 + lq) ^ od_swz_key<T_KEY>(q)) * 16));
       }
     f32x4 acc[4][2];
 #pragma unroll
@@ -153,13 +137,7 @@ __global__ __launch_bounds__(256, 2) void od_tconv_64_32(TconvKP p) {
       for (int c = 0; c < 4; ++c) {
         const int py = c >> 1, px = c & 1;
         float o[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float a = acc[c][0][e], b = acc[c][1][e];
-          od_permlane16_swap(a, b);
-          o[e] = a;
-          o[4 + e] = b;
-        }
+        od_pair_row8(acc[c][0], acc[c][1], o);
         f16x8 h;
 #pragma unroll
         for (int e = 0; e < 8; ++e) h[e] = (f16)(o[e] * sc[e] + bi[e]);
@@ -194,9 +172,6 @@ int od_tconv_small_prepare(od_ctx* ctx, const od_conv_desc* d, od_launches* L) {
   p.tiles_x = d->W / T_C;
   p.tiles_per_img = (d->H / T_R) * p.tiles_x;
   p.ntiles = d->B * p.tiles_per_img;
-  const int cus = ctx->num_cu;
-  int grid = 2 * cus;
-  if (grid > p.ntiles) grid = p.ntiles;
-  if (int rc = od_ensure_lds(ctx, (const void*)&od_tconv_64_32, (size_t)T_LDS)) return rc;
-  return od_add_launch(L, {"od_tconv_64_32", od_issue_kp, (const void*)&od_tconv_64_32, dim3(grid), dim3(256), T_LDS}, p);
+  const ConvKernelInfo k = {(const void*)&od_tconv_64_32, "od_tconv_64_32", 0, 0, 0, 256, (size_t)T_LDS};
+  return od_direct_launch(ctx, L, k, od_persistent_grid(2, ctx->num_cu, p.ntiles), p);
 }

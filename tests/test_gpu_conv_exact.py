@@ -585,3 +585,147 @@ def test_bn_partials_sum_the_rounded_values_they_store(cuda, case):
     """'partial sums of the f16 values it stores' (include/odhip.h): with a z that the store rounds, sum z must be the sum
     of the ROUNDED values -- the sum of the f32 values before the cast is a different number on most channels."""
     check_bn_partial_rows(cuda, case, rounded=True)
+
+
+# ------------------------------------------------------------------------------------------------ persistent tile walks
+# The direct kernels (csrc/conv_direct.h) are persistent: a workgroup -- in od_conv_rdirect / od_tconv_rdirect a wave --
+# walks several tiles, with the next windows in flight.  On a 256-CU part none of the small cases above makes a workgroup
+# take a second tile, so the second window buffer, the loader waves' steady state, the counted vmcnt waits and the `xb`
+# half of the ping-pong were reached by the tolerance-based full-size tests only.  The shapes here are built from the
+# device's CU count and the grid rules of the *_prepare functions so that, on whatever part this runs,
+#   every worker takes at least NBUF + 2 tiles (4 where there is no ring): prologue, steady state and drain all run;
+#   the work is no whole multiple of the workers: trip counts differ between them.
+# (The pointwise od_conv_rdirect forms reach this with the (8, 160, 160, ...) cases of tc.RDIRECT_CASES: 12 800 items for
+# 2 x 256 x 8 waves; od_bneck<128> runs one tile per workgroup.)
+DIRECT_KERNELS = ({f"od_stem_k<{a}>" for a in range(3)} | {f"od_bneck<{c}, {a}>" for c in (64, 128) for a in range(3)}
+                  | {f"od_conv_rdirect<{kc}, {nc}, 1, 1>" for kc, nc in ((64, 32), (32, 64), (128, 64), (64, 128))}
+                  | {"od_conv_rdirect<64, 128, 2, 3>", "od_tconv_rdirect<128, 64>", "od_tconv_64_32"}
+                  | {"od_conv_stream3<64, 32, 1>", "od_conv_stream3<32, 64, 1>", "od_conv_stream3<32, 64, 2>"})
+DIRECT_PREFIXES = ("od_stem_k", "od_bneck", "od_conv_rdirect", "od_tconv_rdirect", "od_conv_stream3", "od_tconv_64_32")
+# name -> (units of work per image, workers per CU, least trips per worker, kernel, case builder from the batch)
+WALKS = {
+    # od_bottleneck_prepare: grid = min(num_cu, tiles), 16 x 16 tiles, two x-window buffers
+    "bneck64": (4, 1, 4, "od_bneck<64, 1>", lambda B: (B, 32, 32, 64, "leaky")),
+    # od_stem_prepare: grid = min(num_cu, tiles), 32 x 32 input pixels per tile, two uint8 window buffers
+    "stem": (4, 1, 4, "od_stem_k<1>", lambda B: ((B, 64, 64), "leaky")),
+    # od_conv_rdirect_prepare, 3x3: num_cu workgroups x 8 waves, item = 16 output pixels of a row (Ho = 64, Wo = 16)
+    "rdirect3x3": (64, 8, 4, "od_conv_rdirect<64, 128, 2, 3>", lambda B: (B, 128, 32, 64, 128, 3, 2, "leaky", False)),
+    # the same grid; item = 16 dZ pixels of a row (dZ 64 x 16); the case is the forward layer's
+    "tconv_rdirect": (64, 8, 4, "od_tconv_rdirect<128, 64>", lambda B: (B, 128, 32, 64, 128, 3, 2)),
+    # od_conv_stream3_prepare: grid = min(2 num_cu, tiles), 4 x 16 output tiles (Ho = 16, Wo = 32), ring of 3 or 2
+    "stream3_64_32": (8, 2, 5, "od_conv_stream3<64, 32, 1>", lambda B: (B, 16, 32, 64, 32, 3, 1, None, "none", -1)),
+    "stream3_32_64": (8, 2, 5, "od_conv_stream3<32, 64, 1>", lambda B: (B, 16, 32, 32, 64, 3, 1, "leaky", "none", -1)),
+    "stream3_32_64_s2": (8, 2, 5, "od_conv_stream3<32, 64, 2>", lambda B: (B, 32, 64, 32, 64, 3, 2, "elu", "none", -1)),
+    # od_tconv_small_prepare: grid = min(2 num_cu, tiles), 4 x 16 dZ tiles (dZ 16 x 32), ring of 3
+    "tconv_64_32": (8, 2, 5, "od_tconv_64_32", lambda B: (B, 32, 64, 32, 64, 3, 2)),
+}
+
+
+def walk_batch(units_per_image, workers, trips):
+    """The smallest batch whose work gives each of `workers` at least `trips` units and is no multiple of `workers`."""
+    assert units_per_image % workers != 0, "an image is a whole number of rounds: no batch gives unequal trip counts"
+    B = -(-(trips * workers + 1) // units_per_image)
+    while B * units_per_image % workers == 0:
+        B += 1
+    return B
+
+
+def assert_walks(work, workers, trips, what, uneven=True):
+    assert work > workers and work // workers >= trips and (work % workers != 0 or not uneven), \
+        f"{what}: {work} units over {workers} workers is not a walk of >= {trips} units each" + " with unequal trip counts" * uneven
+
+
+def _plan_kernel(cuda, fill):
+    """The kernel a one-op plan resolves to (creation only: nothing is launched, the tensors are one dummy buffer)."""
+    from object_detector_amd import _lib
+    ctx = _ctx(cuda)
+    dummy = torch.zeros(4096, dtype=torch.uint8, device=cuda)
+    op = _lib.PlanOp()
+    fill(op, dummy.data_ptr())
+    h = C.c_void_p()
+    _lib.check(ctx.lib.od_plan_create(ctx.handle, (_lib.PlanOp * 1)(op), 1, C.byref(h)), "od_plan_create (one op)")
+    try:
+        return ctx.lib.od_plan_op_kernel_name(h, 0).decode()
+    finally:
+        ctx.lib.od_plan_destroy(h)
+
+
+def conv_kernel(cuda, B, H, W, Cin, Cout, k, stride, act=None, resm="none", cfg=-1, transposed=False):
+    from object_detector_amd import _lib
+
+    def fill(op, ptr):
+        op.kind, d = _lib.OD_OP_CONV, op.conv
+        d.x = d.w = d.scale = d.bias = d.out = ptr
+        d.res = ptr if resm != "none" else None
+        d.B, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = B, H, W, Cin, Cout, k, stride
+        d.act, d.alpha = _lib.ACT_ENUM[act], _alpha(act)
+        d.res_mode = {"none": _lib.OD_RES_NONE, "same": _lib.OD_RES_SAME, "up2": _lib.OD_RES_UP2}[resm]
+        d.out_dtype, d.tile_cfg, d.splitk, d.transposed = _lib.OD_DT_F16, cfg, 1, int(transposed)
+    return _plan_kernel(cuda, fill)
+
+
+def bneck_kernel(cuda, case):
+    from object_detector_amd import _lib
+    B, H, W, Cc, act = case
+
+    def fill(op, ptr):
+        op.kind, d = _lib.OD_OP_BNECK, op.bneck
+        d.x = d.w1 = d.scale1 = d.bias1 = d.w3 = d.scale3 = d.bias3 = d.out = ptr
+        d.B, d.H, d.W, d.C, d.act, d.alpha = B, H, W, Cc, _lib.ACT_ENUM[act], _alpha(act)
+    return _plan_kernel(cuda, fill)
+
+
+def stem_kernel(cuda, case):
+    from object_detector_amd import _lib
+    (B, H, W), act = case
+
+    def fill(op, ptr):
+        op.kind, d = _lib.OD_OP_STEM, op.stem
+        d.x = d.w0 = d.scale0 = d.bias0 = d.w3 = d.scale3 = d.bias3 = d.out = ptr
+        d.B, d.H, d.W, d.act, d.alpha = B, H, W, _lib.ACT_ENUM[act], _alpha(act)
+    return _plan_kernel(cuda, fill)
+
+
+def bwd_data_kernel(cuda, case):
+    """Backward-data of the forward layer `case`: stride 2 is the transposed launch over the dZ map, stride 1 a forward
+    launch with the channels swapped (od_conv2d_bwd_data)."""
+    B, H, W, Cin, Cout, k, stride = case
+    if stride == 2:
+        return conv_kernel(cuda, B, H // 2, W // 2, Cout, Cin, k, 2, transposed=True)
+    return conv_kernel(cuda, B, H, W, Cout, Cin, k, 1)
+
+
+@pytest.mark.parametrize("walk", sorted(WALKS), ids=str)
+def test_persistent_walk_takes_several_tiles_per_worker(cuda, walk, monkeypatch):
+    monkeypatch.setenv("OD_CONV_RDIRECT_MIN_PIXELS", "0")
+    units, per_cu, trips, kernel, make = WALKS[walk]
+    workers = per_cu * torch.cuda.get_device_properties(cuda).multi_processor_count
+    B = walk_batch(units, workers, trips)
+    case = make(B)
+    assert_walks(B * units, workers, trips, f"{walk} {case}")  # before anything is built or launched
+    if walk == "bneck64":
+        assert bneck_kernel(cuda, case) == kernel
+        test_bottleneck(cuda, case)
+    elif walk == "stem":
+        assert stem_kernel(cuda, case) == kernel
+        test_stem(cuda, case)
+    elif walk == "rdirect3x3":
+        assert conv_kernel(cuda, *case[:7], act=case[7]) == kernel
+        test_fwd_weights_resident_kernels(cuda, case, monkeypatch)
+    elif walk.startswith("stream3"):
+        assert conv_kernel(cuda, *case[:7], act=case[7]) == kernel
+        test_fwd_every_table_config(cuda, case)
+    else:
+        assert bwd_data_kernel(cuda, case) == kernel
+        check_backward_data(cuda, case)
+
+
+def test_every_direct_kernel_is_exercised(cuda, monkeypatch):
+    """The exact case lists reach all 19 direct kernels: what the library selects for each case, not what a table says."""
+    monkeypatch.setenv("OD_CONV_RDIRECT_MIN_PIXELS", "0")
+    reached = {bneck_kernel(cuda, c) for c in tb.CASES} | {stem_kernel(cuda, c) for c in STEM_CASES}
+    reached |= {conv_kernel(cuda, *c[:7], act=c[7], resm=c[8], cfg=c[9]) for c in tc.CASES}
+    reached |= {conv_kernel(cuda, *c[:7], act=c[7], resm="same" if c[8] else "none") for c in tc.RDIRECT_CASES}
+    reached |= {bwd_data_kernel(cuda, c) for c in BWD_CASES}
+    reached = {n for n in reached if n.startswith(DIRECT_PREFIXES)}
+    assert reached == DIRECT_KERNELS, f"never exercised: {sorted(DIRECT_KERNELS - reached)}, unknown: {sorted(reached - DIRECT_KERNELS)}"

@@ -230,3 +230,35 @@ def test_poison_patterns():
     assert L.quantum_of(s16) == 2.0 ** -16  # finer than any lattice used here (>= 2^-13): never an expected value
     with pytest.raises(AssertionError, match="elements differ"):
         L.assert_equal(np.array([np.nan], np.float32), np.array([np.nan], np.float32), "NaN equals nothing")
+
+
+# ---- the persistent-walk cases of test_gpu_conv_exact.WALKS: their rule and their references, without a GPU
+@pytest.mark.parametrize("num_cu", [64, 228, 256, 304], ids=str)
+def test_walk_shapes_hold_their_rule_on_any_part(num_cu):
+    for name, (units, per_cu, trips, _kernel, _make) in E.WALKS.items():
+        workers = per_cu * num_cu
+        E.assert_walks(E.walk_batch(units, workers, trips) * units, workers, trips, f"{name} on {num_cu} CUs")
+    with pytest.raises(AssertionError, match="not a walk"):
+        E.assert_walks(33 * 4, num_cu, 4, "the old (33, 32, 32, 64) case")  # 132 tiles: one each on 256 CUs, 2 on 64
+
+
+def test_fullsize_cases_walk_on_256_cus():
+    """What the full-size cases of the stream kernels give a 256-CU part (work, workers, least trips).  The two ring kernels
+    get 25 tiles per workgroup, the same for all: unequal trip counts come from the WALKS cases alone."""
+    B, Hs, Ws = E.TCONV_STREAM_CASES[-1]  # od_tconv_64_32: 4 x 16 dZ tiles, 2 workgroups per CU, ring of 3
+    E.assert_walks(B * (Hs // 4) * (Ws // 16), 2 * 256, 5, "od_tconv_64_32 (32, 160, 160)", uneven=False)
+    B, Hs, Ws = E.TCONV_RDIRECT_CASES[-1]  # od_tconv_rdirect: 16 dZ pixels of a row per item, 8 waves per CU
+    E.assert_walks(B * Hs * (Ws // 16), 8 * 256, 4, "od_tconv_rdirect (32, 80, 80)")
+    B, H, W = E.tc.CASES[-1][:3]  # od_conv_stream3<32, 64, 1>: 4 x 16 output tiles, 2 workgroups per CU
+    E.assert_walks(B * (H // 4) * (W // 16), 2 * 256, 5, "od_conv_stream3 (32, 160, 160)", uneven=False)
+    for c in E.tc.RDIRECT_CASES[-2:]:  # the pointwise od_conv_rdirect forms: 2 workgroups per CU x 8 waves
+        E.assert_walks(c[0] * c[1] * (c[2] // 16), 2 * 8 * 256, 3, f"od_conv_rdirect {c}")
+
+
+@pytest.mark.parametrize("walk", sorted(E.WALKS), ids=str)
+def test_walk_case_references_are_exact(walk):
+    units, per_cu, trips, _kernel, make = E.WALKS[walk]
+    case = make(E.walk_batch(units, per_cu * 16, trips))  # a 16-CU part's shape: the conditions do not depend on the batch
+    build = {"bneck64": E.build_bneck, "stem": E.build_stem, "rdirect3x3": E.build_rdirect, "tconv_rdirect": E.build_bwd,
+             "tconv_64_32": E.build_bwd}.get(walk, E.build_fwd)
+    build(case)
