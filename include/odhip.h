@@ -326,6 +326,15 @@ size_t od_loss_workspace_bytes(int B, int P);
 int od_loss_fwd_bwd(od_ctx* ctx, const float* pred, const float* y, float* grad, float* losses, int B, int P, int NC,
                     float focal_alpha, float focal_gamma, int box_mode, float w_obj, float w_cls, float w_box,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* The same with an IoU-family box loss: box_mode 2 = giou, 3 = diou, 4 = ciou is 1 - GIoU / DIoU / CIoU between the DECODED
+ * predicted and target boxes of every assigned prior (decode = od_decode_locs without clip, prior of row r = priors[r % P],
+ * priors f32 [P,4], 16-byte aligned), in the same single pass over pred / y.  A predicted box with crossed corners is sorted
+ * first (GIoU paper, Algorithm 2); eps = 1e-9 keeps every denominator positive for a zero-size predicted box; CIoU's alpha
+ * is a constant in the gradient.  box_mode 0 / 1: priors may be NULL, loc_scale is not read, and the result is
+ * od_loss_fwd_bwd's bit for bit.  Same workspace (od_loss_workspace_bytes). */
+int od_loss_fwd_bwd_iou(od_ctx* ctx, const float* pred, const float* y, const float* priors, float* grad, float* losses,
+                        int B, int P, int NC, float focal_alpha, float focal_gamma, int box_mode, float loc_scale,
+                        float w_obj, float w_cls, float w_box, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K11/K12: training-side kernels (the Keras fit() machinery behind tk.dl.od.ObjectDetector: Conv2D backward,

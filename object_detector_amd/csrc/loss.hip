@@ -2,7 +2,8 @@
 // reference docs/MODEL.md:33-52:
 //   objectness : 2-class focal loss (alpha_t, gamma)                    [:33-37]
 //   class      : softmax + categorical cross-entropy on assigned priors [:39-44]
-//   box        : MSE (doc mode) or smooth-L1 (north_star mode) on the corner-form offsets, assigned priors only [:46-52]
+//   box        : MSE (doc mode) or smooth-L1 (north_star mode) on the corner-form offsets, assigned priors only [:46-52];
+//                through od_loss_fwd_bwd_iou also 1 - GIoU / DIoU / CIoU of the DECODED boxes (od_iou_box below)
 // Rows: pred/y f32 [R, 2+NC+4] (R = B*P); y as written by od_assign_anchors (row all-zero = ignore).
 // total = (sum_obj + sum_cls + sum_box) / max(1, #assigned rows); grad is d total / d pred.
 // Reduction is deterministic: per-workgroup partials, then one workgroup sums them in a fixed order.
@@ -23,6 +24,7 @@
 // -Inf or a box offset of +-Inf into finite values, so each group adds `value * 0` (0, or NaN for a non-finite value).
 // Rows whose target is all zero (ignore) get an exactly zero gradient and add nothing, whatever the prediction holds.
 #include "common.h"
+#include "post_common.h"  // od_decode_one: the loss is taken on the boxes inference will output
 
 namespace {
 
@@ -49,12 +51,97 @@ __device__ __forceinline__ float od_log1p_unit(float e) {
   return d > 0.f ? logf(u) * (e * __builtin_amdgcn_rcpf(d)) : e;  // NaN stays NaN
 }
 
+// Box modes 2 = giou, 3 = diou, 4 = ciou (od_loss_fwd_bwd_iou): 1 - m of the decoded predicted box b and target box g of one
+// ASSIGNED row, and its gradient w.r.t. the four loc columns.  [BUILD-DEFINED] placement of eps = 1e-9 (normalised image
+// units; real boxes have areas >= 2e-6), restated in f64 with an autograd gradient by tests/iou_loss_ref.py:
+//   b, g = od_decode_one(pred loc | target loc, prior, loc_scale, no clip);  x1, x2 = min / max (bx1, bx2), y likewise: a
+//   predicted box with crossed corners is made well-formed as in Algorithm 2 of the GIoU paper, the derivative follows the
+//   selection;  iw = max(0, min(x2, gx2) - max(x1, gx1)), inter = iw * ih, U = ((wb * hb + wg * hg) - inter) + eps,
+//   IoU = inter / U;  cw, ch = sides of the enclosing box;
+//   giou: C = cw * ch + eps,          m = IoU - (C - U) / C
+//   diou: D = (cw^2 + ch^2) + eps,    m = IoU - rho2 / D     (rho2 = squared centre distance)
+//   ciou: v = (4 / pi^2) * (atan2(wg, hg + eps) - atan2(wb, hb + eps))^2,  a = v / (((1 - IoU) + v) + eps),  m = diou - a * v,
+//         a held constant in the gradient, as published.
+// Every denominator stays positive for a zero-size predicted box: U >= wg * hg, C and D are at least those of g, and
+// atan2's derivative divides by wb^2 + (hb + eps)^2 >= eps^2.  At an exact tie of a min / max the derivative is the one of
+// the branch `<=` / `>` / `<` below picks (a convention).  v_rcp_f32 (1 ulp) for the quotients, as in the objectness term.
+struct od_iou_args {
+  const float* priors;  // f32 [P,4]; row r of pred belongs to prior r % P
+  int P;
+  float loc_scale;
+};
+
+constexpr float OD_IOU_EPS = 1e-9f;
+
+// p, t -> the four loc columns of the row.  -> loss; gl[k] = d loss / d p[k] (unscaled).
+__device__ __forceinline__ float od_iou_box(const float* p, const float* t, f32x4 pr, float loc_scale, int box_mode,
+                                            float gl[4]) {
+  const f32x4 lp = {p[0], p[1], p[2], p[3]}, lt = {t[0], t[1], t[2], t[3]};
+  const f32x4 b = od_decode_one(lp, pr, loc_scale, 0), g = od_decode_one(lt, pr, loc_scale, 0);
+  const bool sx = b[0] <= b[2], sy = b[1] <= b[3];
+  const float x1 = sx ? b[0] : b[2], x2 = sx ? b[2] : b[0], y1 = sy ? b[1] : b[3], y2 = sy ? b[3] : b[1];
+  const float wb = x2 - x1, hb = y2 - y1, wg = g[2] - g[0], hg = g[3] - g[1];
+  const float iwr = fminf(x2, g[2]) - fmaxf(x1, g[0]), ihr = fminf(y2, g[3]) - fmaxf(y1, g[1]);
+  const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
+  const float inter = iw * ih;
+  const float uni = ((wb * hb + wg * hg) - inter) + OD_IOU_EPS;
+  const float ru = __builtin_amdgcn_rcpf(uni);
+  const float iou = inter * ru;
+  const float cw = fmaxf(x2, g[2]) - fminf(x1, g[0]), ch = fmaxf(y2, g[3]) - fminf(y1, g[1]);
+  // derivatives w.r.t. (x1, y1, x2, y2) of the well-formed box: inter, then U, then IoU = inter / U
+  const float di[4] = {iwr > 0.f && x1 > g[0] ? -ih : 0.f, ihr > 0.f && y1 > g[1] ? -iw : 0.f,
+                       iwr > 0.f && x2 < g[2] ? ih : 0.f, ihr > 0.f && y2 < g[3] ? iw : 0.f};
+  const float du[4] = {-hb - di[0], -wb - di[1], hb - di[2], wb - di[3]};
+  // d cw / d x1, d ch / d y1, d cw / d x2, d ch / d y2
+  const float de[4] = {x1 < g[0] ? -1.f : 0.f, y1 < g[1] ? -1.f : 0.f, x2 > g[2] ? 1.f : 0.f, y2 > g[3] ? 1.f : 0.f};
+  float m, dm[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) dm[k] = (di[k] - iou * du[k]) * ru;
+  if (box_mode == 2) {
+    const float c = cw * ch + OD_IOU_EPS;
+    const float rc = __builtin_amdgcn_rcpf(c);
+    const float uc = uni * rc;  // m = IoU - 1 + U / C
+    m = iou - (c - uni) * rc;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dm[k] += (du[k] - uc * (de[k] * ((k & 1) ? cw : ch))) * rc;
+  } else {
+    const float dx = ((x1 + x2) - (g[0] + g[2])) * 0.5f, dy = ((y1 + y2) - (g[1] + g[3])) * 0.5f;
+    const float rd = __builtin_amdgcn_rcpf((cw * cw + ch * ch) + OD_IOU_EPS);
+    const float pen = (dx * dx + dy * dy) * rd;
+    m = iou - pen;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dm[k] -= (((k & 1) ? dy : dx) - pen * (2.f * ((k & 1) ? ch : cw) * de[k])) * rd;
+    if (box_mode == 4) {
+      const float kv = 0.40528473456935109f;  // 4 / pi^2
+      const float hbe = hb + OD_IOU_EPS;
+      const float da = atan2f(wg, hg + OD_IOU_EPS) - atan2f(wb, hbe);
+      const float v = kv * (da * da);
+      const float a = v * __builtin_amdgcn_rcpf(((1.f - iou) + v) + OD_IOU_EPS);
+      m -= a * v;
+      // d v / d wb = -2 kv da * hbe / (wb^2 + hbe^2),  d v / d hb = 2 kv da * wb / (wb^2 + hbe^2)
+      const float q = a * (2.f * kv * da) * __builtin_amdgcn_rcpf(wb * wb + hbe * hbe);
+      const float avw = -q * hbe, avh = q * wb;  // a * d v / d wb, a * d v / d hb;  wb = x2 - x1, hb = y2 - y1
+      dm[0] += avw, dm[2] -= avw, dm[1] += avh, dm[3] -= avh;
+    }
+  }
+  // loss = 1 - m;  back through the corner selection and the decode: d b_k / d loc_k = loc_scale * (pw | ph)
+  const float sw = (pr[2] - pr[0]) * loc_scale, sh = (pr[3] - pr[1]) * loc_scale;
+  gl[0] = -(sx ? dm[0] : dm[2]) * sw;
+  gl[2] = -(sx ? dm[2] : dm[0]) * sw;
+  gl[1] = -(sy ? dm[1] : dm[3]) * sh;
+  gl[3] = -(sy ? dm[3] : dm[1]) * sh;
+  return 1.f - m;
+}
+
 // Objectness (focal loss over softmax(l0, l1)) and box columns of one row: p = prediction row, t = target row, g = gradient
 // row (g may be p: every column is read before it is written).  Writes g[0], g[1] and g[2+NC .. 2+NC+3], sets l_obj, adds the
-// four box terms to l_box.  The one copy of this arithmetic, for od_loss_rows and od_loss_rows_wide.
+// four box terms to l_box.  The one copy of this arithmetic, for od_loss_rows and od_loss_rows_wide.  IOU (box modes 2..4) is
+// a compile-time property, so that the smooth-L1 / MSE instantiations keep their code and registers; `row` = the row's
+// index in [0, B*P), `ia` the prior table: both are looked at by assigned rows of an IOU instantiation only.
+template <bool IOU>
 __device__ __forceinline__ void od_loss_obj_box(const float* p, const float* t, float* g, int NC, float alpha, float gamma,
-                                                int box_mode, float w_obj, float w_box, float invn, float& l_obj,
-                                                float& l_box) {
+                                                int box_mode, float w_obj, float w_box, float invn, long long row,
+                                                const od_iou_args& ia, float& l_obj, float& l_box) {
   const float t0 = t[0], t1 = t[1];
   const float l0 = p[0], l1 = p[1];  // read beside the targets, not behind the branch on them: one load latency, not two
   const bool pos = t1 > 0.5f;
@@ -80,6 +167,22 @@ __device__ __forceinline__ void od_loss_obj_box(const float* p, const float* t, 
   }
   g[0] = -g1 * w_obj * invn;
   g[1] = g1 * w_obj * invn;
+  if constexpr (IOU) {
+    float gl[4] = {0.f, 0.f, 0.f, 0.f};
+    if (pos) {
+      const float* pl = p + 2 + NC;
+      const float* tl = t + 2 + NC;
+      // 0, or NaN for a non-finite loc column: fminf / fmaxf and the clamps would hide one
+      const float nf = (((pl[0] + pl[1]) + (pl[2] + pl[3])) + ((tl[0] + tl[1]) + (tl[2] + tl[3]))) * 0.f;
+      const f32x4 pr = *(const f32x4*)(ia.priors + 4 * (row % ia.P));
+      l_box += od_iou_box(pl, tl, pr, ia.loc_scale, box_mode, gl) + nf;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) gl[k] = (gl[k] + nf) * w_box * invn;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g[2 + NC + k] = gl[k];
+    return;
+  }
   for (int k = 0; k < 4; ++k) {
     float gg = 0.f;
     if (pos) {
@@ -142,10 +245,12 @@ __device__ __forceinline__ float od_cls_grad(const od_cls_row& r, int c, float v
   return c == r.imax ? (t == 1.f ? r.q1m1 : r.q1 - t) : expf(lq) - t;
 }
 
+template <bool IOU>
 __global__ __launch_bounds__(256) void od_loss_rows(const float* __restrict__ pred, const float* __restrict__ y,
                                                     float* __restrict__ grad, long long R, int NC, float alpha,
                                                     float gamma, int box_mode, float w_obj, float w_cls, float w_box,
-                                                    const int* __restrict__ npos, float* __restrict__ partials) {
+                                                    const int* __restrict__ npos, float* __restrict__ partials,
+                                                    od_iou_args ia) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int C = NC + 6, tid = threadIdx.x;
   float* sp = sm;                // [LROWS][C] pred -> grad
@@ -171,7 +276,7 @@ __global__ __launch_bounds__(256) void od_loss_rows(const float* __restrict__ pr
   if (tid < nrows) {
     float* p = sp + tid * C;
     const float* t = sy + tid * C;
-    od_loss_obj_box(p, t, p, NC, alpha, gamma, box_mode, w_obj, w_box, invn, l_obj, l_box);
+    od_loss_obj_box<IOU>(p, t, p, NC, alpha, gamma, box_mode, w_obj, w_box, invn, r0 + tid, ia, l_obj, l_box);
     if (t[1] > 0.5f) {
       od_cls_row cr;
       for (int c = 0; c < NC; ++c) od_cls_max(cr, c, p[2 + c]);
@@ -216,10 +321,12 @@ __device__ __forceinline__ void od_loss_stage(const float* __restrict__ src, int
   }
 }
 
+template <bool IOU>
 __global__ __launch_bounds__(256) void od_loss_rows_wide(const float* __restrict__ pred, const float* __restrict__ y,
                                                          float* __restrict__ grad, long long R, int NC, float alpha,
                                                          float gamma, int box_mode, float w_obj, float w_cls, float w_box,
-                                                         const int* __restrict__ npos, float* __restrict__ partials) {
+                                                         const int* __restrict__ npos, float* __restrict__ partials,
+                                                         od_iou_args ia) {
   __shared__ float tp[LROWS * LW_LD], ty[LROWS * LW_LD];
   __shared__ float red[3][4];
   const int C = NC + 6, tid = threadIdx.x;
@@ -234,8 +341,8 @@ __global__ __launch_bounds__(256) void od_loss_rows_wide(const float* __restrict
   if (tid < nrows) {
     const float* t = yb + (long long)tid * C;
     pos = t[1] > 0.5f;
-    od_loss_obj_box(pb + (long long)tid * C, t, gb + (long long)tid * C, NC, alpha, gamma, box_mode, w_obj, w_box, invn,
-                    l_obj, l_box);
+    od_loss_obj_box<IOU>(pb + (long long)tid * C, t, gb + (long long)tid * C, NC, alpha, gamma, box_mode, w_obj, w_box,
+                         invn, r0 + tid, ia, l_obj, l_box);
   }
   // ---- class: softmax cross-entropy on assigned rows; zero gradient elsewhere ----
   const bool any_pos = __syncthreads_or(pos);
@@ -322,18 +429,45 @@ extern "C" size_t od_loss_workspace_bytes(int B, int P) {
   return 256 + (size_t)((R + LROWS - 1) / LROWS) * 3 * sizeof(float);
 }
 
-extern "C" int od_loss_fwd_bwd(od_ctx* ctx, const float* pred, const float* y, float* grad, float* losses, int B, int P,
-                               int NC, float focal_alpha, float focal_gamma, int box_mode, float w_obj, float w_cls,
-                               float w_box, void* workspace, size_t workspace_bytes, void* stream) {
-  OD_REQUIRE(ctx && pred && y && grad && losses && workspace, "od_loss_fwd_bwd: null argument");
-  OD_REQUIRE(NC >= 1 && NC <= 1024, "od_loss_fwd_bwd: NC = %d outside the supported class counts 1..1024", NC);
-  OD_REQUIRE(B > 0 && P > 0, "od_loss_fwd_bwd: bad dims");
-  OD_REQUIRE(box_mode == 0 || box_mode == 1, "od_loss_fwd_bwd: box_mode 0 = smooth-L1, 1 = MSE");
+namespace {
+
+template <bool IOU>
+int od_loss_launch(od_ctx* ctx, const float* pred, const float* y, float* grad, float* losses, long long R, int NC,
+                   float focal_alpha, float focal_gamma, int box_mode, float w_obj, float w_cls, float w_box, int* npos,
+                   float* partials, od_iou_args ia, hipStream_t s) {
+  const int nblocks = (int)((R + LROWS - 1) / LROWS);
+  if (NC > LMAX_LDS_NC) {
+    hipLaunchKernelGGL(od_loss_rows_wide<IOU>, dim3(nblocks), dim3(256), 0, s, pred, y, grad, R, NC, focal_alpha,
+                       focal_gamma, box_mode, w_obj, w_cls, w_box, npos, partials, ia);
+    OD_CHECK_LAUNCH();
+  } else {
+    const size_t lds = (size_t)2 * LROWS * (NC + 6) * sizeof(float);
+    if (int rc = od_ensure_lds(ctx, (const void*)&od_loss_rows<IOU>, lds)) return rc;
+    hipLaunchKernelGGL(od_loss_rows<IOU>, dim3(nblocks), dim3(256), lds, s, pred, y, grad, R, NC, focal_alpha, focal_gamma,
+                       box_mode, w_obj, w_cls, w_box, npos, partials, ia);
+    OD_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(od_loss_final, dim3(1), dim3(256), 0, s, partials, nblocks, npos, w_obj, w_cls, w_box, losses);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
+// Both entry points: `fn` names the caller in error messages.
+int od_loss_run(const char* fn, od_ctx* ctx, const float* pred, const float* y, const float* priors, float* grad,
+                float* losses, int B, int P, int NC, float focal_alpha, float focal_gamma, int box_mode, float loc_scale,
+                float w_obj, float w_cls, float w_box, void* workspace, size_t workspace_bytes, void* stream) {
+  OD_REQUIRE(ctx && pred && y && grad && losses && workspace, "%s: null argument", fn);
+  OD_REQUIRE(NC >= 1 && NC <= 1024, "%s: NC = %d outside the supported class counts 1..1024", fn, NC);
+  OD_REQUIRE(B > 0 && P > 0, "%s: bad dims", fn);
+  OD_REQUIRE(box_mode >= 0 && box_mode <= 4, "%s: box_mode 0 = smooth-L1, 1 = MSE, 2 = giou, 3 = diou, 4 = ciou", fn);
+  const bool iou = box_mode >= 2;
+  OD_REQUIRE(!iou || priors, "%s: box modes 2..4 need the prior table", fn);
+  OD_REQUIRE(!iou || ((uintptr_t)priors & 15) == 0, "%s: priors must be 16-byte aligned", fn);
   const long long R = (long long)B * P;
   const int nblocks = (int)((R + LROWS - 1) / LROWS);
   const size_t need = 256 + (size_t)nblocks * 3 * sizeof(float);
   if (workspace_bytes < need) {
-    od_set_error("od_loss_fwd_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
+    od_set_error("%s: workspace %zu < %zu bytes", fn, workspace_bytes, need);
     return OD_ERR_WORKSPACE;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -344,20 +478,27 @@ extern "C" int od_loss_fwd_bwd(od_ctx* ctx, const float* pred, const float* y, f
   if (cb > 2048) cb = 2048;
   hipLaunchKernelGGL(od_loss_count, dim3(cb), dim3(256), 0, s, y, R, NC + 6, npos);
   OD_CHECK_LAUNCH();
-  if (NC > LMAX_LDS_NC) {
-    hipLaunchKernelGGL(od_loss_rows_wide, dim3(nblocks), dim3(256), 0, s, pred, y, grad, R, NC, focal_alpha, focal_gamma,
-                       box_mode, w_obj, w_cls, w_box, npos, partials);
-    OD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(od_loss_final, dim3(1), dim3(256), 0, s, partials, nblocks, npos, w_obj, w_cls, w_box, losses);
-    OD_CHECK_LAUNCH();
-    return OD_OK;
-  }
-  const size_t lds = (size_t)2 * LROWS * (NC + 6) * sizeof(float);
-  if (int rc = od_ensure_lds(ctx, (const void*)&od_loss_rows, lds)) return rc;
-  hipLaunchKernelGGL(od_loss_rows, dim3(nblocks), dim3(256), lds, s, pred, y, grad, R, NC, focal_alpha, focal_gamma,
-                     box_mode, w_obj, w_cls, w_box, npos, partials);
-  OD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(od_loss_final, dim3(1), dim3(256), 0, s, partials, nblocks, npos, w_obj, w_cls, w_box, losses);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
+  const od_iou_args ia = {iou ? priors : nullptr, P, loc_scale};
+  return iou ? od_loss_launch<true>(ctx, pred, y, grad, losses, R, NC, focal_alpha, focal_gamma, box_mode, w_obj, w_cls,
+                                    w_box, npos, partials, ia, s)
+             : od_loss_launch<false>(ctx, pred, y, grad, losses, R, NC, focal_alpha, focal_gamma, box_mode, w_obj, w_cls,
+                                     w_box, npos, partials, ia, s);
+}
+
+}  // namespace
+
+extern "C" int od_loss_fwd_bwd_iou(od_ctx* ctx, const float* pred, const float* y, const float* priors, float* grad,
+                                   float* losses, int B, int P, int NC, float focal_alpha, float focal_gamma, int box_mode,
+                                   float loc_scale, float w_obj, float w_cls, float w_box, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  return od_loss_run("od_loss_fwd_bwd_iou", ctx, pred, y, priors, grad, losses, B, P, NC, focal_alpha, focal_gamma, box_mode,
+                     loc_scale, w_obj, w_cls, w_box, workspace, workspace_bytes, stream);
+}
+
+extern "C" int od_loss_fwd_bwd(od_ctx* ctx, const float* pred, const float* y, float* grad, float* losses, int B, int P,
+                               int NC, float focal_alpha, float focal_gamma, int box_mode, float w_obj, float w_cls,
+                               float w_box, void* workspace, size_t workspace_bytes, void* stream) {
+  OD_REQUIRE(box_mode == 0 || box_mode == 1, "od_loss_fwd_bwd: box_mode 0 = smooth-L1, 1 = MSE");
+  return od_loss_run("od_loss_fwd_bwd", ctx, pred, y, nullptr, grad, losses, B, P, NC, focal_alpha, focal_gamma, box_mode, 0.f,
+                     w_obj, w_cls, w_box, workspace, workspace_bytes, stream);
 }

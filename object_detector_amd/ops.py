@@ -187,19 +187,41 @@ def decode_locs(locs: torch.Tensor, priors: torch.Tensor, loc_scale=0.1, clip=Fa
     return out[0] if squeeze else out
 
 
+BOX_MODES = {"smooth_l1": 0, "mse": 1, "giou": 2, "diou": 3, "ciou": 4}  # od_loss_fwd_bwd_iou's box_mode
+IOU_BOX_MODES = ("giou", "diou", "ciou")
+
+
+def check_box_mode(box_mode, priors, num_priors):
+    """The argument rules of loss_fwd_bwd (no device needed): a known mode, and for an IoU mode a prior table [P,4]."""
+    if box_mode not in BOX_MODES:
+        raise ValueError(f"box_mode must be one of {sorted(BOX_MODES)}, got {box_mode!r}")
+    if box_mode in IOU_BOX_MODES:
+        if priors is None:
+            raise ValueError(f"box_mode {box_mode!r} is taken on decoded boxes: pass priors=<f32 [P,4] device tensor>")
+        if priors.dim() != 2 or priors.shape[1] != 4 or priors.shape[0] != num_priors:
+            raise ValueError(f"priors {tuple(priors.shape)} do not match the {num_priors} rows per image of pred")
+
+
 def loss_fwd_bwd(pred: torch.Tensor, y: torch.Tensor, num_classes=20, alpha=0.25, gamma=2.0, box_mode="smooth_l1",
-                 weights=(1.0, 1.0, 1.0)):
-    """pred, y f32 [B,P,2+NC+4] -> (losses f32 [4] = obj, cls, box, total ; grad f32 like pred)   (K10)"""
+                 weights=(1.0, 1.0, 1.0), priors: torch.Tensor | None = None, loc_scale=0.1):
+    """pred, y f32 [B,P,2+NC+4] -> (losses f32 [4] = obj, cls, box, total ; grad f32 like pred)   (K10)
+    box_mode "giou" | "diou" | "ciou": 1 - IoU metric of the boxes decoded from the loc columns with `priors` (f32 [P,4] on
+    pred's device) and `loc_scale`; "smooth_l1" | "mse" read neither."""
+    check_box_mode(box_mode, priors, pred.shape[-2])
     ctx = _ctx(pred)
     assert pred.dtype == torch.float32 and y.dtype == torch.float32 and pred.is_contiguous() and y.is_contiguous()
     B, P, Cc = pred.shape
     assert Cc == num_classes + 6 and y.shape == pred.shape
+    pr_ptr = None
+    if box_mode in IOU_BOX_MODES:
+        assert priors.dtype == torch.float32 and priors.is_contiguous() and priors.device == pred.device
+        pr_ptr = priors.data_ptr()
     grad = torch.empty_like(pred)
     losses = torch.empty((4,), dtype=torch.float32, device=pred.device)
     wsb = ctx.lib.od_loss_workspace_bytes(B, P)
     ws = torch.empty((wsb,), dtype=torch.uint8, device=pred.device)
-    _lib.check(ctx.lib.od_loss_fwd_bwd(ctx.handle, pred.data_ptr(), y.data_ptr(), grad.data_ptr(), losses.data_ptr(),
-                                       B, P, num_classes, float(alpha), float(gamma),
-                                       {"smooth_l1": 0, "mse": 1}[box_mode], float(weights[0]), float(weights[1]),
-                                       float(weights[2]), ws.data_ptr(), wsb, _stream_ptr()), "od_loss_fwd_bwd")
+    _lib.check(ctx.lib.od_loss_fwd_bwd_iou(ctx.handle, pred.data_ptr(), y.data_ptr(), pr_ptr, grad.data_ptr(),
+                                           losses.data_ptr(), B, P, num_classes, float(alpha), float(gamma),
+                                           BOX_MODES[box_mode], float(loc_scale), float(weights[0]), float(weights[1]),
+                                           float(weights[2]), ws.data_ptr(), wsb, _stream_ptr()), "od_loss_fwd_bwd_iou")
     return losses, grad

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib, train_ops as T, weights as W
 from .net import Context, _stream_ptr
+from .ops import BOX_MODES
 from .pb import PriorBoxes
 
 BN_MOMENTUM = 0.99  # Keras default
@@ -44,7 +45,7 @@ class Trainer:
     def __init__(self, params, batch_size, input_size=(320, 320), device="cuda:0", lr=1e-3, momentum=0.9,
                  weight_decay=0.0, loss_scale=1024.0, box_mode="smooth_l1", backbone_act=("leaky", 0.1),
                  head_act=("elu", 1.0), comm=None, world_size=1, grad_payload=None, dynamic_loss_scale=True,
-                 lr_multipliers=None, prior_wh=None, ignore_regions=False, ign_thr=None):
+                 lr_multipliers=None, prior_wh=None, ignore_regions=False, ign_thr=None, loss_weights=(1.0, 1.0, 1.0)):
         self.ctx = Context.get(device)
         self.lib = self.ctx.lib
         self.device = torch.device(device)
@@ -54,6 +55,13 @@ class Trainer:
         self.C = self.num_classes + 6
         self.lr, self.momentum, self.weight_decay = float(lr), float(momentum), float(weight_decay)
         self.loss_scale, self.box_mode = float(loss_scale), box_mode
+        # box_mode "giou" | "diou" | "ciou": the box loss is taken on the boxes decoded with self.pb's priors and loc_scale;
+        # loss_weights = (objectness, class, box) multiply the three components
+        if box_mode not in BOX_MODES:
+            raise ValueError(f"box_mode must be one of {sorted(BOX_MODES)}, got {box_mode!r}")
+        self.loss_weights = tuple(float(v) for v in loss_weights)
+        if len(self.loss_weights) != 3:
+            raise ValueError(f"loss_weights must be (objectness, class, box), got {loss_weights!r}")
         # per-layer learning-rate multipliers (docs/MODEL.md:84-90 by default: the reference fine-tunes a PRE-TRAINED base
         # network at 1/100; a from-scratch run passes {"h.": 1/3} to train the base network at the full rate)
         self.lr_multipliers = dict(LR_MULTIPLIERS if lr_multipliers is None else lr_multipliers)
@@ -378,11 +386,13 @@ class Trainer:
 
     def loss(self, y_target):
         """pred (from forward) + targets f32 [B,P,C] -> losses [4] on device; fills grad_pred."""
-        _lib.check(self.lib.od_loss_fwd_bwd(self.ctx.handle, self.pred.data_ptr(), y_target.data_ptr(),
-                                            self.grad_pred.data_ptr(), self.losses.data_ptr(), self.B, self.P,
-                                            self.num_classes, 0.25, 2.0, {"smooth_l1": 0, "mse": 1}[self.box_mode], 1.0,
-                                            1.0, 1.0, self.loss_ws.data_ptr(), self.loss_ws.numel(), _stream_ptr()),
-                   "od_loss_fwd_bwd")
+        w = self.loss_weights
+        _lib.check(self.lib.od_loss_fwd_bwd_iou(self.ctx.handle, self.pred.data_ptr(), y_target.data_ptr(),
+                                                self.pb.priors_device.data_ptr(), self.grad_pred.data_ptr(),
+                                                self.losses.data_ptr(), self.B, self.P, self.num_classes, 0.25, 2.0,
+                                                BOX_MODES[self.box_mode], self.pb.loc_scale, w[0], w[1], w[2],
+                                                self.loss_ws.data_ptr(), self.loss_ws.numel(), _stream_ptr()),
+                   "od_loss_fwd_bwd_iou")
         return self.losses
 
     def _grad(self, key):

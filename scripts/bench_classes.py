@@ -7,7 +7,8 @@ Prints ONE JSON line: per NC
     at 32 x 320^2 and 16 x 640^2, timed like bench.py (warm-up, then exactly --steps steps between synchronizes);
   od_detect alone on one batch's pred (the network's own output), on a quiet stream, hipEvents around --steps calls;
   od_detect's workspace bytes, and pass 1's HBM floor: B * P * (NC + 6) * 4 bytes at 6.3 TB/s;
-  od_loss_fwd_bwd at the training shard (32 x 320^2, bench.py's ground-truth recipe with NC classes), hipEvents."""
+  od_loss_fwd_bwd_iou at the training shard (32 x 320^2, bench.py's ground-truth recipe with NC classes) with the box loss
+    --box-loss names, hipEvents."""
 import argparse
 import json
 import pathlib
@@ -60,10 +61,11 @@ def predict(nc, size, batch, steps, warmup, dev):
     return rec
 
 
-def loss(nc, size, batch, steps, dev):
+def loss(nc, size, batch, steps, dev, box_loss="smooth_l1"):
     from object_detector_amd.net import Context, _stream_ptr
     from object_detector_amd.pb import ObjectsAnnotation, PriorBoxes
     from object_detector_amd import _lib
+    from object_detector_amd.ops import BOX_MODES
     rng = np.random.default_rng(1000)
     anns = []
     for _ in range(batch):  # bench.py's ground-truth recipe, classes drawn from 0..nc-1
@@ -83,13 +85,15 @@ def loss(nc, size, batch, steps, dev):
     ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
 
     def call():
-        _lib.check(ctx.lib.od_loss_fwd_bwd(ctx.handle, pred.data_ptr(), y.data_ptr(), grad.data_ptr(), losses.data_ptr(), B, P,
-                                           nc, 0.25, 2.0, 0, 1.0, 1.0, 1.0, ws.data_ptr(), wsb, _stream_ptr()),
-                   "od_loss_fwd_bwd")
+        _lib.check(ctx.lib.od_loss_fwd_bwd_iou(ctx.handle, pred.data_ptr(), y.data_ptr(), pb.priors_device.data_ptr(),
+                                               grad.data_ptr(), losses.data_ptr(), B, P, nc, 0.25, 2.0, BOX_MODES[box_loss],
+                                               pb.loc_scale, 1.0, 1.0, 1.0, ws.data_ptr(), wsb, _stream_ptr()),
+                   "od_loss_fwd_bwd_iou")
     call()
     torch.cuda.synchronize()
     ms = _events_ms(call, steps)
-    return {"loss_us": round(ms * 1e3, 1), "loss_bytes": 3 * B * P * C * 4}
+    return {"loss_us": round(ms * 1e3, 1), "loss_bytes": 3 * B * P * C * 4, "loss_box_mode": box_loss,
+            "loss_assigned_rows": int(_npos.sum().item())}
 
 
 def main():
@@ -97,6 +101,7 @@ def main():
     ap.add_argument("--classes", type=int, nargs="+", default=[20, 80, 365])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--box-loss", default="smooth_l1", choices=("smooth_l1", "mse", "giou", "diou", "ciou"))
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
@@ -106,7 +111,7 @@ def main():
         for size, batch in ((320, 32), (640, 16)):
             for k, v in predict(nc, size, batch, a.steps, a.warmup, dev).items():
                 row[f"{k}_{batch}x{size}"] = v
-        row.update(loss(nc, 320, 32, a.steps, dev))
+        row.update(loss(nc, 320, 32, a.steps, dev, a.box_loss))
         out[str(nc)] = row
     print(json.dumps({"metric": "class_count_scaling", "unit": "see keys", "by_num_classes": out}))
 

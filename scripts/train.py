@@ -21,8 +21,7 @@ import _common  # noqa: F401
 import pytoolkit as tk
 
 
-def _main():
-    tk.better_exceptions()
+def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--vocdevkit-dir", default=None, type=pathlib.Path)
     p.add_argument("--image-set", default="trainval")
@@ -47,8 +46,10 @@ def _main():
     p.add_argument("--from-scratch", action="store_true",
                    help="base network at the full learning rate instead of docs/MODEL.md:84-90's 1/100 (no pre-trained "
                         "Darknet53 is available offline)")
-    p.add_argument("--box-loss", default="smooth_l1", choices=("smooth_l1", "mse"),
-                   help="bounding-box loss: smooth-L1 (north_star) or the mean squared error docs/MODEL.md:46-52 describes")
+    p.add_argument("--box-loss", default="smooth_l1", choices=("smooth_l1", "mse", "giou", "diou", "ciou"),
+                   help="bounding-box loss: smooth-L1 (north_star), the mean squared error docs/MODEL.md:46-52 describes, or "
+                        "1 - GIoU / DIoU / CIoU of the decoded boxes")
+    p.add_argument("--box-weight", default=1.0, type=float, metavar="W", help="weight of the box loss in the total")
     p.add_argument("--fit-priors", action="store_true",
                    help="prior-box sizes from KMeans over the training boxes in grid-cell units (docs/MODEL.md:29-31) instead of "
                         "the frozen default table; they travel with the weights file")
@@ -63,7 +64,12 @@ def _main():
     p.add_argument("--shapes-difficult", default=0.0, type=float, help="--shapes: share of objects marked difficult")
     p.add_argument("--shapes-crowd", default=0.0, type=float, help="--shapes: share of images with a crowd region")
     p.add_argument("--prefetch", default=2, type=int, help="batches the generator thread runs ahead (0 = in the training thread)")
-    args = p.parse_args()
+    return p
+
+
+def _main():
+    tk.better_exceptions()
+    args = build_parser().parse_args()
     with tk.dl.session():
         tk.log.init(args.result_dir / "train.log")
         _run(args)
@@ -135,7 +141,7 @@ def _run(args):
         log.info(f"fitted prior sizes (grid-cell units), level 0: {np.round(prior_wh[0], 2).tolist()}")
     tr = Trainer(params, args.batch_size, tuple(args.input_size), device=dev, lr=args.lr, momentum=args.momentum,
                  weight_decay=args.weight_decay, comm=comm, world_size=world, lr_multipliers=mult, prior_wh=prior_wh, box_mode=args.box_loss,
-                 ignore_regions=args.ignore_regions)
+                 ignore_regions=args.ignore_regions, loss_weights=(1.0, 1.0, args.box_weight))
     gen = od_gen.create_generator(tuple(args.input_size), preprocess_input=None, encode_truth=tr.pb.encode_truth_device,
                                   device=dev, on_device=True, device_cache=not args.no_device_cache, mosaic=args.mosaic,
                                   ignore_regions=args.ignore_regions)
