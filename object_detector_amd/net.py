@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, weights as W
+from . import _lib, desc, weights as W
 
 
 def _stream_ptr():
@@ -64,6 +64,13 @@ def pad_vec(v: np.ndarray, n: int):
     out = np.zeros(n, np.float32)
     out[:len(v)] = v
     return out
+
+
+def pack_layer(w_ohwi: np.ndarray, scale, bias, first=False):
+    """One layer's host arrays for the kernels: (packed weight, scale, bias), scale / bias zero-padded to the packed Cout.
+    first: the image layer's [Cout, 32] pack."""
+    wp = pack_first_weight(w_ohwi) if first else pack_conv_weight(w_ohwi)
+    return wp, pad_vec(np.asarray(scale, np.float32), wp.shape[0]), pad_vec(np.asarray(bias, np.float32), wp.shape[0])
 
 
 # the cheapest plan that keeps EVERY logit within 1e-3 x scale of the fp32 oracle at 32 x 320^2 / 16 x 640^2 with margin
@@ -127,14 +134,10 @@ class Net:
             w = params[name + ".w"]
             assert w.shape == (cout, k, k, cin), (name, w.shape)
             scale, bias = W.fold_bn(params, name)
-            if name == "b.conv0":
-                wp = pack_first_weight(w)
+            first = name == "b.conv0"
+            if first:
                 scale = (scale / np.float32(255.0)).astype(np.float32)  # uint8 input normalisation folded in
-                npad = cout
-            else:
-                wp = pack_conv_weight(w)
-                npad = wp.shape[0]
-            self._dev[name] = (self._to_dev(wp), self._to_dev(pad_vec(scale, npad)), self._to_dev(pad_vec(bias, npad)))
+            self._dev[name] = tuple(self._to_dev(a) for a in pack_layer(w, scale, bias, first))
             if name in self.split:  # operand = [hi | lo] along the channels: the same weights for both halves
                 self._dev[name + "#split"] = (self._to_dev(pack_conv_weight(np.concatenate([w, w], axis=3))),) + self._dev[name][1:]
         self.input = torch.zeros((self.B, self.H, self.W, 3), dtype=torch.uint8, device=self.device)
@@ -147,9 +150,7 @@ class Net:
             nbytes = min(32 * self._splitk_elems * 4, 256 << 20)  # room for up to 32 partial slabs of the largest layer
             self.splitk_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
             for i in self._splitk_descs:
-                self.ops[i].conv.splitk = 0
-                self.ops[i].conv.splitk_workspace = self.splitk_ws.data_ptr()
-                self.ops[i].conv.splitk_workspace_bytes = nbytes
+                desc.set_splitk(self.ops[i].conv, 0, self.splitk_ws, nbytes)
         # TIMING ABLATION ONLY (results become garbage): drop ops whose name matches a prefix*suffix pattern, to measure what a
         # group of layers costs inside the running pipeline (scripts/dev/exp_ablate.sh); never set in tests / bench lines
         abl = [q.partition("*") for q in filter(None, os.environ.get("OD_ABLATE_OPS", "").split(","))]
@@ -192,26 +193,20 @@ class Net:
         self._keep.append(t)
         return t
 
+    def _emit(self, kind, d, /, **info):
+        """One plan op: the descriptor wrapped as od_plan_op, and its op_info record (name, flops, bytes, shape, tensors)."""
+        self.ops.append(desc.plan_op(kind, d))
+        self.op_info.append(info)
+
     def _wide(self, name, y32, res, res_f32, out32, out16, hilo, h, w, c, up2=False):
         """od_wide_add as a plan op: v = y32 (+ res, or + its nearest-neighbour parent on the half-size map `res` with
         up2); out32 = v, out16 = f16(v), hilo = [f16(v) | f16(v - f16(v))]."""
-        d = _lib.WideDesc()
-        d.y = y32.data_ptr()
-        d.res = res.data_ptr() if res is not None else None
-        d.out32 = out32.data_ptr() if out32 is not None else None
-        d.out16 = out16.data_ptr() if out16 is not None else None
-        d.out_hilo = hilo.data_ptr() if hilo is not None else None
-        d.M, d.C, d.res_f32 = self.B * h * w, c, int(bool(res_f32))
-        d.res_up2, d.H, d.W = int(bool(up2)), h, w
-        op = _lib.PlanOp()
-        op.kind = _lib.OD_OP_WIDE
-        op.wide = d
-        self.ops.append(op)
         m = self.B * h * w
         nbytes = m * c * (4 + (0 if res is None else (4 if res_f32 else 2)) + (4 if out32 is not None else 0)
                           + (2 if out16 is not None else 0) + (4 if hilo is not None else 0))
-        self.op_info.append(dict(name=name, flops=0.0, bytes=float(nbytes), shape=(m, c, 0), kind="wide", y=y32, res=res,
-                                 res_f32=bool(res_f32), out32=out32, out16=out16, hilo=hilo))
+        self._emit(_lib.OD_OP_WIDE, desc.wide(y32, res, out32, out16, hilo, m, c, h, w, res_f32=res_f32, up2=up2),
+                   name=name, flops=0.0, bytes=float(nbytes), shape=(m, c, 0), kind="wide", y=y32, res=res,
+                   res_f32=bool(res_f32), out32=out32, out16=out16, hilo=hilo)
 
     def _neck_conv(self, name, x, x_hilo, h, w, cin, cout, k, act, up16=None, up32=None, need16=False, keep32=False,
                    consumers=None):
@@ -248,114 +243,66 @@ class Net:
         """then = (name2, cout2, act2): the pointwise layer that consumes this layer's output rides in the same op
         (od_conv_desc.w2: inside the 8-wave kernel's epilogue, or as a second launch of the library's choosing);
         returns (out, ho, wo, out2) then."""
-        wt, sc, bi = self._dev[wkey or name]
         ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
         if out is None:
             out = self._buf(ho, wo, cout)
-        d = _lib.ConvDesc()
-        d.x, d.w, d.scale, d.bias = x.data_ptr(), wt.data_ptr(), sc.data_ptr(), bi.data_ptr()
-        d.res = res.data_ptr() if res is not None else None
-        d.out = out if isinstance(out, int) else out.data_ptr()
-        d.B, d.H, d.W, d.Cin, d.Cout = self.B, h, w, cin, cout
-        d.ksize, d.stride = k, stride
-        d.act, d.alpha = _lib.ACT_ENUM[act[0] if act else None], float(act[1]) if act else 0.0
-        d.res_mode = res_mode
-        d.out_dtype = _lib.OD_DT_F32 if out_f32 else _lib.OD_DT_F16
-        d.out_batch_stride, d.out_pix_stride = obs, ops
-        d.tile_cfg = self.tile_cfg.get(name, self.auto_cfg)
+        tile_cfg = self.tile_cfg.get(name, self.auto_cfg)
         for pat, cfg in self.tile_cfg.items():  # patterns "prefix*suffix", e.g. "b.s3*a" = the 1x1 convs of stage 3
             pre, star, suf = pat.partition("*")
             if star and name.startswith(pre) and name.endswith(suf):
-                d.tile_cfg = cfg
+                tile_cfg = cfg
         out2 = None
         if then is not None:
             name2, cout2, act2 = then
-            w2, sc2, bi2 = self._dev[name2]
             out2 = self._buf(ho, wo, cout2)
-            d.w2, d.scale2, d.bias2, d.out2 = w2.data_ptr(), sc2.data_ptr(), bi2.data_ptr(), out2.data_ptr()
-            d.Cout2 = cout2
-            d.act2, d.alpha2 = _lib.ACT_ENUM[act2[0] if act2 else None], float(act2[1]) if act2 else 0.0
+        d = desc.conv(x, *self._dev[wkey or name], out, self.B, h, w, cin, cout, k, stride, act, res=res, res_mode=res_mode,
+                      out_f32=out_f32, out_batch_stride=obs, out_pix_stride=ops, tile_cfg=tile_cfg,
+                      then=None if then is None else self._dev[name2] + (out2, cout2, act2))
         m = self.B * ho * wo
         if self.splitk and m * cout <= (1 << 22):  # candidates only; the library decides per layer
             self._splitk_elems = max(self._splitk_elems, m * cout)
             self._splitk_descs.append(len(self.ops))
-        op = _lib.PlanOp()
-        op.kind = _lib.OD_OP_CONV
-        op.conv = d
-        self.ops.append(op)
-        osz = 4 if out_f32 else 2
-        self.op_info.append(dict(name=name, flops=2.0 * m * cout * k * k * cin,
-                                 bytes=float(self.B * h * w * cin * 2 + m * cout * osz + cout * k * k * cin * 2
-                                             + (m * cout * 2 if res_mode == _lib.OD_RES_SAME else 0)
-                                             + (m * cout // 2 if res_mode == _lib.OD_RES_UP2 else 0)),
-                                 shape=(m, cout, k * k * cin),
-                                 # the op's tensors, for per-layer parity checks (tests/test_gpu_fullsize.py)
-                                 kind="conv", x=x, res=res, res_mode=res_mode, out=None if isinstance(out, int) else out,
-                                 stride=stride, ksize=k, act=act, out_f32=out_f32))
-        if wkey is not None and wkey.endswith("#split"):  # algorithmic flops: the (hi, lo) pair is ONE operand
-            self.op_info[-1]["flops"] *= 0.5
-            self.op_info[-1]["split"] = True
+        split = wkey is not None and wkey.endswith("#split")  # algorithmic flops: the (hi, lo) pair is ONE operand
+        flops = 2.0 * m * cout * k * k * cin * (0.5 if split else 1.0)
+        nbytes = float(self.B * h * w * cin * 2 + m * cout * (4 if out_f32 else 2) + cout * k * k * cin * 2
+                       + (m * cout * 2 if res_mode == _lib.OD_RES_SAME else 0)
+                       + (m * cout // 2 if res_mode == _lib.OD_RES_UP2 else 0))
+        extra = {"split": True} if split else {}
         if then is not None:
-            inf = self.op_info[-1]
-            inf["flops"] += 2.0 * m * cout2 * cout
-            inf["bytes"] += float(m * cout2 * 2 + cout2 * cout * 2)  # the 1x1's input never comes back from HBM
-            inf["then"] = dict(name=name2, out=out2, act=act2)
-            return out, ho, wo, out2
-        return out, ho, wo
+            flops += 2.0 * m * cout2 * cout
+            nbytes += float(m * cout2 * 2 + cout2 * cout * 2)  # the 1x1's input never comes back from HBM
+            extra["then"] = dict(name=name2, out=out2, act=act2)
+        self._emit(_lib.OD_OP_CONV, d, name=name, flops=flops, bytes=nbytes, shape=(m, cout, k * k * cin),
+                   # the op's tensors, for per-layer parity checks (tests/test_gpu_fullsize.py)
+                   kind="conv", x=x, res=res, res_mode=res_mode, out=None if isinstance(out, int) else out,
+                   stride=stride, ksize=k, act=act, out_f32=out_f32, **extra)
+        return (out, ho, wo) if then is None else (out, ho, wo, out2)
 
     def _conv_grouped(self, name, xs, dims, cin, cout, act, outs=None, out_f32=False, obs=0, ops=0):
         """One 3x3 stride-1 layer over several maps in ONE plan op (od_conv_desc.nseg): the prediction module shared by the
         pyramid levels.  xs: input tensors, dims: [(h, w)], outs: raw output pointers (else dense f16 buffers are made)."""
-        wt, sc, bi = self._dev[name]
-        if outs is None:
-            bufs = [self._buf(h, w, cout) for h, w in dims]
-            outs = [t.data_ptr() for t in bufs]
-        else:
-            bufs = [None] * len(dims)
-        d = _lib.ConvDesc()
-        d.w, d.scale, d.bias = wt.data_ptr(), sc.data_ptr(), bi.data_ptr()
-        d.B, d.Cin, d.Cout, d.ksize, d.stride = self.B, cin, cout, 3, 1
-        d.act, d.alpha = _lib.ACT_ENUM[act[0] if act else None], float(act[1]) if act else 0.0
-        d.out_dtype = _lib.OD_DT_F32 if out_f32 else _lib.OD_DT_F16
-        d.out_batch_stride, d.out_pix_stride = obs, ops
-        d.tile_cfg = self.tile_cfg.get(name, self.auto_cfg)
-        d.nseg = len(xs)
-        for i, (x, (h, w), o) in enumerate(zip(xs, dims, outs)):
-            d.seg_x[i], d.seg_out[i], d.seg_H[i], d.seg_W[i] = x.data_ptr(), o, h, w
-        op = _lib.PlanOp()
-        op.kind = _lib.OD_OP_CONV
-        op.conv = d
-        self.ops.append(op)
+        bufs = [self._buf(h, w, cout) for h, w in dims] if outs is None else [None] * len(dims)
+        d = desc.conv_grouped(xs, dims, bufs if outs is None else outs, *self._dev[name], self.B, cin, cout, act,
+                              out_f32=out_f32, out_batch_stride=obs, out_pix_stride=ops,
+                              tile_cfg=self.tile_cfg.get(name, self.auto_cfg))
         m = sum(self.B * h * w for h, w in dims)
         if self.splitk and max(self.B * h * w for h, w in dims) * cout <= (1 << 22):
             # small maps (batch 1): the library runs the segments as separate launches and may split K for them
             self._splitk_elems = max(self._splitk_elems, max(self.B * h * w for h, w in dims) * cout)
-            self._splitk_descs.append(len(self.ops) - 1)
-        osz = 4 if out_f32 else 2
-        self.op_info.append(dict(name=name, flops=2.0 * m * cout * 9 * cin,
-                                 bytes=float(m * cin * 2 + m * cout * osz + cout * 9 * cin * 2), shape=(m, cout, 9 * cin),
-                                 kind="conv_group", xs=list(xs), dims=list(dims), outs=bufs, act=act, out_f32=out_f32))
+            self._splitk_descs.append(len(self.ops))
+        self._emit(_lib.OD_OP_CONV, d, name=name, flops=2.0 * m * cout * 9 * cin,
+                   bytes=float(m * cin * 2 + m * cout * (4 if out_f32 else 2) + cout * 9 * cin * 2), shape=(m, cout, 9 * cin),
+                   kind="conv_group", xs=list(xs), dims=list(dims), outs=bufs, act=act, out_f32=out_f32)
         return bufs
 
     def _bneck(self, name, x, h, w, ch, act):
         """one fused residual block (1x1 ch -> ch/2, 3x3 ch/2 -> ch, + x): od_bottleneck_fwd"""
-        w1, s1, b1 = self._dev[name + ".a"]
-        w3, s3, b3 = self._dev[name + ".b"]
         out = self._buf(h, w, ch)
-        d = _lib.BneckDesc()
-        d.x, d.out = x.data_ptr(), out.data_ptr()
-        d.w1, d.scale1, d.bias1 = w1.data_ptr(), s1.data_ptr(), b1.data_ptr()
-        d.w3, d.scale3, d.bias3 = w3.data_ptr(), s3.data_ptr(), b3.data_ptr()
-        d.B, d.H, d.W, d.C = self.B, h, w, ch
-        d.act, d.alpha = _lib.ACT_ENUM[act[0] if act else None], float(act[1]) if act else 0.0
-        op = _lib.PlanOp()
-        op.kind = _lib.OD_OP_BNECK
-        op.bneck = d
-        self.ops.append(op)
         m = self.B * h * w
-        self.op_info.append(dict(name=name, flops=2.0 * m * (ch * (ch // 2) + 9 * (ch // 2) * ch),
-                                 bytes=float(2 * m * ch * 2 + (ch * ch // 2 + 9 * ch * ch // 2) * 2),
-                                 shape=(m, ch, 10 * (ch // 2)), kind="bneck", x=x, out=out, act=act))
+        d = desc.bneck(x, *self._dev[name + ".a"], *self._dev[name + ".b"], out, self.B, h, w, ch, act)
+        self._emit(_lib.OD_OP_BNECK, d, name=name, flops=2.0 * m * (ch * (ch // 2) + 9 * (ch // 2) * ch),
+                   bytes=float(2 * m * ch * 2 + (ch * ch // 2 + 9 * ch * ch // 2) * 2),
+                   shape=(m, ch, 10 * (ch // 2)), kind="bneck", x=x, out=out, act=act)
         return out
 
     def _build(self, bact, hact):
@@ -363,40 +310,20 @@ class Net:
         fuse_stem = self.fuse_blocks and self.lib.od_stem_supported(H, Wd)
         if fuse_stem:
             # first two layers in one launch (od_stem_fwd): uint8 in, f16 [B,H/2,W/2,64] out
-            w0, sc0, bi0 = self._dev["b.conv0"]
-            w3, sc3, bi3 = self._dev["b.down1"]
             x = self._buf(H // 2, Wd // 2, 64)
-            d = _lib.StemDesc()
-            d.x, d.out = self.input.data_ptr(), x.data_ptr()
-            d.w0, d.scale0, d.bias0 = w0.data_ptr(), sc0.data_ptr(), bi0.data_ptr()
-            d.w3, d.scale3, d.bias3 = w3.data_ptr(), sc3.data_ptr(), bi3.data_ptr()
-            d.B, d.H, d.W = B, H, Wd
-            d.act, d.alpha = _lib.ACT_ENUM[bact[0]], float(bact[1])
-            op = _lib.PlanOp()
-            op.kind = _lib.OD_OP_STEM
-            op.stem = d
-            self.ops.append(op)
             m1 = B * (H // 2) * (Wd // 2)
-            self.op_info.append(dict(name="b.stem", flops=2.0 * B * H * Wd * 32 * 27 + 2.0 * m1 * 64 * 288,
-                                     bytes=float(B * H * Wd * 3 + m1 * 64 * 2), shape=(m1, 64, 288 + 27),
-                                     kind="stem", x=self.input, out=x, act=bact))
+            d = desc.stem(self.input, *self._dev["b.conv0"], *self._dev["b.down1"], x, B, H, Wd, bact)
+            self._emit(_lib.OD_OP_STEM, d, name="b.stem", flops=2.0 * B * H * Wd * 32 * 27 + 2.0 * m1 * 64 * 288,
+                       bytes=float(B * H * Wd * 3 + m1 * 64 * 2), shape=(m1, 64, 288 + 27),
+                       kind="stem", x=self.input, out=x, act=bact)
         else:
             # first layer (uint8 in)
-            wt, sc, bi = self._dev["b.conv0"]
             x = self._buf(H, Wd, 32)
-            d = _lib.ConvDesc()
-            d.x, d.w, d.scale, d.bias, d.out = (self.input.data_ptr(), wt.data_ptr(), sc.data_ptr(), bi.data_ptr(),
-                                                x.data_ptr())
-            d.B, d.H, d.W, d.Cin, d.Cout = B, H, Wd, 3, 32
-            d.ksize, d.stride = 3, 1
-            d.act, d.alpha = _lib.ACT_ENUM[bact[0]], float(bact[1])
-            op = _lib.PlanOp()
-            op.kind = _lib.OD_OP_CONV_FIRST
-            op.conv = d
-            self.ops.append(op)
-            self.op_info.append(dict(name="b.conv0", flops=2.0 * B * H * Wd * 32 * 27,
-                                     bytes=float(B * H * Wd * (3 + 64)), shape=(B * H * Wd, 32, 27),
-                                     kind="first", x=self.input, out=x, act=bact))
+            # (od_conv_first_fwd has no tile table: tile_cfg stays 0)
+            d = desc.conv(self.input, *self._dev["b.conv0"], x, B, H, Wd, 3, 32, 3, 1, bact, tile_cfg=0)
+            self._emit(_lib.OD_OP_CONV_FIRST, d, name="b.conv0", flops=2.0 * B * H * Wd * 32 * 27,
+                       bytes=float(B * H * Wd * (3 + 64)), shape=(B * H * Wd, 32, 27),
+                       kind="first", x=self.input, out=x, act=bact)
         h, w, cin = H, Wd, 32
         taps = []
         for si, (n, ch) in enumerate(W.STAGES, start=1):

@@ -7,14 +7,19 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
-from .net import Context, _stream_ptr, pack_conv_weight, pack_first_weight, pad_vec
+from . import _lib, desc
+from .net import Context, _stream_ptr, pack_layer
 
 
 def _ctx(t: torch.Tensor) -> Context:
     if not t.is_cuda:
         raise _lib.OdError("object_detector_amd ops need device tensors (MI355X); there is no CPU path")
     return Context.get(t.device)
+
+
+def _upload(w_ohwi, scale, bias, device, first=False):
+    """pack_layer's three host arrays as device tensors."""
+    return tuple(torch.from_numpy(a).to(device) for a in pack_layer(w_ohwi, scale, bias, first))
 
 
 def conv2d(x: torch.Tensor, w_ohwi: np.ndarray, scale: np.ndarray, bias: np.ndarray, stride=1, act=None, alpha=0.0,
@@ -27,37 +32,21 @@ def conv2d(x: torch.Tensor, w_ohwi: np.ndarray, scale: np.ndarray, bias: np.ndar
     assert x.dtype == torch.float16 and x.is_contiguous()
     B, H, Wd, Cin = x.shape
     Cout, k = w_ohwi.shape[0], w_ohwi.shape[1]
-    wp = torch.from_numpy(pack_conv_weight(w_ohwi)).to(x.device)
-    npad = wp.shape[0]
-    sc = torch.from_numpy(pad_vec(np.asarray(scale, np.float32), npad)).to(x.device)
-    bi = torch.from_numpy(pad_vec(np.asarray(bias, np.float32), npad)).to(x.device)
+    layer = _upload(w_ohwi, scale, bias, x.device)
     Ho, Wo = (H + stride - 1) // stride, (Wd + stride - 1) // stride
     if out is None:
         out = torch.empty((B, Ho, Wo, Cout), dtype=torch.float32 if out_f32 else torch.float16, device=x.device)
-    d = _lib.ConvDesc()
-    d.x, d.w, d.scale, d.bias, d.out = x.data_ptr(), wp.data_ptr(), sc.data_ptr(), bi.data_ptr(), out.data_ptr()
-    d.res = res.data_ptr() if res is not None else None
-    d.B, d.H, d.W, d.Cin, d.Cout = B, H, Wd, Cin, Cout
-    d.ksize, d.stride = k, stride
-    d.act, d.alpha = _lib.ACT_ENUM[act], float(alpha)
-    d.res_mode = {"none": _lib.OD_RES_NONE, "same": _lib.OD_RES_SAME, "up2": _lib.OD_RES_UP2}[res_mode]
-    d.out_dtype = _lib.OD_DT_F32 if out_f32 else _lib.OD_DT_F16
-    d.out_batch_stride, d.out_pix_stride = out_batch_stride, out_pix_stride
-    d.tile_cfg = tile_cfg
-    if splitk != 1:
-        if splitk_ws is None:
-            splitk_ws = torch.empty(32 * B * Ho * Wo * Cout, dtype=torch.float32, device=x.device)
-        d.splitk, d.splitk_workspace, d.splitk_workspace_bytes = splitk, splitk_ws.data_ptr(), splitk_ws.numel() * 4
-    out2 = None
+    if splitk != 1 and splitk_ws is None:
+        splitk_ws = torch.empty(32 * B * Ho * Wo * Cout, dtype=torch.float32, device=x.device)
+    out2 = then = None
     if next_pointwise is not None:
         w2, scale2, bias2, act2, alpha2 = next_pointwise
         assert w2.shape[1:] == (1, 1, Cout)
-        w2p = torch.from_numpy(pack_conv_weight(w2)).to(x.device)
-        sc2 = torch.from_numpy(pad_vec(np.asarray(scale2, np.float32), w2p.shape[0])).to(x.device)
-        bi2 = torch.from_numpy(pad_vec(np.asarray(bias2, np.float32), w2p.shape[0])).to(x.device)
         out2 = torch.empty((B, Ho, Wo, w2.shape[0]), dtype=torch.float16, device=x.device)
-        d.w2, d.scale2, d.bias2, d.out2 = w2p.data_ptr(), sc2.data_ptr(), bi2.data_ptr(), out2.data_ptr()
-        d.Cout2, d.act2, d.alpha2 = w2.shape[0], _lib.ACT_ENUM[act2], float(alpha2)
+        then = _upload(w2, scale2, bias2, x.device) + (out2, w2.shape[0], act2, alpha2)
+    d = desc.conv(x, *layer, out, B, H, Wd, Cin, Cout, k, stride, act, alpha, res=res, res_mode=res_mode, out_f32=out_f32,
+                  out_batch_stride=out_batch_stride, out_pix_stride=out_pix_stride, tile_cfg=tile_cfg, then=then,
+                  splitk=None if splitk == 1 else (splitk, splitk_ws, splitk_ws.numel() * 4))
     _lib.check(ctx.lib.od_conv2d_fwd(ctx.handle, C.byref(d), _stream_ptr()), "od_conv2d_fwd")
     if splitk != 1:
         out._splitk_ws = splitk_ws  # keep the workspace alive / inspectable
@@ -74,21 +63,13 @@ def conv2d_grouped(xs, w_ohwi: np.ndarray, scale: np.ndarray, bias: np.ndarray, 
     ctx = _ctx(xs[0])
     B, Cin = xs[0].shape[0], xs[0].shape[3]
     Cout, k = w_ohwi.shape[0], w_ohwi.shape[1]
-    wp = torch.from_numpy(pack_conv_weight(w_ohwi)).to(xs[0].device)
-    sc = torch.from_numpy(pad_vec(np.asarray(scale, np.float32), wp.shape[0])).to(xs[0].device)
-    bi = torch.from_numpy(pad_vec(np.asarray(bias, np.float32), wp.shape[0])).to(xs[0].device)
+    layer = _upload(w_ohwi, scale, bias, xs[0].device)
     outs = [torch.empty(tuple(x.shape[:3]) + (Cout,), dtype=torch.float32 if out_f32 else torch.float16, device=x.device)
             for x in xs]
-    d = _lib.ConvDesc()
-    d.w, d.scale, d.bias = wp.data_ptr(), sc.data_ptr(), bi.data_ptr()
-    d.B, d.Cin, d.Cout, d.ksize, d.stride = B, Cin, Cout, k, 1
-    d.act, d.alpha = _lib.ACT_ENUM[act], float(alpha)
-    d.out_dtype = _lib.OD_DT_F32 if out_f32 else _lib.OD_DT_F16
-    d.tile_cfg = tile_cfg
-    d.nseg = len(xs)
-    for i, (x, o) in enumerate(zip(xs, outs)):
+    for x in xs:
         assert x.dtype == torch.float16 and x.is_contiguous() and x.shape[0] == B and x.shape[3] == Cin
-        d.seg_x[i], d.seg_out[i], d.seg_H[i], d.seg_W[i] = x.data_ptr(), o.data_ptr(), x.shape[1], x.shape[2]
+    d = desc.conv_grouped(xs, [tuple(x.shape[1:3]) for x in xs], outs, *layer, B, Cin, Cout, act, alpha, out_f32=out_f32,
+                          tile_cfg=tile_cfg, ksize=k)
     _lib.check(ctx.lib.od_conv2d_fwd(ctx.handle, C.byref(d), _stream_ptr()), "od_conv2d_fwd(grouped)")
     torch.cuda.current_stream().synchronize()  # the packed weights above are temporaries
     return outs
@@ -101,22 +82,9 @@ def bottleneck(x: torch.Tensor, w1_ohwi: np.ndarray, scale1, bias1, w3_ohwi: np.
     assert x.dtype == torch.float16 and x.is_contiguous()
     B, H, Wd, Cc = x.shape
     assert w1_ohwi.shape == (Cc // 2, 1, 1, Cc) and w3_ohwi.shape == (Cc, 3, 3, Cc // 2)
-    keep = []
-
-    def dev(a):
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(x.device)
-        keep.append(t)
-        return t
-    w1p, w3p = dev(pack_conv_weight(w1_ohwi)), dev(pack_conv_weight(w3_ohwi))
     out = torch.empty_like(x)
-    d = _lib.BneckDesc()
-    d.x, d.out, d.w1, d.w3 = x.data_ptr(), out.data_ptr(), w1p.data_ptr(), w3p.data_ptr()
-    d.scale1 = dev(pad_vec(np.asarray(scale1, np.float32), w1p.shape[0])).data_ptr()
-    d.bias1 = dev(pad_vec(np.asarray(bias1, np.float32), w1p.shape[0])).data_ptr()
-    d.scale3 = dev(pad_vec(np.asarray(scale3, np.float32), w3p.shape[0])).data_ptr()
-    d.bias3 = dev(pad_vec(np.asarray(bias3, np.float32), w3p.shape[0])).data_ptr()
-    d.B, d.H, d.W, d.C = B, H, Wd, Cc
-    d.act, d.alpha = _lib.ACT_ENUM[act], float(alpha)
+    d = desc.bneck(x, *_upload(w1_ohwi, scale1, bias1, x.device), *_upload(w3_ohwi, scale3, bias3, x.device), out,
+                   B, H, Wd, Cc, act, alpha)
     _lib.check(ctx.lib.od_bottleneck_fwd(ctx.handle, C.byref(d), _stream_ptr()), "od_bottleneck_fwd")
     torch.cuda.current_stream().synchronize()  # the packed weights above are temporaries
     return out
@@ -128,22 +96,9 @@ def stem(x_u8: torch.Tensor, w0_ohwi: np.ndarray, scale0, bias0, w3_ohwi: np.nda
     assert x_u8.dtype == torch.uint8 and x_u8.is_contiguous()
     B, H, Wd, _ = x_u8.shape
     assert w0_ohwi.shape == (32, 3, 3, 3) and w3_ohwi.shape == (64, 3, 3, 32)
-    keep = []
-
-    def dev(a):
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(x_u8.device)
-        keep.append(t)
-        return t
-    w0p, w3p = dev(pack_first_weight(w0_ohwi)), dev(pack_conv_weight(w3_ohwi))
     out = torch.empty((B, H // 2, Wd // 2, 64), dtype=torch.float16, device=x_u8.device)
-    d = _lib.StemDesc()
-    d.x, d.out, d.w0, d.w3 = x_u8.data_ptr(), out.data_ptr(), w0p.data_ptr(), w3p.data_ptr()
-    d.scale0 = dev(np.asarray(scale0, np.float32)).data_ptr()
-    d.bias0 = dev(np.asarray(bias0, np.float32)).data_ptr()
-    d.scale3 = dev(pad_vec(np.asarray(scale3, np.float32), w3p.shape[0])).data_ptr()
-    d.bias3 = dev(pad_vec(np.asarray(bias3, np.float32), w3p.shape[0])).data_ptr()
-    d.B, d.H, d.W = B, H, Wd
-    d.act, d.alpha = _lib.ACT_ENUM[act], float(alpha)
+    d = desc.stem(x_u8, *_upload(w0_ohwi, scale0, bias0, x_u8.device, first=True),
+                  *_upload(w3_ohwi, scale3, bias3, x_u8.device), out, B, H, Wd, act, alpha)
     _lib.check(ctx.lib.od_stem_fwd(ctx.handle, C.byref(d), _stream_ptr()), "od_stem_fwd")
     torch.cuda.current_stream().synchronize()
     return out
@@ -154,12 +109,10 @@ def conv_first(x_u8: torch.Tensor, w_ohwi: np.ndarray, scale, bias, act="leaky",
     assert x_u8.dtype == torch.uint8 and x_u8.is_contiguous()
     B, H, Wd, _ = x_u8.shape
     Cout = w_ohwi.shape[0]
-    wp = torch.from_numpy(pack_first_weight(w_ohwi)).to(x_u8.device)
-    sc = torch.from_numpy(np.asarray(scale, np.float32)).to(x_u8.device)
-    bi = torch.from_numpy(np.asarray(bias, np.float32)).to(x_u8.device)
+    wp, sc, bi = _upload(w_ohwi, scale, bias, x_u8.device, first=True)
     out = torch.empty((B, H, Wd, Cout), dtype=torch.float16, device=x_u8.device)
     _lib.check(ctx.lib.od_conv_first_fwd(ctx.handle, x_u8.data_ptr(), wp.data_ptr(), sc.data_ptr(), bi.data_ptr(),
-                                         out.data_ptr(), B, H, Wd, Cout, _lib.ACT_ENUM[act], float(alpha),
+                                         out.data_ptr(), B, H, Wd, Cout, *desc.act_pair(act, alpha),
                                          _stream_ptr()), "od_conv_first_fwd")
     return out
 

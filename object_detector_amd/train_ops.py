@@ -6,14 +6,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
-from .net import Context, _stream_ptr
-
-
-def _ctx(t):
-    if not t.is_cuda:
-        raise _lib.OdError("training ops need device tensors (MI355X); there is no CPU path")
-    return Context.get(t.device)
+from . import _lib, desc
+from .net import _stream_ptr
+from .ops import _ctx
 
 
 def bn_stats(z, gamma, beta, eps=1e-3, run_mean=None, run_var=None, momentum=0.99):
@@ -26,8 +21,7 @@ def bn_stats(z, gamma, beta, eps=1e-3, run_mean=None, run_var=None, momentum=0.9
     ws = torch.empty(wsb, dtype=torch.uint8, device=z.device)
     _lib.check(ctx.lib.od_bn_stats(ctx.handle, z.data_ptr(), M, Cc, gamma.data_ptr(), beta.data_ptr(), float(eps),
                                    out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(),
-                                   run_mean.data_ptr() if run_mean is not None else None,
-                                   run_var.data_ptr() if run_var is not None else None, float(momentum),
+                                   desc.ptr(run_mean), desc.ptr(run_var), float(momentum),
                                    ws.data_ptr(), wsb, _stream_ptr()), "od_bn_stats")
     return out
 
@@ -36,10 +30,9 @@ def scale_act(z, scale, shift, act=None, alpha=0.0, res=None, res_mode="none"):
     ctx = _ctx(z)
     B, H, W, Cc = z.shape
     y = torch.empty_like(z)
-    rm = {"none": 0, "same": 1, "up2": 2}[res_mode]
     _lib.check(ctx.lib.od_scale_act(ctx.handle, z.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                    res.data_ptr() if res is not None else None, rm, y.data_ptr(), B, H, W, Cc,
-                                    _lib.ACT_ENUM[act], float(alpha), _stream_ptr()), "od_scale_act")
+                                    desc.ptr(res), desc.res_code(res_mode), y.data_ptr(), B, H, W, Cc,
+                                    *desc.act_pair(act, alpha), _stream_ptr()), "od_scale_act")
     return y
 
 
@@ -54,10 +47,9 @@ def bn_bwd(z, dy, scale, shift, mean, rstd, act=None, alpha=0.0, bn=True, dgamma
     wsb = ctx.lib.od_bn_workspace_bytes(M, Cc) + 2 * Cc * 4
     ws = torch.empty(wsb, dtype=torch.uint8, device=z.device)
     _lib.check(ctx.lib.od_bn_bwd(ctx.handle, z.data_ptr(), dy.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                                 mean.data_ptr() if mean is not None else None,
-                                 rstd.data_ptr() if rstd is not None else None, M, Cc, _lib.ACT_ENUM[act], float(alpha),
-                                 int(bn), dgamma.data_ptr(), dbeta.data_ptr(), dz.data_ptr(), ws.data_ptr(), wsb,
-                                 _stream_ptr()), "od_bn_bwd")
+                                 desc.ptr(mean), desc.ptr(rstd), M, Cc, *desc.act_pair(act, alpha), int(bn),
+                                 dgamma.data_ptr(), dbeta.data_ptr(), dz.data_ptr(), ws.data_ptr(), wsb, _stream_ptr()),
+               "od_bn_bwd")
     return dz, dgamma, dbeta
 
 
@@ -98,16 +90,8 @@ def conv_packed(x, w_packed, scale, bias, Cin, Cout, ksize, stride=1, act=None, 
         Ho, Wo = (H + stride - 1) // stride, (W + stride - 1) // stride
     if out is None:
         out = torch.empty((B, Ho, Wo, Cout), dtype=torch.float16, device=x.device)
-    d = _lib.ConvDesc()
-    d.x, d.w, d.scale, d.bias, d.out = x.data_ptr(), w_packed.data_ptr(), scale.data_ptr(), bias.data_ptr(), out.data_ptr()
-    d.res = res.data_ptr() if res is not None else None
-    d.B, d.H, d.W, d.Cin, d.Cout = B, H, W, Cin, Cout
-    d.ksize, d.stride = ksize, stride
-    d.act, d.alpha = _lib.ACT_ENUM[act], float(alpha)
-    d.res_mode = {"none": 0, "same": 1, "up2": 2}[res_mode]
-    d.out_dtype = _lib.OD_DT_F16
-    d.tile_cfg = tile_cfg
-    d.transposed = int(transposed)
+    d = desc.conv(x, w_packed, scale, bias, out, B, H, W, Cin, Cout, ksize, stride, act, alpha, res=res, res_mode=res_mode,
+                  tile_cfg=tile_cfg, transposed=transposed)
     _lib.check(ctx.lib.od_conv2d_fwd(ctx.handle, C.byref(d), _stream_ptr()), "od_conv2d_fwd")
     return out
 

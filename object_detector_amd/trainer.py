@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, train_ops as T, weights as W
+from . import _lib, desc, weights as W
 from .net import Context, _stream_ptr
 from .ops import BOX_MODES
 from .pb import PriorBoxes
@@ -38,7 +38,9 @@ def lr_multiplier(name: str, table=None) -> float:
 
 class _Node:
     __slots__ = ("name", "x", "out", "res", "res_mode", "H", "W", "Cin", "Cout", "k", "stride", "act", "bn", "z",
-                 "mean", "rstd", "scale", "shift", "first", "pred_off", "pred_rows", "need_dx")
+                 "mean", "rstd", "scale", "shift", "first", "pred_off", "pred_rows", "need_dx",
+                 # constants of the node, computed once: output size, rows, od_scale_act / od_bn_bwd arguments, od_bn_stats workspace
+                 "Ho", "Wo", "M", "act_enum", "alpha", "res_code", "bn_wsb")
 
 
 class Trainer:
@@ -94,7 +96,7 @@ class Trainer:
         for name, (_n, cin, cout, k, _s, bn) in self.specs.items():
             for kind, n in (("w", cout * k * k * cin),) + ((("gamma", cout), ("beta", cout)) if bn else (("bias", cout),)):
                 self.seg[(name, kind)] = (off, n)
-                off += (n + 3) // 4 * 4
+                off += desc.pad_to(n, 4)
         self.n_flat = off
         host = np.zeros(off, np.float32)
         for (name, kind), (o, n) in self.seg.items():
@@ -108,20 +110,20 @@ class Trainer:
         for n, sp in self.specs.items():
             if sp[5]:
                 rviews[n] = roff
-                roff += 2 * ((sp[2] + 3) // 4 * 4)
+                roff += 2 * desc.pad_to(sp[2], 4)
         rhost = np.zeros(max(roff, 4), np.float32)
         for n, o in rviews.items():
             c = self.specs[n][2]
-            cp = (c + 3) // 4 * 4
+            cp = desc.pad_to(c, 4)
             rhost[o:o + c] = np.asarray(params[n + ".mean"], np.float32)
             rhost[o + cp:o + cp + c] = np.asarray(params[n + ".var"], np.float32)
         self.run_stats = torch.from_numpy(rhost).to(dev)
         self.run_stats_saved = torch.empty_like(self.run_stats)
         self.run_mean = {n: self.run_stats[o:o + self.specs[n][2]] for n, o in rviews.items()}
-        self.run_var = {n: self.run_stats[o + (self.specs[n][2] + 3) // 4 * 4:][:self.specs[n][2]] for n, o in rviews.items()}
+        self.run_var = {n: self.run_stats[o + desc.pad_to(self.specs[n][2], 4):][:self.specs[n][2]] for n, o in rviews.items()}
         # per-channel stand-ins (scale / shift / bias / sink) cover every layer's Cout, read in whole 256-channel pads: the
         # prediction conv of a many-class head has Cout = 8 * (NC + 6), beyond the backbone's widths from NC = 251
-        maxpad = max(2048, max((s[2] + 255) // 256 * 256 for s in self.specs.values()))
+        maxpad = max(2048, max(desc.pad_to(s[2], 256) for s in self.specs.values()))
         self.ones = torch.ones(maxpad, dtype=torch.float32, device=dev)
         self.zeros = torch.zeros(maxpad, dtype=torch.float32, device=dev)
         self.in_scale = torch.full((32,), 1.0 / 255.0, dtype=torch.float32, device=dev)
@@ -136,7 +138,18 @@ class Trainer:
             self.wf[name] = torch.zeros((cp, kp), dtype=torch.float16, device=dev)
             cp2, kp2 = _lib.conv_weight_dims(cin, cout, k)
             self.wb[name] = torch.zeros((cp2, kp2), dtype=torch.float16, device=dev)
+        layers = []
+        for name, (_n, cin, cout, k, _s, _bn) in self.specs.items():
+            if name == "b.conv0":
+                continue
+            L = _lib.PackLayer()
+            L.w_offset = self.seg[(name, "w")][0]
+            L.w_fwd, L.w_bwd = self.wf[name].data_ptr(), self.wb[name].data_ptr()
+            L.Cout, L.Cin, L.ksize = cout, cin, k
+            layers.append(L)
+        self._pack_table, self._pack_n = self._device_table(layers), len(layers)
         self._repack()
+        self._sgd_key = None  # (lr, weight decay, multipliers) of the device table sgd() last built
         # ---- graph ------------------------------------------------------------------------------------------------
         self.tensors = {"img": torch.zeros((self.B, self.H0, self.W0, 3), dtype=torch.uint8, device=dev)}
         self.gradbuf = {}
@@ -146,7 +159,7 @@ class Trainer:
         self.grad_pred = torch.zeros_like(self.pred)
         self.losses = torch.zeros(4, dtype=torch.float32, device=dev)
         self.loss_ws = torch.empty(self.lib.od_loss_workspace_bytes(self.B, self.P), dtype=torch.uint8, device=dev)
-        mx = max(self.B * (n.H // n.stride) * (n.W // n.stride) * n.Cout for n in self.nodes)
+        mx = max(n.M * n.Cout for n in self.nodes)
         # dz of the node being processed: three rotating buffers, because the weight gradient of node k runs on a second
         # stream while the main stream already computes node k-1's dz (backward())
         self.dzs = [torch.empty(mx, dtype=torch.float16, device=dev) for _ in range(3)]
@@ -177,23 +190,33 @@ class Trainer:
         self.max_consecutive_skips = 50  # fit() gives up after this many skipped steps in a row (see diverged())
         self._buckets = self._make_buckets(int(self.bucket_mb * (1 << 20) / 4)) if self.cstream is not None else []
         self._next_bucket = 0
-        mxc = max(self.lib.od_bn_workspace_bytes(self.B * (n.H // n.stride) * (n.W // n.stride), n.Cout) + 2 * n.Cout * 4
-                  for n in self.nodes)
-        self.bn_ws = torch.empty(mxc, dtype=torch.uint8, device=dev)
+        self.bn_ws = torch.empty(max(n.bn_wsb + 2 * n.Cout * 4 for n in self.nodes), dtype=torch.uint8, device=dev)
         # BatchNorm statistics from the conv epilogue (od_conv_desc.bn_partials): one partial row per m-tile, at most M / 64
         # rows of 2 x Cout floats.  OFF by default: measured neutral (profiles/r02/train_bn_stats_fusion.txt: the separate
         # pass reads z hot out of L2 / MALL for 0.46 ms per step; the epilogue sums + more partial rows + giving up the
         # 8-wave kernel for those layers cost 0.5 ms).  OD_TRAIN_FUSE_BN_STATS=1 turns it on.
         self.fuse_bn_stats = os.environ.get("OD_TRAIN_FUSE_BN_STATS", "0") == "1"
-        self._bn_rows = {}
-        mxp = max(((self.B * (n.H // n.stride) * (n.W // n.stride) + 63) // 64) * 2 * n.Cout for n in self.nodes)
-        self.bn_part = torch.empty(mxp, dtype=torch.float32, device=dev)
+        self.bn_part = torch.empty(max(desc.pad_to(n.M, 64) // 64 * 2 * n.Cout for n in self.nodes), dtype=torch.float32,
+                                   device=dev)
+        self._bn_rows = {}  # node -> partial rows its statistics launch writes
+        for n in self.nodes if self.fuse_bn_stats else ():
+            if n.first or n.pred_off is not None:
+                continue
+            d = self._fwd_desc(n, self.tensors[n.x], n.z, bn_partials=self.bn_part)
+            rows = self._bn_rows[n] = self.lib.od_conv2d_fwd_bn_rows(self.ctx.handle, C.byref(d))
+            if rows <= 0 or rows * 2 * n.Cout > self.bn_part.numel():
+                raise _lib.OdError(f"bn_partials too small for {n.name}: {rows} rows")
+        # the prediction conv's bias, read in whole 256-channel pads like every scale / bias vector
+        nb = self.seg[("h.out", "bias")][1]
+        self._bias_pad = torch.zeros(desc.pad_to(nb, 256), dtype=torch.float32, device=dev) if nb % 256 else None
+        self._first_ws = torch.empty(self.lib.od_conv_first_bwd_weight_workspace_bytes(self.ctx.handle, self.B, self.H0, self.W0),
+                                     dtype=torch.uint8, device=dev)
 
     # ------------------------------------------------------------------------------------------------------------
     def _make_buckets(self, min_elems):
         layers = []  # (lo, hi, name) per layer, in buffer order
         for name in self.specs:
-            offs = [(o, o + (n + 3) // 4 * 4) for (nm, _k), (o, n) in self.seg.items() if nm == name]
+            offs = [(o, o + desc.pad_to(n, 4)) for (nm, _k), (o, n) in self.seg.items() if nm == name]
             layers.append((min(o for o, _ in offs), max(h for _, h in offs), name))
         return make_buckets(layers, self.n_flat, min_elems)
 
@@ -236,17 +259,6 @@ class Trainer:
         return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
 
     def _repack(self):
-        if getattr(self, "_pack_table", None) is None:
-            layers = []
-            for name, (_n, cin, cout, k, _s, _bn) in self.specs.items():
-                if name == "b.conv0":
-                    continue
-                L = _lib.PackLayer()
-                L.w_offset = self.seg[(name, "w")][0]
-                L.w_fwd, L.w_bwd = self.wf[name].data_ptr(), self.wb[name].data_ptr()
-                L.Cout, L.Cin, L.ksize = cout, cin, k
-                layers.append(L)
-            self._pack_table, self._pack_n = self._device_table(layers), len(layers)
         w0 = self.view(self.params, "b.conv0", "w")
         wf0 = self.wf["b.conv0"]
         wf0.zero_()
@@ -272,7 +284,11 @@ class Trainer:
         n.name, n.x, n.out, n.res, n.res_mode = name, x, out, res, res_mode
         n.H, n.W, n.Cin, n.Cout, n.k, n.stride, n.act, n.bn = H, Wd, cin, cout, k, stride, act, bn
         n.first, n.pred_off, n.pred_rows, n.need_dx = first, pred_off, pred_rows, need_dx
-        Ho, Wo = H // stride, Wd // stride
+        Ho, Wo = n.Ho, n.Wo = H // stride, Wd // stride
+        n.M = self.B * Ho * Wo
+        n.act_enum, n.alpha = desc.act_pair(act)
+        n.res_code = desc.res_code(res_mode)
+        n.bn_wsb = self.lib.od_bn_workspace_bytes(n.M, cout)  # a pure function of (M, C): asked once, not per step
         dev = self.device
         if pred_off is None:
             n.z = torch.empty((self.B, Ho, Wo, cout), dtype=torch.float16, device=dev)
@@ -311,26 +327,21 @@ class Trainer:
             self._add_node("h.out", cur, f"L{li}.out", h, w, None, pred_off=off, pred_rows=rows)
             off += rows
         assert off == self.P
+        self._build_wgrad_slabs()
 
     # ------------------------------------------------------------------------------------------------------------
-    def _conv_raw(self, n, x, out, out_f32=False, obs=0, ops=0, bias=None, bn_partials=None):
-        d = _lib.ConvDesc()
-        d.x, d.w = x.data_ptr(), self.wf[n.name].data_ptr()
-        d.scale, d.bias = self.ones.data_ptr(), (bias if bias is not None else self.zeros).data_ptr()
-        d.out = out if isinstance(out, int) else out.data_ptr()
-        d.B, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = self.B, n.H, n.W, n.Cin, n.Cout, n.k, n.stride
-        d.act, d.res_mode, d.tile_cfg = _lib.OD_ACT_LINEAR, _lib.OD_RES_NONE, -1
-        d.out_dtype = _lib.OD_DT_F32 if out_f32 else _lib.OD_DT_F16
-        d.out_batch_stride, d.out_pix_stride = obs, ops
-        if bn_partials is not None:  # BatchNorm partial sums from the conv epilogue (no separate pass over z)
-            d.bn_partials, d.bn_partials_bytes = bn_partials.data_ptr(), bn_partials.numel() * 4
-            rows = self._bn_rows.get(n)
-            if rows is None:
-                rows = self._bn_rows[n] = self.lib.od_conv2d_fwd_bn_rows(self.ctx.handle, C.byref(d))
-                if rows <= 0 or rows * 2 * n.Cout > bn_partials.numel():
-                    raise _lib.OdError(f"bn_partials too small for {n.name}: {rows} rows")
+    def _fwd_desc(self, n, x, out, bias=None, bn_partials=None):
+        """od_conv_desc of node n's raw forward convolution (identity scale, linear epilogue): z f16 into `out`, or for a
+        prediction conv f32 logits plus `bias` into the level's rows of pred (`out` = the address of the first of them)."""
+        pred = n.pred_off is not None
+        return desc.conv(x, self.wf[n.name], self.ones, self.zeros if bias is None else bias, out, self.B, n.H, n.W, n.Cin,
+                         n.Cout, n.k, n.stride, out_f32=pred, out_batch_stride=self.P * self.C if pred else 0,
+                         out_pix_stride=n.Cout if pred else 0,
+                         bn_partials=None if bn_partials is None else (bn_partials, bn_partials.numel() * 4))
+
+    def _conv_raw(self, n, x, out, bias=None, bn_partials=None):
+        d = self._fwd_desc(n, x, out, bias, bn_partials)
         _lib.check(self.lib.od_conv2d_fwd(self.ctx.handle, C.byref(d), _stream_ptr()), f"conv fwd {n.name}")
-        return self._bn_rows.get(n) if bn_partials is not None else None
 
     def forward(self, x_u8):
         """uint8 [B,H,W,3] (device) -> pred f32 [B,P,C]; keeps z / statistics of every layer for the backward pass."""
@@ -340,48 +351,33 @@ class Trainer:
         self.run_stats_saved.copy_(self.run_stats, non_blocking=True)  # put back by sgd() when the step is skipped
         for n in self.nodes:
             x = self.tensors[n.x]
+            fused_stats = self.fuse_bn_stats and not n.first  # BatchNorm partial sums from the conv epilogue
             if n.first:
                 _lib.check(lib.od_conv_first_fwd(h, x.data_ptr(), self.wf[n.name].data_ptr(), self.in_scale.data_ptr(),
                                                  self.zeros.data_ptr(), n.z.data_ptr(), self.B, n.H, n.W, n.Cout,
                                                  _lib.OD_ACT_LINEAR, 0.0, s), "conv_first")
             elif n.pred_off is not None:
                 bias = self.view(self.params, n.name, "bias")
-                if bias.numel() % 256:  # scale/bias vectors are read in whole 256-channel pads
-                    bp = getattr(self, "_bias_pad", None)
-                    if bp is None:
-                        bp = self._bias_pad = torch.zeros((bias.numel() + 255) // 256 * 256, dtype=torch.float32,
-                                                          device=self.device)
-                    bp[:bias.numel()].copy_(bias)
-                    bias = bp
-                self._conv_raw(n, x, self.pred.data_ptr() + n.pred_off * self.C * 4, out_f32=True, obs=self.P * self.C,
-                               ops=n.Cout, bias=bias)
+                if self._bias_pad is not None:
+                    self._bias_pad[:bias.numel()].copy_(bias)
+                    bias = self._bias_pad
+                self._conv_raw(n, x, self.pred.data_ptr() + n.pred_off * self.C * 4, bias=bias)
                 continue
             else:
-                rows = self._conv_raw(n, x, n.z, bn_partials=self.bn_part if self.fuse_bn_stats else None)
-            M = n.z.numel() // n.Cout
-            if not n.first and self.fuse_bn_stats:
-                _lib.check(lib.od_bn_stats_from_partials(h, self.bn_part.data_ptr(), rows, M, n.Cout,
-                                                         self.view(self.params, n.name, "gamma").data_ptr(),
-                                                         self.view(self.params, n.name, "beta").data_ptr(), W.BN_EPS,
-                                                         n.mean.data_ptr(), n.rstd.data_ptr(), n.scale.data_ptr(),
-                                                         n.shift.data_ptr(), self.run_mean[n.name].data_ptr(),
-                                                         self.run_var[n.name].data_ptr(), BN_MOMENTUM, s),
+                self._conv_raw(n, x, n.z, bn_partials=self.bn_part if fused_stats else None)
+            stats = (self.view(self.params, n.name, "gamma").data_ptr(), self.view(self.params, n.name, "beta").data_ptr(),
+                     W.BN_EPS, n.mean.data_ptr(), n.rstd.data_ptr(), n.scale.data_ptr(), n.shift.data_ptr(),
+                     self.run_mean[n.name].data_ptr(), self.run_var[n.name].data_ptr(), BN_MOMENTUM)
+            if fused_stats:
+                _lib.check(lib.od_bn_stats_from_partials(h, self.bn_part.data_ptr(), self._bn_rows[n], n.M, n.Cout, *stats, s),
                            "od_bn_stats_from_partials")
             else:
-                wsb = lib.od_bn_workspace_bytes(M, n.Cout)
-                _lib.check(lib.od_bn_stats(h, n.z.data_ptr(), M, n.Cout, self.view(self.params, n.name, "gamma").data_ptr(),
-                                           self.view(self.params, n.name, "beta").data_ptr(), W.BN_EPS, n.mean.data_ptr(),
-                                           n.rstd.data_ptr(), n.scale.data_ptr(), n.shift.data_ptr(),
-                                           self.run_mean[n.name].data_ptr(), self.run_var[n.name].data_ptr(), BN_MOMENTUM,
-                                           self.bn_ws.data_ptr(), wsb, s), "od_bn_stats")
-            y = self.tensors[n.out]
-            res = self.tensors[n.res] if n.res else None
-            rm = {"none": 0, "same": 1, "up2": 2}[n.res_mode]
-            Ho, Wo = n.H // n.stride, n.W // n.stride
+                _lib.check(lib.od_bn_stats(h, n.z.data_ptr(), n.M, n.Cout, *stats, self.bn_ws.data_ptr(), n.bn_wsb, s),
+                           "od_bn_stats")
             _lib.check(lib.od_scale_act(h, n.z.data_ptr(), n.scale.data_ptr(), n.shift.data_ptr(),
-                                        res.data_ptr() if res is not None else None, rm, y.data_ptr(), self.B, Ho, Wo,
-                                        n.Cout, _lib.ACT_ENUM[n.act[0] if n.act else None],
-                                        float(n.act[1]) if n.act else 0.0, s), "od_scale_act")
+                                        self.tensors[n.res].data_ptr() if n.res else None, n.res_code,
+                                        self.tensors[n.out].data_ptr(), self.B, n.Ho, n.Wo, n.Cout, n.act_enum, n.alpha, s),
+                       "od_scale_act")
         return self.pred
 
     def loss(self, y_target):
@@ -435,8 +431,6 @@ class Trainer:
         """grad_pred -> self.grads (f32, loss-scaled sums over this rank's batch)."""
         lib, h = self.lib, self.ctx.handle
         s = _stream_ptr()
-        if getattr(self, "_wgrad_table", None) is None:
-            self._build_wgrad_slabs()
         self.grads.zero_()
         have = set()
         pending = dict(self._wgrad_nodes)
@@ -447,13 +441,12 @@ class Trainer:
         if self.cstream is not None:
             self.cstream.wait_stream(main)  # grads.zero_() above
         for k, n in enumerate(reversed(self.nodes)):
-            Ho, Wo = n.H // n.stride, n.W // n.stride
-            M = self.B * Ho * Wo
+            M, Ho, Wo = n.M, n.Ho, n.Wo
             slot = k % len(self.dzs)
             if self._wg_done[slot] is not None:
                 main.wait_event(self._wg_done[slot])  # the weight gradient that read this buffer three nodes ago
             dz = self.dzs[slot][:M * n.Cout]
-            wsb = lib.od_bn_workspace_bytes(M, n.Cout) + 2 * n.Cout * 4
+            wsb = n.bn_wsb + 2 * n.Cout * 4
             if n.pred_off is not None:
                 _lib.check(lib.od_pred_grad_to_level(h, self.grad_pred.data_ptr(), dz.data_ptr(), self.B, self.P, self.C,
                                                      n.pred_off, n.pred_rows, self.loss_scale, s), "od_pred_grad_to_level")
@@ -483,7 +476,7 @@ class Trainer:
                     have.add(n.res)
                 _lib.check(lib.od_bn_bwd(h, n.z.data_ptr(), dy.data_ptr(), n.scale.data_ptr(), n.shift.data_ptr(),
                                          n.mean.data_ptr(), n.rstd.data_ptr(), M, n.Cout,
-                                         _lib.ACT_ENUM[n.act[0] if n.act else None], float(n.act[1]) if n.act else 0.0, 1,
+                                         n.act_enum, n.alpha, 1,
                                          self.view(self.grads, n.name, "gamma").data_ptr(),
                                          self.view(self.grads, n.name, "beta").data_ptr(), dz.data_ptr(),
                                          self.bn_ws.data_ptr(), wsb, s), f"od_bn_bwd {n.name}")
@@ -495,9 +488,6 @@ class Trainer:
             self.wstream.wait_event(ev)
             ws = C.c_void_p(self.wstream.cuda_stream)
             if n.first:
-                if getattr(self, "_first_ws", None) is None:
-                    nb = lib.od_conv_first_bwd_weight_workspace_bytes(h, self.B, n.H, n.W)
-                    self._first_ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
                 _lib.check(lib.od_conv_first_bwd_weight(h, x.data_ptr(), dz.data_ptr(), dw.data_ptr(), self.B, n.H, n.W,
                                                         n.Cout, 1.0 / 255.0, self._first_ws.data_ptr(),
                                                         self._first_ws.numel(), ws), "od_conv_first_bwd_weight")
@@ -518,17 +508,9 @@ class Trainer:
             if n.first or not n.need_dx:
                 continue
             g = self._grad(n.x)
-            d = _lib.ConvDesc()
-            d.x, d.w, d.scale, d.bias = dz.data_ptr(), self.wb[n.name].data_ptr(), self.ones.data_ptr(), self.zeros.data_ptr()
-            d.out = g.data_ptr()
-            d.B, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = self.B, Ho, Wo, n.Cout, n.Cin, n.k, n.stride
-            d.act, d.out_dtype, d.tile_cfg = _lib.OD_ACT_LINEAR, _lib.OD_DT_F16, -1
-            d.transposed = int(n.stride == 2)
-            if n.x in have:
-                d.res, d.res_mode = g.data_ptr(), _lib.OD_RES_SAME  # accumulate in place
-            else:
-                d.res, d.res_mode = None, _lib.OD_RES_NONE
-            _lib.check(lib.od_conv2d_fwd(h, C.byref(d), s), f"dgrad {n.name}")
+            # dx = backward-data of dz (the transposed form for stride 2), accumulated in place when n.x already has a gradient
+            _lib.check(lib.od_conv2d_bwd_data(h, dz.data_ptr(), self.wb[n.name].data_ptr(), g.data_ptr() if n.x in have else None,
+                                              g.data_ptr(), self.B, Ho, Wo, n.Cin, n.Cout, n.k, n.stride, s), f"dgrad {n.name}")
             have.add(n.x)
         main.wait_stream(self.wstream)
         self._wg_done = [None] * len(self.dzs)
@@ -556,7 +538,7 @@ class Trainer:
         _lib.check(self.lib.od_grad_nonfinite(self.ctx.handle, self.grads.data_ptr(), self.n_flat, self.nonfinite.data_ptr(),
                                               _stream_ptr()), "od_grad_nonfinite")
         key = (self.lr, self.weight_decay, tuple(sorted(self.lr_multipliers.items())))
-        if getattr(self, "_sgd_key", None) != key:
+        if self._sgd_key != key:
             segs = []
             for (name, kind), (o, n) in self.seg.items():
                 sg = _lib.SgdSeg()

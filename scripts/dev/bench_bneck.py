@@ -9,8 +9,8 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent.parent))
-from object_detector_amd import _lib  # noqa: E402
-from object_detector_amd.net import Context, pack_conv_weight, pad_vec  # noqa: E402
+from object_detector_amd import _lib, desc  # noqa: E402
+from object_detector_amd.net import Context, pack_conv_weight  # noqa: E402
 
 
 def main():
@@ -34,11 +34,7 @@ def main():
         b1 = torch.zeros(w1.shape[0], device=dev)
         s3 = torch.ones(w3.shape[0], device=dev)
         b3 = torch.zeros(w3.shape[0], device=dev)
-        d = _lib.BneckDesc()
-        d.x, d.out, d.w1, d.w3 = x.data_ptr(), out.data_ptr(), w1.data_ptr(), w3.data_ptr()
-        d.scale1, d.bias1, d.scale3, d.bias3 = s1.data_ptr(), b1.data_ptr(), s3.data_ptr(), b3.data_ptr()
-        d.B, d.H, d.W, d.C = a.batch, hw, hw, ch
-        d.act, d.alpha = 1, 0.1
+        d = desc.bneck(x, w1, s1, b1, w3, s3, b3, out, a.batch, hw, hw, ch, "leaky", 0.1)
         s = torch.cuda.current_stream().cuda_stream
         for _ in range(3):
             _lib.check(ctx.lib.od_bottleneck_fwd(ctx.handle, C.byref(d), C.c_void_p(s)))

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent.parent))
-from object_detector_amd import _lib  # noqa: E402
+from object_detector_amd import _lib, desc  # noqa: E402
 from object_detector_amd.net import Context, pack_conv_weight  # noqa: E402
 
 
@@ -24,14 +24,9 @@ def run(ctx, B, H, W, Cin, Cout, k, stride, cfg, reps=20, res=True, splitk=1):
     Ho, Wo = (H + stride - 1) // stride, (W + stride - 1) // stride
     out = torch.empty((B, Ho, Wo, Cout), dtype=torch.float16, device=dev)
     r = torch.randn((B, Ho, Wo, Cout), device=dev).half() if res else None
-    d = _lib.ConvDesc()
-    d.x, d.w, d.scale, d.bias, d.out = x.data_ptr(), wp.data_ptr(), sc.data_ptr(), bi.data_ptr(), out.data_ptr()
-    d.res = r.data_ptr() if res else None
-    d.B, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = B, H, W, Cin, Cout, k, stride
-    d.act, d.alpha, d.res_mode, d.out_dtype, d.tile_cfg = 1, 0.1, 1 if res else 0, 0, cfg
-    if splitk != 1:
-        ws = torch.empty(32 * B * Ho * Wo * Cout, dtype=torch.float32, device=dev)
-        d.splitk, d.splitk_workspace, d.splitk_workspace_bytes = splitk, ws.data_ptr(), ws.numel() * 4
+    ws = torch.empty(32 * B * Ho * Wo * Cout, dtype=torch.float32, device=dev) if splitk != 1 else None
+    d = desc.conv(x, wp, sc, bi, out, B, H, W, Cin, Cout, k, stride, "leaky", 0.1, res=r, res_mode="same" if res else "none",
+                  tile_cfg=cfg, splitk=None if splitk == 1 else (splitk, ws, ws.numel() * 4))
     s = torch.cuda.current_stream().cuda_stream
     for _ in range(3):
         _lib.check(ctx.lib.od_conv2d_fwd(ctx.handle, C.byref(d), C.c_void_p(s)))

@@ -344,19 +344,17 @@ def _verify_train_forward(tr, n, cuda):
         g.bias = np.zeros(n.Cout, np.float32)
     r = L.ref_forward(g.x, g.w, g.scale, g.bias, n.stride, out_f32=pred, what=f"train fwd {n.name} {case[:7]}")
     keep = [L.poisoned(g.x, cuda), E._packed(g.w, g.scale, g.bias, cuda)]
-    d = _lib.ConvDesc()
-    d.x = keep[0].data_ptr()
-    d.w, d.scale, d.bias = (t.data_ptr() for t in keep[1])
-    d.B, d.H, d.W, d.Cin, d.Cout, d.ksize, d.stride = B, n.H, n.W, n.Cin, n.Cout, n.k, n.stride
-    d.act, d.res_mode, d.tile_cfg = _lib.OD_ACT_LINEAR, _lib.OD_RES_NONE, -1
     if pred:
         out = L.Guarded((B, tr.P, tr.C), torch.float32, cuda)
         out.t.fill_(7.0)
-        d.out = out.t.data_ptr() + n.pred_off * tr.C * 4
-        d.out_dtype, d.out_batch_stride, d.out_pix_stride = _lib.OD_DT_F32, tr.P * tr.C, n.Cout
+        out_ptr = out.t.data_ptr() + n.pred_off * tr.C * 4
     else:
         out = L.Guarded(r.ref16.shape, torch.float16, cuda)
-        d.out, d.out_dtype = out.t.data_ptr(), _lib.OD_DT_F16
+        out_ptr = out.t.data_ptr()
+    # the Trainer's own descriptor of this node; only the pointers are replaced, by the guarded buffers
+    d = tr._fwd_desc(n, keep[0], out_ptr, bias=keep[1][2] if pred else None)
+    d.x, d.out = keep[0].data_ptr(), out_ptr
+    d.w, d.scale, d.bias = (t.data_ptr() for t in keep[1])
     _lib.check(tr.lib.od_conv2d_fwd(tr.ctx.handle, C.byref(d), E._stream()), f"conv fwd {n.name}")
     torch.cuda.synchronize()
     got = out.numpy(n.name)
