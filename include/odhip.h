@@ -233,7 +233,7 @@ int od_gather_detections(od_ctx* ctx, const float* conf, const float* boxes, con
                          const int32_t* keep_count, int B, int P, int NC, int max_det, float* out, void* stream);
 
 /* K5-K8 as ONE call, the path `predict` runs (reference voc_validate.py:27; docs/MODEL.md:54-58,78-82): pred -> decoded boxes,
- * the exact top-K key set, class-aware NMS kept indices -- five launches, the confidence tensor is never materialised
+ * the exact top-K key set, class-aware NMS kept indices -- three launches (four for NC > 76), the confidence tensor is never materialised
  * (one pass over pred computes the confidences on chip, their first-digit histogram and one max per prior; the second pass
  * recomputes only the priors that can hold a top-K candidate).  Results are bit-identical to od_head_postprocess ->
  * od_topk_scores -> od_nms on the same pred (keys come back SORTED descending here, unused slots 0).
@@ -261,7 +261,7 @@ int od_gather_detections_pred(od_ctx* ctx, const float* pred, const float* boxes
 /* dst[b,y,x,:] = src[b,y,W-1-x,:] for uint8 NHWC [B,H,W,3].  src and dst must not overlap. */
 int od_hflip_u8(od_ctx* ctx, const uint8_t* src, uint8_t* dst, int B, int H, int W, void* stream);
 
-/* od_detect without its two NMS launches: pred -> boxes [B,P,4], SORTED keys [B,K] (unused slots 0) and counts [B], bit-identical
+/* od_detect without the NMS: pred -> boxes [B,P,4], SORTED keys [B,K] (unused slots 0) and counts [B], bit-identical
  * to what od_detect returns for the same pred, by the same kernels (both dispatches: NC <= 76 and the streamed ones above).
  * Same workspace as od_detect (left ready for the next call of either).  nms_workspace (od_nms_workspace_bytes(B, K)) receives
  * the rank-ordered keys / boxes / classes the sort kernel gathers, as in od_detect; nothing else in it is touched. */

@@ -1,22 +1,24 @@
-// The product path of K5-K8 as ONE call (od_detect): pred -> boxes + exact top-K + NMS kept indices in five launches, without
+// The product path of K5-K8 as ONE call (od_detect): pred -> boxes + exact top-K + NMS kept indices in three launches, without
 // materialising the confidence tensor.
 //
 // Round 2 ran od_head_postprocess (writes conf f32 [B,P,NC]: 43 MB at 32 x 320^2), od_topk_scores (two full passes over conf:
 // histogram, partition) and od_nms -- 9 kernels + 2 memsets and 194 MB of HBM traffic per batch.  Here:
-//   pass 1  (od_detect_pass1)  reads pred once: confidences in LDS, decoded boxes out, the 4096-bin first-digit histogram of
-//           all scores (LDS atomics -> global), and ONE float per prior: its largest confidence (rowmax)
+//   pass 1  (od_detect_pass1)  reads pred once: 256 rows in LDS at an odd pitch, one thread per row; decoded boxes out, the
+//           4096-bin first-digit histogram of all scores (LDS atomics -> global), and ONE float per prior: its largest
+//           confidence (rowmax)
 //   pass 2  (od_detect_pass2)  finds the first digit d0 of the K-th key from the histogram, then reads rowmax and recomputes
 //           (od_row_conf again: bit-identical) the confidences of ONLY the priors whose best score reaches the d0 bin -- a
 //           fraction of a percent of them -- and partitions those into winners (digit > d0) and the d0-bin candidate list, as
 //           64-bit keys
-//   refine  (od_detect_refine_sort)  one workgroup per image: od_radix_refine inside the d0 bin on the remaining <= 51 key
-//           bits, od_bitonic_sort_desc of the K winners in LDS, od_rank_gather of their boxes / classes for the NMS, counts;
-//           re-zeroes the histogram.  All three are topk_common.h's, shared with topk.hip, nms.hip and detect_wide.hip
-//   od_nms_mask, od_nms_scan  as in od_nms (nms.hip)
+//   tail    (od_detect_tail)  one workgroup per image: od_radix_refine inside the d0 bin on the remaining <= 51 key bits,
+//           od_bitonic_sort_desc of the K winners in LDS, od_rank_gather of their boxes / classes, counts; re-zeroes the
+//           histogram; then od_nms_greedy on the candidates still in LDS.  All four are topk_common.h's, shared with topk.hip,
+//           nms.hip and detect_wide.hip.  od_detect_refine_sort is the same kernel without the last step
 // Same total order, same exact selection, same kept indices as the three-call path (tests compare them bit for bit).
-// od_detect_candidates is the same call stopped after refine (boxes, sorted keys, counts): one view of od_tta_merge (tta.hip).
+// od_detect_candidates is the same call with od_detect_refine_sort for a tail (boxes, sorted keys, counts): one view of
+// od_tta_merge (tta.hip).
 // Compiled with -ffp-contract=off like post.hip / topk.hip / nms.hip.  NC <= 76 (256 whole rows in LDS); larger class counts
-// take the streamed kernels of detect_wide.hip through the same entry points.
+// take the streamed kernels of detect_wide.hip through the same entry points, and od_nms's suppression launch after them.
 #include <string.h>
 
 #include "post_common.h"
@@ -27,16 +29,53 @@ constexpr int NB = OD_TOPK_NB;
 constexpr int DT_ROWS = OD_DT_ROWS, DT2_RPT = OD_DT2_RPT;  // priors per workgroup in pass 1 / per thread in pass 2
 constexpr int DT_CAND_CAP = 1024; // d0-bin candidates a workgroup compacts in LDS before falling back to global atomics
 
-// grid (ceil(P / 256), B).  LDS: rows [256][C] f32 (confidences are computed in place over the class logits) + hist[4096].
+constexpr int dt_row_pitch(int C) { return C | 1; }  // LDS row pitch in floats, odd: a thread walking its own row meets no other
+
+// The workgroup's nel = nrows * C contiguous floats at src go to rows [nrows][CS] in LDS, V floats per global load (V = 4, 2:
+// src is V * 4-byte aligned; 1: it is not), eight loads in flight per thread before the first LDS store: one round trip to
+// memory for rows of up to 32 floats instead of one per load.  A load past the last whole vector is clamped onto it (and not
+// stored), so no load sits under a branch.  (r, c) walk along with the element index instead of being divided out of it.
+template <int V>
+__device__ __forceinline__ void dt_stage_rows(const float* __restrict__ src, int nel, int C, int CS, float* rows) {
+  typedef float vec __attribute__((ext_vector_type(V)));
+  constexpr int U = 8;
+  const int nfull = nel & ~(V - 1);  // >= V: a workgroup has at least two rows of at least 7 floats
+  const int step = 256 * V, dr = step / C, dc = step - dr * C;
+  int i = threadIdx.x * V, r = i / C, c = i - r * C;
+  for (; i < nfull; i += U * step) {
+    vec t[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) t[u] = *(const vec*)(src + min(i + u * step, nfull - V));
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      int rr = r, cc = c;
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        if (i + u * step < nfull) rows[rr * CS + cc] = t[u][e];
+        if (++cc == C) cc = 0, ++rr;
+      }
+      r += dr, c += dc;
+      if (c >= C) c -= C, ++r;
+    }
+  }
+  const int e = nfull + threadIdx.x;  // the last nel % V floats
+  if (e < nel) rows[(e / C) * CS + (e - (e / C) * C)] = src[e];
+}
+
+// grid (ceil(P / 256), B).  LDS: rows [256][C | 1] f32 + hist[4096].  NCT: the class count at compile time (the loops over
+// classes unroll and the confidences stay in registers), or 0 = NC_rt at run time (computed in place over the class logits in
+// LDS).  Either way od_row_conf's operations in od_row_conf's order: the same bits as pass 2's and od_gather_det_pred's.
+template <int NCT>
 __global__ __launch_bounds__(256) void od_detect_pass1(const float* __restrict__ pred, const float* __restrict__ priors,
                                                        float* __restrict__ boxes, float* __restrict__ rowmax,
                                                        float* __restrict__ conf_out, int* __restrict__ hist,
-                                                       TopkState* __restrict__ st, int P, int NC, float loc_scale, int clip,
+                                                       TopkState* __restrict__ st, int P, int NC_rt, float loc_scale, int clip,
                                                        float thr, unsigned dbase, int dshift) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int C = NC + 6, tid = threadIdx.x, b = blockIdx.y;
-  float* rows = sm;                        // [DT_ROWS][C]
-  int* lh = (int*)(sm + DT_ROWS * C);      // [NB]
+  const int NC = NCT ? NCT : NC_rt;
+  const int C = NC + 6, CS = dt_row_pitch(C), tid = threadIdx.x, b = blockIdx.y;
+  float* rows = sm;                        // [DT_ROWS][CS]
+  int* lh = (int*)(sm + DT_ROWS * CS);     // [NB]
   const int p0 = blockIdx.x * DT_ROWS;
   const int nrows = min(DT_ROWS, P - p0);
   for (int i = tid; i < NB; i += 256) lh[i] = 0;
@@ -45,26 +84,40 @@ __global__ __launch_bounds__(256) void od_detect_pass1(const float* __restrict__
     st[b] = z;
   }
   const long long r0 = (long long)b * P + p0;
-  const float* src = pred + r0 * C;  // 16-byte aligned: P is even and p0 a multiple of 256
+  // the block's first element sits at float (b * P + p0) * C of pred: a multiple of 4 for even C (P is even, p0 a multiple of
+  // 256), but only of 2 for odd C when b * P is 2 mod 4 -- so the load width follows the address
+  const float* src = pred + r0 * C;
   const int nel = nrows * C;
-  for (int i = tid * 4; i < nel; i += 256 * 4) {
-    if (i + 3 < nel) {
-      *(f32x4*)(rows + i) = *(const f32x4*)(src + i);
-    } else {
-      for (int e = i; e < nel; ++e) rows[e] = src[e];
-    }
+  const unsigned mis = (unsigned)(uintptr_t)src & 15u;
+  if (mis == 0) {
+    dt_stage_rows<4>(src, nel, C, CS, rows);
+  } else if ((mis & 7u) == 0) {
+    dt_stage_rows<2>(src, nel, C, CS, rows);
+  } else {
+    dt_stage_rows<1>(src, nel, C, CS, rows);
   }
   __syncthreads();
   if (tid < nrows) {
-    float* row = rows + tid * C;
+    float* row = rows + tid * CS;
     const f32x4 loc = {row[2 + NC], row[3 + NC], row[4 + NC], row[5 + NC]};
-    od_row_conf(row, NC, row + 2);
     float mx = 0.f;
-    for (int c = 0; c < NC; ++c) {
-      const float v = row[2 + c];
+    const auto score = [&](float v) {
       mx = fmaxf(mx, v);
       const unsigned sb = od_score_bits(v, thr);
       if (sb) atomicAdd(&lh[od_digit0(sb, dbase, dshift)], 1);
+    };
+    if constexpr (NCT > 0) {
+      float cf[NCT];
+      od_row_conf(row, NCT, cf);
+#pragma unroll
+      for (int c = 0; c < NCT; ++c) score(cf[c]);
+      if (conf_out) {
+#pragma unroll
+        for (int c = 0; c < NCT; ++c) row[2 + c] = cf[c];
+      }
+    } else {
+      od_row_conf(row, NC, row + 2);
+      for (int c = 0; c < NC; ++c) score(row[2 + c]);
     }
     rowmax[r0 + tid] = mx;
     const f32x4 pr = *(const f32x4*)(priors + (long long)(p0 + tid) * 4);
@@ -78,7 +131,7 @@ __global__ __launch_bounds__(256) void od_detect_pass1(const float* __restrict__
     float* dst = conf_out + r0 * NC;
     for (int i = tid; i < nrows * NC; i += 256) {
       const int r = i / NC, c = i - r * NC;
-      dst[i] = rows[r * C + 2 + c];
+      dst[i] = rows[r * CS + 2 + c];
     }
   }
 }
@@ -141,35 +194,68 @@ __global__ __launch_bounds__(256) void od_detect_pass2(const float* __restrict__
   for (int j = tid; j < nc; j += 256) oc[j] = l_cand[j];
 }
 
-// One workgroup (1024 threads) per image: the winners pass 2 wrote straight to the output, plus the krem best of the d0-bin
-// candidate list (od_radix_refine), then sort + gather for the NMS.
-__global__ __launch_bounds__(1024) void od_detect_refine_sort(const float* __restrict__ boxes, TopkState* __restrict__ st,
-                                                              u64* __restrict__ keys, const u64* __restrict__ cand,
-                                                              int* __restrict__ hist, int* __restrict__ counts, int P, int NC,
-                                                              int K, int KP, long long cand_stride, u64* __restrict__ skeys,
-                                                              f32x4* __restrict__ sbox, int* __restrict__ scls, unsigned dbase,
-                                                              int dshift) {
-  __shared__ u64 s[1024];
+// what one image's refine / sort / gather reads and writes (od_detect_refine_sort and od_detect_tail)
+struct RefineArgs {
+  const float* boxes;
+  TopkState* st;
+  u64* keys;
+  const u64* cand;
+  int *hist, *counts;
+  int P, NC, K, KP;
+  long long cand_stride;
+  u64* skeys;
+  f32x4* sbox;
+  int* scls;
+  unsigned dbase;
+  int dshift;
+};
+
+// One workgroup (1024 threads) for image blockIdx.x: the winners pass 2 wrote straight to the output, plus the krem best of the
+// d0-bin candidate list (od_radix_refine), then sort (s [1024], LDS) + gather for the NMS.  Returns the number of candidates n;
+// s[0..n) are their keys in rank order, lbox / lcls (LDS, optional) their boxes / classes, not yet published by a barrier.
+__device__ __forceinline__ int dt_refine_sort_gather(const RefineArgs& a, u64* s, f32x4* lbox, int* lcls) {
   __shared__ int n_win;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const TopkState t = st[b];
+  const int b = blockIdx.x, tid = threadIdx.x, K = a.K;
+  const TopkState t = a.st[b];
   const int nout0 = min(t.nout, K);
   if (tid == 0) n_win = 0;
   // winners that pass 2 wrote straight to the output; the rest of the sort array is empty (key 0 sorts last)
-  s[tid] = tid < nout0 ? keys[(long long)b * K + tid] : 0ull;
+  s[tid] = tid < nout0 ? a.keys[(long long)b * K + tid] : 0ull;
   __syncthreads();
   if (t.d0 >= 0 && t.krem > 0) {
-    const u64* ic = cand + (long long)b * cand_stride;
+    const u64* ic = a.cand + (long long)b * a.cand_stride;
     od_radix_refine(
-        t.ncand, t.ncand, t.krem, dbase, dshift, [&](int i) { return ic[i]; },
+        t.ncand, t.ncand, t.krem, a.dbase, a.dshift, [&](int i) { return ic[i]; },
         [&](u64 key) {
           const int slot = nout0 + atomicAdd(&n_win, 1);
           if (slot < K) s[slot] = key;
         });
     __syncthreads();
   }
-  od_bitonic_sort_desc(s, KP);
-  od_rank_gather(s, min(nout0 + n_win, K), b, boxes, P, NC, K, KP, skeys, sbox, scls, keys, counts, hist);
+  od_bitonic_sort_desc(s, a.KP);
+  const int n = min(nout0 + n_win, K);
+  od_rank_gather(s, n, b, a.boxes, a.P, a.NC, K, a.KP, a.skeys, a.sbox, a.scls, a.keys, a.counts, a.hist, lbox, lcls);
+  return n;
+}
+
+__global__ __launch_bounds__(1024) void od_detect_refine_sort(const RefineArgs a) {
+  __shared__ u64 s[1024];
+  dt_refine_sort_gather(a, s, nullptr, nullptr);
+}
+
+// The per-image tail of od_detect in one launch, one workgroup (1024 threads) per image: od_detect_refine_sort, then od_nms's
+// greedy suppression (od_nms_greedy of topk_common.h: the code od_nms_greedy_k runs) on the n candidates while their keys, boxes
+// and classes are still in LDS.  Dynamic LDS: s [1024] keys | boxes [KP] | classes [KP].
+__global__ __launch_bounds__(1024) void od_detect_tail(const RefineArgs a, float iou_thr, int strict, int max_det,
+                                                       int* __restrict__ keep_flat, int* __restrict__ keep_count) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  u64* s = (u64*)smem;
+  f32x4* lb = (f32x4*)(smem + 1024 * 8);
+  int* lc = (int*)(lb + a.KP);
+  const int b = blockIdx.x;
+  const int n = dt_refine_sort_gather(a, s, lb, lc);
+  __syncthreads();
+  od_nms_greedy(lb, lc, s, n, iou_thr, strict, max_det, keep_flat + (long long)b * max_det, keep_count + b);
 }
 
 // one workgroup per image: row r of out[b] = {flat index (int bits), conf, x1, y1, x2, y2} of kept detection r, the
@@ -258,12 +344,31 @@ extern "C" int od_detect_workspace_init(od_ctx* ctx, void* workspace, size_t wor
 }
 
 namespace {
-// pass 1 / pass 2 / refine of od_detect (either dispatch): pred -> boxes, sorted keys, counts, and the rank-ordered keys / boxes /
-// classes in the NMS workspace.  od_detect queues the two NMS launches behind it; od_detect_candidates stops here.
-int detect_candidates_launch(od_ctx* ctx, const char* who, const float* pred, const float* priors, int B, int P, int NC,
-                             float loc_scale, int clip, float conf_threshold, int K, float* boxes, float* conf, uint64_t* keys,
-                             int32_t* counts, void* workspace, size_t workspace_bytes, void* nms_workspace,
-                             size_t nms_workspace_bytes, hipStream_t s) {
+struct NmsArgs {  // what od_detect adds to od_detect_candidates
+  float iou_threshold;
+  int strict, max_det;
+  int32_t *keep_flat, *keep_count;
+};
+
+template <int NCT>
+int launch_pass1(od_ctx* ctx, dim3 grid, size_t lds, hipStream_t s, const float* pred, const float* priors, float* boxes,
+                 float* rowmax, float* conf, int* hist, TopkState* st, int P, int NC, float loc_scale, int clip, float thr,
+                 unsigned dbase, int dshift) {
+  if (int rc = od_ensure_lds(ctx, (const void*)&od_detect_pass1<NCT>, lds)) return rc;
+  hipLaunchKernelGGL(od_detect_pass1<NCT>, grid, dim3(256), lds, s, pred, priors, boxes, rowmax, conf, hist, st, P, NC, loc_scale,
+                     clip, thr, dbase, dshift);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
+// od_detect (nms given) and od_detect_candidates (nms null), either dispatch: pred -> boxes, sorted keys, counts, the
+// rank-ordered keys / boxes / classes in the NMS workspace, and for od_detect the kept indices.  NC <= 76: pass 1, pass 2 and
+// od_detect_tail (od_detect) or od_detect_refine_sort (od_detect_candidates).  NC > 76: the three streamed launches of
+// detect_wide.hip, whose refine kernel is another one, and for od_detect od_nms's suppression launch behind them.
+int detect_launch(od_ctx* ctx, const char* who, const float* pred, const float* priors, int B, int P, int NC, float loc_scale,
+                  int clip, float conf_threshold, int K, float* boxes, float* conf, uint64_t* keys, int32_t* counts,
+                  void* workspace, size_t workspace_bytes, void* nms_workspace, size_t nms_workspace_bytes, const NmsArgs* nms,
+                  hipStream_t s) {
   OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "%s: NC = %d outside the supported class counts 1..%d", who, NC, OD_MAX_NC);
   OD_REQUIRE(B > 0 && B <= 65535 && P > 0 && P % 2 == 0 && K > 0 && K <= 1024, "%s: bad dims (P even, K <= 1024)", who);
   OD_REQUIRE((long long)P * NC < (1LL << 31), "%s: P * NC must fit 31 bits", who);
@@ -296,22 +401,33 @@ int detect_candidates_launch(od_ctx* ctx, const char* who, const float* pred, co
   int KP;
   od_nms_sorted_buffers(nms_workspace, B, K, &skeys, &sbox, &scls, &KP);
   if (NC > OD_MAX_LDS_NC) {
-    return od_detect_wide_launch(pred, priors, B, P, NC, loc_scale, clip, conf_threshold, dbase, dshift, K, KP, boxes, conf,
-                                 (u64*)keys, counts, hist, st, rowmax, (int*)(ws + l.nhot), (HotRow*)(ws + l.hot), skeys, sbox,
-                                 scls, s);
+    if (int rc = od_detect_wide_launch(pred, priors, B, P, NC, loc_scale, clip, conf_threshold, dbase, dshift, K, KP, boxes, conf,
+                                       (u64*)keys, counts, hist, st, rowmax, (int*)(ws + l.nhot), (HotRow*)(ws + l.hot), skeys,
+                                       sbox, scls, s))
+      return rc;
+    if (!nms) return OD_OK;
+    return od_nms_greedy_launch(nms_workspace, counts, B, K, nms->iou_threshold, nms->strict, nms->max_det, nms->keep_flat,
+                                nms->keep_count, s);
   }
-  const size_t lds1 = (size_t)DT_ROWS * C * 4 + (size_t)NB * 4;
-  if (int rc = od_ensure_lds(ctx, (const void*)&od_detect_pass1, lds1)) return rc;
-  hipLaunchKernelGGL(od_detect_pass1, grid, dim3(256), lds1, s, pred, priors, boxes, rowmax, conf, hist, st, P, NC, loc_scale,
-                     clip, conf_threshold, dbase, dshift);
-  OD_CHECK_LAUNCH();
+  // the class counts with a compile-time pass 1: VOC's 20 (every other count up to 76 runs the same kernel with NC at run time)
+  const size_t lds1 = (size_t)DT_ROWS * dt_row_pitch(C) * 4 + (size_t)NB * 4;
+  const auto pass1 = NC == 20 ? launch_pass1<20> : launch_pass1<0>;
+  if (int rc = pass1(ctx, grid, lds1, s, pred, priors, boxes, rowmax, conf, hist, st, P, NC, loc_scale, clip, conf_threshold,
+                     dbase, dshift))
+    return rc;
   const size_t lds2 = (size_t)DT_ROWS * C * 4 + ((size_t)K + DT_CAND_CAP) * 8;
   if (int rc = od_ensure_lds(ctx, (const void*)&od_detect_pass2, lds2)) return rc;
   hipLaunchKernelGGL(od_detect_pass2, grid2, dim3(256), lds2, s, pred, rowmax, hist, st, (u64*)keys, cand, P, NC, K,
                      conf_threshold, l.cand_stride, dbase, dshift);
   OD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(od_detect_refine_sort, dim3(B), dim3(1024), 0, s, boxes, st, (u64*)keys, cand, hist, counts, P, NC, K, KP,
-                     l.cand_stride, skeys, sbox, scls, dbase, dshift);
+  const RefineArgs ra = {boxes, st, (u64*)keys, cand, hist, counts, P, NC, K, KP, l.cand_stride, skeys, sbox, scls, dbase, dshift};
+  if (!nms) {
+    hipLaunchKernelGGL(od_detect_refine_sort, dim3(B), dim3(1024), 0, s, ra);
+    OD_CHECK_LAUNCH();
+    return OD_OK;
+  }
+  hipLaunchKernelGGL(od_detect_tail, dim3(B), dim3(1024), (size_t)1024 * 8 + (size_t)KP * 20, s, ra, nms->iou_threshold,
+                     nms->strict, nms->max_det, nms->keep_flat, nms->keep_count);
   OD_CHECK_LAUNCH();
   return OD_OK;
 }
@@ -324,11 +440,9 @@ extern "C" int od_detect(od_ctx* ctx, const float* pred, const float* priors, in
   OD_REQUIRE(ctx && pred && priors && boxes && keys && counts && keep_flat && keep_count && workspace && nms_workspace,
              "od_detect: null argument");
   OD_REQUIRE(max_det > 0, "od_detect: bad dims (P even, K <= 1024)");
-  hipStream_t s = (hipStream_t)stream;
-  if (int rc = detect_candidates_launch(ctx, "od_detect", pred, priors, B, P, NC, loc_scale, clip, conf_threshold, K, boxes, conf,
-                                        keys, counts, workspace, workspace_bytes, nms_workspace, nms_workspace_bytes, s))
-    return rc;
-  return od_nms_mask_scan_launch(ctx, nms_workspace, counts, B, K, iou_threshold, strict, max_det, keep_flat, keep_count, s);
+  const NmsArgs nms = {iou_threshold, strict, max_det, keep_flat, keep_count};
+  return detect_launch(ctx, "od_detect", pred, priors, B, P, NC, loc_scale, clip, conf_threshold, K, boxes, conf, keys, counts,
+                       workspace, workspace_bytes, nms_workspace, nms_workspace_bytes, &nms, (hipStream_t)stream);
 }
 
 extern "C" int od_detect_candidates(od_ctx* ctx, const float* pred, const float* priors, int B, int P, int NC, float loc_scale,
@@ -336,9 +450,8 @@ extern "C" int od_detect_candidates(od_ctx* ctx, const float* pred, const float*
                                     int32_t* counts, void* workspace, size_t workspace_bytes, void* nms_workspace,
                                     size_t nms_workspace_bytes, void* stream) {
   OD_REQUIRE(ctx && pred && priors && boxes && keys && counts && workspace && nms_workspace, "od_detect_candidates: null argument");
-  return detect_candidates_launch(ctx, "od_detect_candidates", pred, priors, B, P, NC, loc_scale, clip, conf_threshold, K, boxes,
-                                  conf, keys, counts, workspace, workspace_bytes, nms_workspace, nms_workspace_bytes,
-                                  (hipStream_t)stream);
+  return detect_launch(ctx, "od_detect_candidates", pred, priors, B, P, NC, loc_scale, clip, conf_threshold, K, boxes, conf, keys,
+                       counts, workspace, workspace_bytes, nms_workspace, nms_workspace_bytes, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int od_gather_detections_pred(od_ctx* ctx, const float* pred, const float* boxes, const int32_t* keep_flat,

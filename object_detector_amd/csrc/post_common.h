@@ -224,8 +224,8 @@ int od_detect_wide_launch(const float* pred, const float* priors, int B, int P, 
 // detect_wide.hip: od_gather_detections_pred's launch for NC > 76
 int od_gather_det_pred_wide_launch(const float* pred, const float* boxes, const int32_t* keep_flat, const int32_t* keep_count,
                                    int B, int P, int NC, int max_det, float* out, hipStream_t s);
-// nms.hip: the suppression-mask and greedy-scan launches of od_nms on already sorted / gathered candidates
-int od_nms_mask_scan_launch(od_ctx* ctx, void* nms_workspace, const int32_t* counts, int B, int K, float iou_threshold,
-                            int strict, int max_det, int32_t* keep_flat, int32_t* keep_count, hipStream_t stream);
+// nms.hip: the greedy-suppression launch of od_nms on already sorted / gathered candidates
+int od_nms_greedy_launch(void* nms_workspace, const int32_t* counts, int B, int K, float iou_threshold, int strict, int max_det,
+                         int32_t* keep_flat, int32_t* keep_count, hipStream_t stream);
 // nms.hip: where od_nms keeps the sorted keys / gathered boxes / classes inside its workspace (KP = next power of two >= K)
 void od_nms_sorted_buffers(void* nms_workspace, int B, int K, unsigned long long** skeys, f32x4** sbox, int** scls, int* KP);

@@ -90,12 +90,13 @@ __device__ __forceinline__ void od_bitonic_sort_desc(u64* s, int KP) {
 }
 
 // Thread tid takes rank tid of image b's sorted s[0..KP): the key goes to skeys, and for the first n ranks the box and the class
-// (flat -> (p, c)) to sbox / scls, which is what od_nms_mask / od_nms_scan read.  Where the caller asks for them (non-null):
+// (flat -> (p, c)) to sbox / scls, which is what od_nms_greedy_k reads.  Where the caller asks for them (non-null):
 // keys = the API's key set (K slots: sorted, unused slots 0), counts[b] = n, and the image's first-digit histogram is zeroed
-// again for the next call.
+// again for the next call; lbox / lcls [n] (LDS) = a copy of the image's sbox / scls for a caller that goes on to the NMS itself.
 __device__ __forceinline__ void od_rank_gather(const u64* s, int n, int b, const float* __restrict__ boxes, int P, int NC, int K,
                                                int KP, u64* __restrict__ skeys, f32x4* __restrict__ sbox, int* __restrict__ scls,
-                                               u64* __restrict__ keys, int* __restrict__ counts, int* __restrict__ hist) {
+                                               u64* __restrict__ keys, int* __restrict__ counts, int* __restrict__ hist,
+                                               f32x4* lbox = nullptr, int* lcls = nullptr) {
   const int tid = threadIdx.x;
   if (tid < KP) {
     const u64 key = s[tid];
@@ -105,8 +106,13 @@ __device__ __forceinline__ void od_rank_gather(const u64* s, int n, int b, const
       const unsigned flat = od_key_flat(key);
       const unsigned p = flat / (unsigned)NC;
       const unsigned c = flat - p * (unsigned)NC;
-      sbox[(long long)b * KP + tid] = *(const f32x4*)(boxes + ((long long)b * P + p) * 4);
+      const f32x4 box = *(const f32x4*)(boxes + ((long long)b * P + p) * 4);
+      sbox[(long long)b * KP + tid] = box;
       scls[(long long)b * KP + tid] = (int)c;
+      if (lbox) {
+        lbox[tid] = box;
+        lcls[tid] = (int)c;
+      }
     }
   }
   if (counts && tid == 0) counts[b] = n;
@@ -164,4 +170,96 @@ __device__ __forceinline__ bool od_iou_exceeds(const f32x4 a, float area_a, cons
   const float area_c = (c[2] - c[0]) * (c[3] - c[1]);
   const float uni = (area_a + area_c) - inter;
   return inter > thr * uni;
+}
+
+// ---- the greedy suppression of one image ---------------------------------------------------------------------------------
+// Row a (class ca) suppresses column c (class cc): same class unless strict, and IoU(a, c) > thr.
+__device__ __forceinline__ bool od_suppresses(const f32x4 a, int ca, const f32x4 c, int cc, float thr, int strict) {
+  const float area_a = (a[2] - a[0]) * (a[3] - a[1]);
+  return (strict || cc == ca) && od_iou_exceeds(a, area_a, c, thr);
+}
+
+__device__ __forceinline__ u64 od_readlane64(u64 v, int l) {
+  const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, l);
+  const unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), l);
+  return ((u64)hi << 32) | lo;
+}
+
+// Class-aware greedy NMS of one image's n <= 1024 candidates in rank order by one workgroup of 1024 threads: candidate j is kept
+// unless a kept candidate i < j suppresses it; the first max_det kept go to keep_flat (flat index of their key, -1 padded), their
+// number to *keep_count.  lb / lc / skeys [n]: the candidates' boxes / classes / keys in LDS, published by the caller's barrier.
+// The only IoU tests made are the ones the answer depends on -- kept rows against later columns -- and none once max_det are
+// kept.  64 columns (one per lane) at a time:
+//   (1) the 16 waves share out the rows kept so far (wave-uniform row: LDS broadcast reads) and OR what they suppress of the
+//       block's columns into one 64-bit word;
+//   (2) every wave takes four rows of the block itself: __ballot of (row suppresses column, column > row) is that row's word of
+//       the 64 x 64 diagonal block;
+//   (3) one wave resolves the diagonal block with scalar 64-bit ops on SGPRs (v_readlane; only rows that suppress something take
+//       a step), appends the block's kept rows to the list and writes their flat indices.
+// Same predicate on the same operands as a full suppression matrix would hold (od_suppresses: oracle/nms.py's op order), so the
+// kept indices are oracle/nms.py's bit for bit.
+__device__ __forceinline__ void od_nms_greedy(const f32x4* lb, const int* lc, const u64* skeys, int n, float thr, int strict,
+                                              int max_det, int* __restrict__ keep_flat, int* __restrict__ keep_count) {
+  __shared__ int kept[1024];  // ranks of the kept rows, ascending
+  __shared__ u64 dgw[64];     // the diagonal block's row words
+  __shared__ u64 remw;        // columns of the block suppressed by rows kept in earlier blocks
+  __shared__ int nkept;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid == 0) {
+    remw = 0ull;
+    nkept = 0;
+  }
+  __syncthreads();
+  const int W = (n + 63) >> 6;
+  int total = 0;  // rows kept so far (workgroup-uniform)
+  for (int blk = 0; blk < W && total < max_det; ++blk) {
+    const int j = blk * 64 + lane;
+    const bool colok = j < n;
+    const f32x4 c = colok ? lb[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+    const int cc = colok ? lc[j] : -1;
+    bool rem = false;
+    for (int e = wv; e < total; e += 16) {
+      const int r = kept[e];
+      rem |= colok && od_suppresses(lb[r], lc[r], c, cc, thr, strict);
+    }
+    const u64 rw = __ballot(rem);
+    if (lane == 0 && rw) atomicOr((u64*)&remw, rw);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int rr = wv * 4 + q, i = blk * 64 + rr;
+      const bool hit = i < n && colok && j > i && od_suppresses(lb[i], lc[i], c, cc, thr, strict);
+      const u64 wd = __ballot(hit);
+      if (lane == 0) dgw[rr] = wd;
+    }
+    __syncthreads();
+    if (wv == 0) {
+      const int nv = n - blk * 64;
+      const u64 valid = nv >= 64 ? ~0ull : ((1ull << nv) - 1ull);
+      u64 alive = ~remw & valid;
+      const u64 dg = dgw[lane];
+      u64 todo = __ballot(dg != 0ull) & alive;
+      while (todo) {
+        const int r = __builtin_ctzll(todo);
+        todo &= todo - 1ull;
+        if ((alive >> r) & 1ull) {
+          alive &= ~od_readlane64(dg, r);
+          todo &= alive;
+        }
+      }
+      const int pos = total + __popcll(alive & ((1ull << lane) - 1ull));
+      if ((alive >> lane) & 1ull) {
+        kept[pos] = j;
+        if (pos < max_det) keep_flat[pos] = (int)od_key_flat(skeys[j]);
+      }
+      if (lane == 0) {
+        nkept = total + __popcll(alive);
+        remw = 0ull;
+      }
+    }
+    __syncthreads();
+    total = __builtin_amdgcn_readfirstlane(nkept);
+  }
+  total = min(total, max_det);
+  for (int i = total + tid; i < max_det; i += 1024) keep_flat[i] = -1;
+  if (tid == 0) *keep_count = total;
 }

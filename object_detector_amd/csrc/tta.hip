@@ -2,13 +2,13 @@
 // ONE NMS + box voting (od_tta_merge).  DESIGN.md "Flip test-time augmentation" freezes the semantics; tests/tta_ref.py is
 // their numpy restatement and tests/test_gpu_tta.py compares the two bit for bit.
 //
-// od_tta_merge is latency-bound (one workgroup of work per image, like od_detect_refine_sort) and takes four launches:
+// od_tta_merge is latency-bound (one workgroup of work per image, like od_detect_refine_sort) and takes three launches:
 //   rank   (od_tta_merge_rank)  one workgroup per image.  Every view's list arrives sorted, so a candidate's place in the
 //          merged order (conf bits desc, view asc, flat asc) is its own position plus, per other view, a binary-searched
 //          count of the entries that precede it (merge path; no sort).  The first Km = min(K, sum counts) are written in
 //          rank order as exactly what od_nms_sort leaves behind: box (un-mirrored), class, and the key re-made with the
 //          flat index rank * NC + class, so the order is preserved and the scan's keep_flat / NC is the merged rank
-//   od_nms_mask, od_nms_scan   the launches of od_nms, unchanged (nms.hip), on that table
+//   od_nms_greedy_k   the suppression launch of od_nms, unchanged (nms.hip), on that table
 //   vote   (od_tta_vote_gather)  one workgroup per image, the merged table in LDS: the waves ballot every kept candidate's
 //          member set, then one thread per kept candidate accumulates conf_j and conf_j * box_j over its members in ascending
 //          rank; writes the record block, the (view, flat) sources and the padding
@@ -318,7 +318,7 @@ extern "C" int od_tta_merge(od_ctx* ctx, const od_tta_view* views, int V, int B,
   hipLaunchKernelGGL(od_tta_merge_rank, dim3(B), dim3(1024), 0, s, vw, NC, K, KP, skeys, sbox, scls, msrc, mcount);
   OD_CHECK_LAUNCH();
   const int md = max_det < K ? max_det : K;  // at most Km <= K are ever kept: the scan's list needs no more slots
-  if (int rc = od_nms_mask_scan_launch(ctx, nms_ws, mcount, B, K, iou_threshold, strict, md, keepf, keep_count, s)) return rc;
+  if (int rc = od_nms_greedy_launch(nms_ws, mcount, B, K, iou_threshold, strict, md, keepf, keep_count, s)) return rc;
   hipLaunchKernelGGL(od_tta_vote_gather, dim3(B), dim3(1024), 0, s, skeys, sbox, scls, msrc, mcount, keepf, keep_count, NC, KP, md,
                      max_det, vote_iou, out, src);
   OD_CHECK_LAUNCH();

@@ -122,7 +122,7 @@ class Postprocessor:
 
     def run(self, pred: torch.Tensor, conf_threshold: float):
         """pred [B,P,C] -> (keep_flat i32 [B,max_det] (-1 padded), keep_count i32 [B]); boxes / keys stay on device.
-        ONE C-ABI call (od_detect, five launches); run_unfused() is the same result through head -> topk -> nms."""
+        ONE C-ABI call (od_detect, three launches); run_unfused() is the same result through head -> topk -> nms."""
         if not self.fused:
             return self.run_unfused(pred, conf_threshold)
         assert pred.dtype == torch.float32 and pred.is_contiguous() and tuple(pred.shape) == (self.B, self.P, self.NC + 6)
