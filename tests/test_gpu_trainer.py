@@ -89,7 +89,9 @@ def test_sgd_step_lowers_loss_and_exports(cuda):
 
 
 def test_multi_tensor_pack_and_sgd_equal_per_layer_forms(cuda):
-    """The one-launch weight re-pack (LDS-transposed backward layout) and SGD write exactly what the per-layer forms write."""
+    """After one real step (multi-tensor SGD with momentum), the one-launch weight re-pack (LDS-transposed backward layout)
+    writes exactly what the per-layer od_pack_weights calls write.  Only the PACKS are compared here; the SGD update itself
+    is held by tests/test_gpu_trainer_update.py and tests/test_gpu_optimizer_exact.py."""
     from object_detector_amd.trainer import Trainer
     B, S = 2, 96
     params, x, anns = _setup(cuda, B, S)
