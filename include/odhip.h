@@ -522,7 +522,8 @@ int od_augment_mosaic(od_ctx* ctx, const uint8_t* src, const void* params, uint8
  *                natural order.  ncomp 1 (grey) or 3 (YCbCr, luma sampling samp_h x samp_v, chroma 1x1).
  *   OD_IMG_RGB   packed uint8 [height,width,3] at src_off.
  * hcoef / vcoef: int32 [out_w][2 + hk] / [out_h][2 + vk] rows of (first source index, taps, weights << 22), Pillow's
- * BILINEAR tables (object_detector_amd/resample.py); a pass whose size does not change is skipped.
+ * BILINEAR tables (object_detector_amd/resample.py); a pass whose size does not change is skipped.  The horizontal pass
+ * runs first, except for an image more than 100 times as tall as wide that shrinks vertically (Image.resize's order).
  * od_jpeg_decode_resize handles the OD_IMG_JPEG entries of the batch, od_rgb_resize the OD_IMG_RGB ones: both may run
  * on the same batch and output.  descs_host is the host copy of descs (validated against blob_bytes / ws_bytes).
  * ---------------------------------------------------------------------------------------------- */

@@ -8,7 +8,8 @@
 //   od_jpeg_idct_k   libjpeg jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2, its range limit), one thread per block
 //   od_jpeg_color_k  libjpeg-turbo's default upsampling (fancy h2v1 / h2v2, replication for chroma <= 2 wide) and
 //                    jdcolor's YCbCr->RGB tables (SCALEBITS 16)
-//   od_img_hpass_k / od_img_vpass_k   Pillow's fixed-point BILINEAR passes (22 fraction bits), letterbox zeros
+//   od_img_hpass_k / od_img_vpass_k   Pillow's fixed-point BILINEAR passes (22 fraction bits), letterbox zeros;
+//                    horizontal then vertical, the other way round where Image.resize does so (vertical_first)
 // Bounds: every stream read is clipped to its restart interval, every coefficient write to the interval's blocks, and
 // the host checks every offset of the descriptors against the blob and workspace sizes before a launch.
 #include "common.h"
@@ -424,14 +425,47 @@ __device__ __forceinline__ uint8_t clip8(int64_t acc) {
   return (uint8_t)min(max(acc >> 22, (int64_t)0), (int64_t)255);
 }
 
-// horizontal pass: source [height, width] -> tmp [height, out_w]; skipped when out_w == width
+// Image.resize runs the vertical pass first for an image more than 100 times as tall as wide that shrinks vertically
+// (the intermediate image is then the small one); the rounding to 8 bits between the passes makes the order visible
+__host__ __device__ __forceinline__ bool vertical_first(const od_img_desc& d) {
+  return d.height > (int64_t)100 * d.width && d.out_h < d.height;
+}
+
+// one output pixel of a pass: taps of table row t over source pixels `step` bytes apart
+__device__ __forceinline__ void resample_px(const uint8_t* s, int64_t step, const int* t, uint8_t* o) {
+  const int nt = t[1];
+  int64_t a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+  for (int k = 0; k < nt; ++k) {
+    const int64_t w = t[2 + k];
+    a0 += s[k * step] * w;
+    a1 += s[k * step + 1] * w;
+    a2 += s[k * step + 2] * w;
+  }
+  o[0] = clip8(a0);
+  o[1] = clip8(a1);
+  o[2] = clip8(a2);
+}
+
+// first pass into tmp.  Horizontal: source [height, width] -> tmp [height, out_w], skipped when out_w == width.
+// vertical_first: source -> tmp [out_h, width]
 __global__ __launch_bounds__(256) void od_img_hpass_k(const uint8_t* __restrict__ blob, const od_img_desc* __restrict__ descs,
                                                       uint8_t* __restrict__ ws, int kind) {
   const od_img_desc d = descs[blockIdx.y];
-  if (d.kind != kind || d.out_w == d.width) return;
+  if (d.kind != kind) return;
   const uint8_t* src = img_src(blob, ws, d);
-  const int* tb = (const int*)(blob + d.hcoef_off);
   uint8_t* tmp = ws + d.tmp_ws;
+  if (vertical_first(d)) {
+    const int* tb = (const int*)(blob + d.vcoef_off);
+    const int stride = 2 + d.vk;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < d.out_h * d.width; i += gridDim.x * 256) {
+      const int y = i / d.width, x = i - y * d.width;
+      const int* t = tb + y * stride;
+      resample_px(src + ((int64_t)t[0] * d.width + x) * 3, 3LL * d.width, t, tmp + (int64_t)i * 3);
+    }
+    return;
+  }
+  if (d.out_w == d.width) return;
+  const int* tb = (const int*)(blob + d.hcoef_off);
   const int ow = d.out_w, stride = 2 + d.hk;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < ow * d.height; i += gridDim.x * 256) {
     const int y = i / ow, xx = i - y * ow;
@@ -452,7 +486,8 @@ __global__ __launch_bounds__(256) void od_img_hpass_k(const uint8_t* __restrict_
   }
 }
 
-// vertical pass into the canvas: rows < out_h, columns < out_w get the image, the rest zeros
+// second pass into the canvas: rows < out_h, columns < out_w get the image, the rest zeros.  Vertical over tmp (or the
+// source when the horizontal pass was skipped); vertical_first: horizontal over tmp [out_h, width]
 __global__ __launch_bounds__(256) void od_img_vpass_k(const uint8_t* __restrict__ blob, const od_img_desc* __restrict__ descs,
                                                       const uint8_t* __restrict__ ws, uint8_t* __restrict__ out, int H,
                                                       int W, int kind) {
@@ -463,11 +498,25 @@ __global__ __launch_bounds__(256) void od_img_vpass_k(const uint8_t* __restrict_
   const int* tb = (const int*)(blob + d.vcoef_off);
   const int ow = d.out_w, stride = 2 + d.vk;
   uint8_t* dst = out + (int64_t)b * H * W * 3;
+  const bool vfirst = vertical_first(d);
+  const int* htb = (const int*)(blob + d.hcoef_off);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < H * W; i += gridDim.x * 256) {
     const int y = i / W, x = i - y * W;
     uint8_t* o = dst + (int64_t)i * 3;
     if (y >= d.out_h || x >= ow) {
       o[0] = o[1] = o[2] = 0;
+      continue;
+    }
+    if (vfirst) {
+      const uint8_t* row = ws + d.tmp_ws + (int64_t)y * d.width * 3;
+      if (ow == d.width) {
+        o[0] = row[3 * x];
+        o[1] = row[3 * x + 1];
+        o[2] = row[3 * x + 2];
+      } else {
+        const int* t = htb + x * (2 + d.hk);
+        resample_px(row + (int64_t)t[0] * 3, 3, t, o);
+      }
       continue;
     }
     if (d.out_h == d.height) {
@@ -495,6 +544,11 @@ __global__ __launch_bounds__(256) void od_img_vpass_k(const uint8_t* __restrict_
 
 int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
 
+// the intermediate image between the two resize passes: [height, out_w], or [out_h, width] when vertical_first
+int64_t tmp_bytes(const od_img_desc& d) {
+  return 3 * (vertical_first(d) ? (int64_t)d.out_h * d.width : (int64_t)d.height * d.out_w);
+}
+
 int64_t jpeg_blocks(const od_img_desc& d) {
   return (int64_t)d.mcux * d.mcuy * (d.ncomp == 1 ? 1 : d.samp_h * d.samp_v + 2);
 }
@@ -516,7 +570,7 @@ int check_batch(const od_img_desc* h, int B, long long blob_bytes, long long ws_
                    in_blob(d.vcoef_off, 4LL * d.out_h * (2 + d.vk)),
                "od_img: image %d: resample tables out of bounds", b);
     const int64_t rgb = 3LL * d.width * d.height;
-    OD_REQUIRE(in_ws(d.tmp_ws, 3LL * d.height * d.out_w), "od_img: image %d: workspace too small", b);
+    OD_REQUIRE(in_ws(d.tmp_ws, tmp_bytes(d)), "od_img: image %d: workspace too small", b);
     if (kind == OD_IMG_RGB) {
       OD_REQUIRE(in_blob(d.src_off, rgb), "od_img: image %d: source out of bounds", b);
     } else {
@@ -577,7 +631,7 @@ extern "C" int od_img_workspace_plan(od_img_desc* descs_host, int B, long long* 
       off = align256(off + 16 + 40LL * d.n_sub);
     }
     d.tmp_ws = off;
-    off = align256(off + 3LL * d.height * d.out_w);
+    off = align256(off + tmp_bytes(d));
   }
   *workspace_bytes = off;
   return OD_OK;

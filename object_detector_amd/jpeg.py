@@ -3,10 +3,10 @@
 `parse(data)` walks the markers of a JPEG file and either returns a `JpegInfo` with everything the device needs (frame
 geometry, quantisation tables, Huffman decode tables, the unstuffed entropy-coded data and where each restart interval
 starts in it) or the reason the file takes the host fallback route.  Supported: SOF0 / SOF1 Huffman, 8-bit samples,
-one interleaved scan, 1 component or 3 YCbCr components with luma sampling (1,1) / (2,1) / (2,2) and chroma (1,1).
-(1,2) luma sampling falls back: PIL cannot write such a file, so no test pins the device output against it.  Everything
-else (progressive, arithmetic, 12-bit, CMYK / Adobe transform, multi-scan, no EOI, a header that does not parse) is
-decoded by PIL on the host.
+one interleaved scan, 1 component or 3 YCbCr components with luma sampling (1,1) / (2,1) / (2,2) / (1,2) and chroma
+(1,1).  Everything else (progressive, arithmetic, 12-bit, CMYK / Adobe transform, multi-scan, no EOI, a header that does
+not parse, a Huffman table libjpeg refuses) is decoded by PIL on the host.  The contract of `parse`: it returns a
+JpegInfo or raises Fallback, whatever the bytes are; no other exception escapes.
 
 Huffman decode tables (HUFF_INTS int32 per table, libjpeg's jdhuff.c scheme):
     [0, 512)    lookahead on the next 9 bits: (code length << 8) | symbol, 0 when the code is longer than 9 bits
@@ -31,7 +31,7 @@ ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 1
                    39, 46, 53, 60, 61, 54, 47, 55, 62, 63], np.int32)
 
 _SOF_OTHER = {0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF}
-_LUMA = {(1, 1), (2, 1), (2, 2)}  # (1, 2) is decodable by the kernels but no test can produce it: fallback
+_LUMA = {(1, 1), (2, 1), (2, 2), (1, 2)}
 _HUFF_CACHE: dict = {}
 
 
@@ -103,7 +103,7 @@ def huff_table(counts: bytes, vals: bytes, is_dc: bool) -> np.ndarray:
                 p += 1
                 code += 1
             maxcode[ln] = code - 1
-        if code > (1 << ln):
+        if code >= (1 << ln):  # libjpeg's check (jdhuff.c): no code is all ones, so a complete length is refused too
             raise Fallback("bad Huffman table")
         code <<= 1
     t[548:548 + len(vals)] = np.frombuffer(vals, np.uint8)
@@ -195,9 +195,10 @@ def parse(data) -> JpegInfo:
                 while k < len(seg):
                     pq, tq = seg[k] >> 4, seg[k] & 15
                     nb = 128 if pq else 64
-                    raw = np.frombuffer(seg[k + 1:k + 1 + nb], ">u2" if pq else np.uint8)
-                    if tq > 3 or len(raw) != 64:
+                    tab = seg[k + 1:k + 1 + nb]
+                    if pq > 1 or tq > 3 or len(tab) != nb:
                         raise Fallback("bad DQT")
+                    raw = np.frombuffer(tab, ">u2" if pq else np.uint8)
                     q = np.zeros(64, np.int32)
                     q[ZIGZAG] = raw
                     quant[tq] = q

@@ -2,9 +2,11 @@
 
 `Image.resize(size, Image.BILINEAR)` on 8-bit RGB is two separable passes, horizontal first, each with per-output-pixel
 integer weights of 22 fraction bits: out = clip8((2^21 + sum(in * w)) >> 22).  A pass is skipped when its dimension does
-not change.  The tables are computed here in double precision exactly as Pillow computes them (Resample.c,
-precompute_coeffs / normalize_coeffs_8bpc) and cached per (source, destination) length; `resize` applies them with numpy
-and is byte-identical to PIL.  The device resample kernels (csrc/jpeg.hip) read the same tables.
+not change.  Image.resize runs the vertical pass first when the image is more than 100 times as tall as wide and
+shrinks vertically; each pass rounds to 8 bits, so the order shows in the result (`vertical_first`).  The tables are
+computed here in double precision exactly as Pillow computes them (Resample.c, precompute_coeffs /
+normalize_coeffs_8bpc) and cached per (source, destination) length; `resize` applies them with numpy and is
+byte-identical to PIL.  The device resample kernels (csrc/jpeg.hip) read the same tables and follow the same order.
 """
 from __future__ import annotations
 
@@ -65,11 +67,18 @@ def resize(img: np.ndarray, size_wh) -> np.ndarray:
     """uint8 [H,W,C] -> uint8 [h,w,C]; equals np.asarray(Image.fromarray(img).resize(size_wh, Image.BILINEAR))."""
     w, h = size_wh
     out = np.asarray(img, np.uint8)
+    if vertical_first(out.shape[:2], h):
+        out = _pass(out, 0, h)
     if out.shape[1] != w:
         out = _pass(out, 1, w)
     if out.shape[0] != h:
         out = _pass(out, 0, h)
     return out
+
+
+def vertical_first(src_hw, out_h) -> bool:
+    """Image.resize's pass order: vertical first for a very tall, narrow image that shrinks vertically."""
+    return src_hw[0] > 100 * src_hw[1] and out_h < src_hw[0]
 
 
 def letterbox_size(src_hw, size_hw, keep_aspect):

@@ -1,7 +1,9 @@
 """Test support: a numpy / Python reference of the device JPEG decoder's three stages (entropy decode, libjpeg "islow"
 IDCT, libjpeg-turbo fancy upsampling + jdcolor YCbCr->RGB).  It reads what object_detector_amd.jpeg.parse produces and
-must equal PIL's decode byte for byte; that pins the libjpeg details the kernels of csrc/jpeg.hip reproduce.  Slow (a
-Python loop per symbol): for small images only."""
+must equal PIL's decode byte for byte; that pins the libjpeg details the kernels of csrc/jpeg.hip reproduce.  `scan`
+also reports what the entropy decode went through (block start bits, largest categories, ZRL runs), and `sync_rounds`
+restates the round scheme of the parallel decode, so the device's round count can be pinned too.  Slow (a Python loop
+per symbol): for small images only."""
 from __future__ import annotations
 
 import numpy as np
@@ -12,16 +14,20 @@ NATURAL = np.concatenate([jpeg.ZIGZAG, np.full(16, 63, np.int32)])  # libjpeg's 
 
 
 class _Bits:
+    """Bit reader over stream bytes [start_byte, end_byte); bytes at or past the end read as zero (libjpeg inserts
+    zeros at a marker).  `p` is the absolute bit position.  Holds the 16-bit window at every bit position."""
+
     def __init__(self, data, start_byte, end_byte):
-        self.d, self.p, self.end = data, start_byte * 8, end_byte
+        bits = np.unpackbits(np.asarray(data[start_byte:end_byte], np.uint8))
+        pad = np.concatenate([bits, np.zeros(16, np.uint8)]).astype(np.int32)
+        w = np.zeros(len(bits) + 1, np.int32)
+        for i in range(16):
+            w = (w << 1) | pad[i:i + len(w)]
+        self.w, self.base, self.p = w.tolist(), start_byte * 8, start_byte * 8
 
     def peek(self, n):
-        v = 0
-        for i in range(n):
-            q = self.p + i
-            byte = int(self.d[q >> 3]) if (q >> 3) < self.end else 0
-            v = (v << 1) | ((byte >> (7 - (q & 7))) & 1)
-        return v
+        i = self.p - self.base
+        return self.w[i] >> (16 - n) if i < len(self.w) else 0
 
     def get(self, n):
         v = self.peek(n)
@@ -48,9 +54,18 @@ def _extend(r, s):
     return r - (1 << s) + 1 if r < (1 << (s - 1)) else r
 
 
-def coefficients(info):
-    """-> int16 [n_blocks, 64] quantised coefficients in natural order, blocks in MCU order (stage 1)."""
+class Scan:
+    """What the entropy decode of a file went through: `coef` int16 [n_blocks, 64] (natural order, MCU order),
+    `starts` int64 [n_blocks] bit position in info.stream of each block's first symbol, `dc_cat` / `ac_cat` the largest
+    DC-difference / AC magnitude category coded, `zrl_run` the longest run of consecutive ZRL symbols."""
+    __slots__ = ("coef", "starts", "dc_cat", "ac_cat", "zrl_run")
+
+
+def scan(info):
+    sc = Scan()
     out = np.zeros((info.n_blocks, 64), np.int16)
+    sc.coef, sc.starts = out, np.zeros(info.n_blocks, np.int64)
+    sc.dc_cat = sc.ac_cat = sc.zrl_run = 0
     mcus = info.restart if info.restart else info.mcux * info.mcuy
     bounds = list(info.seg_start) + [len(info.stream)]
     for s in range(info.n_seg):
@@ -61,23 +76,94 @@ def coefficients(info):
         for g in range(first, last):
             ci = info.blocks[g % info.bpm][0]
             dc, ac = info.huff[2 * ci], info.huff[2 * ci + 1]
+            sc.starts[g] = br.p
             n = _decode(dc, br)
+            sc.dc_cat = max(sc.dc_cat, n)
             if n:
                 pred[ci] += _extend(br.get(n), n)
             out[g, 0] = np.int16(np.int32(pred[ci]).astype(np.int16))
-            k = 1
+            k, zrl = 1, 0
             while k < 64:
                 rs = _decode(ac, br)
                 r, n = rs >> 4, rs & 15
                 if n:
                     k += r
                     out[g, NATURAL[k]] = _extend(br.get(n), n)
+                    sc.ac_cat = max(sc.ac_cat, n)
+                    zrl = 0
                 elif r != 15:
                     break
                 else:
                     k += 15
+                    zrl += 1
+                    sc.zrl_run = max(sc.zrl_run, zrl)
                 k += 1
-    return out
+    return sc
+
+
+def coefficients(info):
+    """-> int16 [n_blocks, 64] quantised coefficients in natural order, blocks in MCU order (stage 1)."""
+    return scan(info).coef
+
+
+def _run_sub(info, huff, br, end_bit, st):
+    """The symbols of one subsequence that start before `end_bit`, from state (bit position, block of the MCU, zig-zag
+    index) -> exit state.  Counting mode of the device decoder's run_sub."""
+    br.p, c, k = st
+    while br.p < end_bit:
+        ci = info.blocks[c][0]
+        if k == 0:
+            n = _decode(huff[2 * ci], br)  # advances br.p past the code
+            br.p += n
+            k = 1
+        else:
+            rs = _decode(huff[2 * ci + 1], br)
+            r, n = rs >> 4, rs & 15
+            if n:
+                k += r + 1
+                br.p += n
+            elif r == 15:
+                k += 16
+            else:
+                k = 64
+        if k >= 64:
+            k = 0
+            c = (c + 1) % info.bpm
+    return br.p, c, k
+
+
+def sync_states(info, sub_bits=jpeg.SUB_BITS):
+    """Rounds the parallel decode described in the header of csrc/jpeg.hip needs for this file: round 0 runs every
+    subsequence from the guessed state (its start bit, block 0 of the MCU, coefficient 0); each further round re-runs
+    subsequence j from j-1's exit state if that exit moved in the round before, and the scheme stops after the first
+    round in which no exit moved (at most n + 1 rounds are tried).  -> (the count the device reports, the final exit
+    state (bit position, block of the MCU, zig-zag index) of every subsequence)."""
+    subs = info.subsequences(sub_bits)
+    n = len(subs)
+    bounds = list(info.seg_start) + [len(info.stream)]
+    readers = [_Bits(info.stream, bounds[s], bounds[s + 1]) for s in range(info.n_seg)]
+    br = [readers[s] for s in np.cumsum(subs[:, 5]) - 1]
+    huff = [t.tolist() for t in info.huff]  # plain lists: the loop below reads them a symbol at a time
+    subs = subs.tolist()
+    ex = [_run_sub(info, huff, br[j], subs[j][1], (subs[j][0], 0, 0)) for j in range(n)]
+    moved = [True] * n
+    rounds = 1
+    while rounds <= n + 1:
+        nex, nmoved = list(ex), [False] * n
+        for j in range(n):
+            if not subs[j][5] and moved[j - 1]:
+                nex[j] = _run_sub(info, huff, br[j], subs[j][1], ex[j - 1])
+                nmoved[j] = nex[j] != ex[j]
+        ex, moved = nex, nmoved
+        if not any(moved):
+            break
+        rounds += 1
+    return rounds, ex
+
+
+def sync_rounds(info, sub_bits=jpeg.SUB_BITS):
+    """Synchronisation rounds of the parallel decode (see sync_states)."""
+    return sync_states(info, sub_bits)[0]
 
 
 C = dict(f0298=2446, f0390=3196, f0541=4433, f0765=6270, f0899=7373, f1175=9633, f1501=12299, f1847=15137,
