@@ -438,6 +438,20 @@ typedef struct od_pack_layer {
  * od_grad_nonfinite writes, so that one f16 overflow in the loss-scaled backward pass cannot poison the master weights */
 int od_sgd_step_multi(od_ctx* ctx, float* w, float* m, const float* g, const od_sgd_seg* segs, int nseg, float momentum,
                       float inv_loss_scale, const int32_t* skip_if_nonzero, void* stream);
+/* od_sgd_step_multi, and in the same pass over each segment an exponential moving average of the new weights:
+ *   d = w_new - ema; p = ema_one_minus_decay * d; ema = ema + p      (three separately rounded f32 operations)
+ * `ema` is a fourth flat buffer with the layout of w; it must not be w, m or g.  This form, not decay*ema + omd*w, is the
+ * contract: it leaves ema bitwise unchanged where w_new == ema.  ema_one_minus_decay must lie in [0, 1].  A set
+ * skip_if_nonzero leaves w, m and ema untouched; elements that belong to no segment are never written.  Any offset and any
+ * 4-byte-aligned base pointers are accepted; a segment that starts at the same distance from a 16-byte boundary in all
+ * four buffers moves as 16-byte accesses, with the same bits. */
+int od_sgd_step_multi_ema(od_ctx* ctx, float* w, float* m, const float* g, float* ema, const od_sgd_seg* segs, int nseg,
+                          float momentum, float inv_loss_scale, float ema_one_minus_decay,
+                          const int32_t* skip_if_nonzero, void* stream);
+/* ema[i] = ema[i] + one_minus_decay * (x[i] - ema[i]) over a flat buffer (the same three operations; the trainer's
+ * average of the BatchNorm running statistics).  skip_if_nonzero (DEVICE int32, may be NULL) as above; ema != x. */
+int od_ema_update(od_ctx* ctx, float* ema, const float* x, long long n, float one_minus_decay,
+                  const int32_t* skip_if_nonzero, void* stream);
 /* flag[0] (DEVICE int32) = 1 when any of g[0..n) is Inf / NaN, else 0.  Run it on the flat gradient buffer AFTER the
  * all-reduce: a non-finite value on one rank reaches every rank through the sum, so all ranks skip the same step. */
 int od_grad_nonfinite(od_ctx* ctx, const float* g, long long n, int32_t* flag, void* stream);

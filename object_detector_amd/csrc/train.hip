@@ -11,6 +11,8 @@
 //   od_sgd_step[_multi]      SGD + momentum + weight decay on f32 masters: one flat segment, or one launch over a device
 //                      table of segments (each with its own learning rate: the trainer folds the per-layer multipliers of
 //                      docs/MODEL.md:84-90 into it); od_grad_nonfinite / od_copy_if_nonzero guard a step that overflowed
+//   od_sgd_step_multi_ema    the same launch with an exponential moving average of the masters updated in the same pass;
+//                      od_ema_update is the average alone over a flat buffer (the BatchNorm running statistics)
 //   od_pack_weights[_multi]  f32 masters -> the f16 forward and backward-data packs of the convolutions
 //
 // reference: the Keras BatchNormalization / activation / optimizer machinery behind the (unseen) `fit` of
@@ -439,6 +441,105 @@ __global__ __launch_bounds__(256) void od_sgd_multi_k(float* __restrict__ w, flo
     sgd_update(ws[i], ms[i], gs[i], sg.lr, momentum, sg.weight_decay, inv_scale);
 }
 
+// e += omd * (x - e): three separately rounded f32 operations (this TU is built with -ffp-contract=off), so that e stays
+// bitwise where x == e -- decay * e + omd * x would not
+__device__ __forceinline__ void ema_update(float& e, float x, float omd) {
+  const float d = x - e;
+  const float p = omd * d;
+  e = e + p;
+}
+
+// Elements in front of the first 16-byte boundary of a run of `count` floats at `p` (0..3, at most count)
+__device__ __forceinline__ long long head_to_16(const float* p, long long count) {
+  const long long h = (4 - (long long)(((uintptr_t)p >> 2) & 3)) & 3;
+  return h < count ? h : count;
+}
+
+// od_sgd_multi_k plus the weight average in the same pass: 4 loads and 3 stores of 4 B per parameter where a separate EMA
+// launch would read w a third time.  Where the segment starts at the same offset from a 16-byte boundary in all four
+// buffers (the trainer's always do: offsets are multiples of 4 floats in 16-byte-aligned buffers) its aligned body moves
+// as 16-byte accesses and only the head (< 4 elements) and the tail (< 4) go one by one; any other segment goes one by
+// one as a whole.  Per element both paths run sgd_update then ema_update, so the bits do not depend on the path.
+__global__ __launch_bounds__(256) void od_sgd_multi_ema_k(float* __restrict__ w, float* __restrict__ m,
+                                                          const float* __restrict__ g, float* __restrict__ ema,
+                                                          const od_sgd_seg* __restrict__ segs, float momentum,
+                                                          float inv_scale, float omd, const int32_t* __restrict__ skip) {
+  if (skip && *skip) return;  // a skipped step leaves the average alone as well
+  const od_sgd_seg sg = segs[blockIdx.y];
+  float* ws = w + sg.offset;
+  float* ms = m + sg.offset;
+  const float* gs = g + sg.offset;
+  float* es = ema + sg.offset;
+  const long long first = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+  const unsigned a = (unsigned)((uintptr_t)ws & 15);
+  if (((uintptr_t)ms & 15) != a || ((uintptr_t)gs & 15) != a || ((uintptr_t)es & 15) != a) {
+    for (long long i = first; i < sg.count; i += stride) {
+      sgd_update(ws[i], ms[i], gs[i], sg.lr, momentum, sg.weight_decay, inv_scale);
+      ema_update(es[i], ws[i], omd);
+    }
+    return;
+  }
+  const long long head = head_to_16(ws, sg.count);
+  const long long nvec = (sg.count - head) >> 2;
+  const long long tail0 = head + 4 * nvec;  // first element behind the aligned body
+  f32x4* w4 = (f32x4*)(ws + head);
+  f32x4* m4 = (f32x4*)(ms + head);
+  const f32x4* g4 = (const f32x4*)(gs + head);
+  f32x4* e4 = (f32x4*)(es + head);
+  for (long long i = first; i < nvec; i += stride) {
+    f32x4 wv = w4[i], mv = m4[i], ev = e4[i];
+    const f32x4 gv = g4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float wk = wv[k], mk = mv[k], ek = ev[k];
+      sgd_update(wk, mk, gv[k], sg.lr, momentum, sg.weight_decay, inv_scale);
+      ema_update(ek, wk, omd);
+      wv[k] = wk, mv[k] = mk, ev[k] = ek;
+    }
+    w4[i] = wv;
+    m4[i] = mv;
+    e4[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 8) {  // lanes 0..3: the head, lanes 4..7: the tail
+    const long long i = threadIdx.x < 4 ? (long long)threadIdx.x : tail0 + (threadIdx.x - 4);
+    if (threadIdx.x < 4 ? i < head : i < sg.count) {
+      sgd_update(ws[i], ms[i], gs[i], sg.lr, momentum, sg.weight_decay, inv_scale);
+      ema_update(es[i], ws[i], omd);
+    }
+  }
+}
+
+// ema[i] += omd * (x[i] - ema[i]) over a flat buffer, unless *skip != 0; same head / 16-byte body / tail split
+__global__ __launch_bounds__(256) void od_ema_k(float* __restrict__ ema, const float* __restrict__ x, long long n, float omd,
+                                                const int32_t* __restrict__ skip) {
+  if (skip && *skip) return;
+  const long long first = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+  if ((((uintptr_t)ema ^ (uintptr_t)x) & 15) != 0) {
+    for (long long i = first; i < n; i += stride) ema_update(ema[i], x[i], omd);
+    return;
+  }
+  const long long head = head_to_16(ema, n);
+  const long long nvec = (n - head) >> 2;
+  const long long tail0 = head + 4 * nvec;
+  f32x4* e4 = (f32x4*)(ema + head);
+  const f32x4* x4 = (const f32x4*)(x + head);
+  for (long long i = first; i < nvec; i += stride) {
+    f32x4 ev = e4[i];
+    const f32x4 xv = x4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float ek = ev[k];
+      ema_update(ek, xv[k], omd);
+      ev[k] = ek;
+    }
+    e4[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 8) {
+    const long long i = threadIdx.x < 4 ? (long long)threadIdx.x : tail0 + (threadIdx.x - 4);
+    if (threadIdx.x < 4 ? i < head : i < n) ema_update(ema[i], x[i], omd);
+  }
+}
+
 // f16 re-pack of conv weights: master f32 [Cout][k*k*Cin] (k index = tap*Cin + cin) -> forward f16 [Cout_pad][Kpad] and, for
 // the backward-data conv, f16 [Cin_pad][Kpad_t] with wt[ci][(k*k-1-tap)*Cout + co] = w[co][tap*Cin + ci] (taps flipped,
 // channels swapped).  One 64 (Cout) x 64 (Cin) tile of one tap per trip: coalesced f32 reads, forward rows written straight
@@ -679,6 +780,30 @@ extern "C" int od_sgd_step_multi(od_ctx* ctx, float* w, float* m, const float* g
   OD_REQUIRE(ctx && w && m && g && segs && nseg > 0 && nseg <= 65535, "od_sgd_step_multi: bad argument");
   hipLaunchKernelGGL(od_sgd_multi_k, dim3(256, nseg), dim3(256), 0, (hipStream_t)stream, w, m, g, segs, momentum,
                      inv_loss_scale, skip_if_nonzero);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
+extern "C" int od_sgd_step_multi_ema(od_ctx* ctx, float* w, float* m, const float* g, float* ema, const od_sgd_seg* segs,
+                                     int nseg, float momentum, float inv_loss_scale, float ema_one_minus_decay,
+                                     const int32_t* skip_if_nonzero, void* stream) {
+  OD_REQUIRE(ctx && w && m && g && ema && segs && nseg > 0 && nseg <= 65535, "od_sgd_step_multi_ema: bad argument");
+  OD_REQUIRE(ema_one_minus_decay >= 0.f && ema_one_minus_decay <= 1.f,  // (false for NaN)
+             "od_sgd_step_multi_ema: ema_one_minus_decay must be in [0, 1]");
+  OD_REQUIRE(ema != w && ema != m && ema != g, "od_sgd_step_multi_ema: ema must be a buffer of its own");
+  hipLaunchKernelGGL(od_sgd_multi_ema_k, dim3(256, nseg), dim3(256), 0, (hipStream_t)stream, w, m, g, ema, segs, momentum,
+                     inv_loss_scale, ema_one_minus_decay, skip_if_nonzero);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
+extern "C" int od_ema_update(od_ctx* ctx, float* ema, const float* x, long long n, float one_minus_decay,
+                             const int32_t* skip_if_nonzero, void* stream) {
+  OD_REQUIRE(ctx && ema && x && n > 0, "od_ema_update: bad argument");
+  OD_REQUIRE(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "od_ema_update: one_minus_decay must be in [0, 1]");
+  OD_REQUIRE(ema != x, "od_ema_update: ema must be a buffer of its own");
+  hipLaunchKernelGGL(od_ema_k, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ema, x, n, one_minus_decay,
+                     skip_if_nonzero);
   OD_CHECK_LAUNCH();
   return OD_OK;
 }

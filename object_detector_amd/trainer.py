@@ -36,6 +36,19 @@ def lr_multiplier(name: str, table=None) -> float:
     return 1.0
 
 
+def ema_decay_at(n: int, decay: float, warmup: bool = True) -> float:
+    """Decay of the weight average at its update number `n` (= sgd() calls made before this one, skipped steps included),
+    in float64: with warm-up min(decay, (1 + n) / (10 + n)), so that the average forgets its starting point quickly (0.1 at
+    n = 0, 0.55 at n = 10, 0.918 at n = 100; the ramp meets decay = 0.999 at n = 8990); without, `decay`."""
+    decay = float(decay)
+    return min(decay, (1.0 + n) / (10.0 + n)) if warmup else decay
+
+
+def ema_omd(n: int, decay: float, warmup: bool = True) -> np.float32:
+    """The kernels' one_minus_decay argument of update `n`: 1 - ema_decay_at(...) in float64, rounded once to f32."""
+    return np.float32(1.0 - ema_decay_at(n, decay, warmup))
+
+
 class _Node:
     __slots__ = ("name", "x", "out", "res", "res_mode", "H", "W", "Cin", "Cout", "k", "stride", "act", "bn", "z",
                  "mean", "rstd", "scale", "shift", "first", "pred_off", "pred_rows", "need_dx",
@@ -47,7 +60,15 @@ class Trainer:
     def __init__(self, params, batch_size, input_size=(320, 320), device="cuda:0", lr=1e-3, momentum=0.9,
                  weight_decay=0.0, loss_scale=1024.0, box_mode="smooth_l1", backbone_act=("leaky", 0.1),
                  head_act=("elu", 1.0), comm=None, world_size=1, grad_payload=None, dynamic_loss_scale=True,
-                 lr_multipliers=None, prior_wh=None, ignore_regions=False, ign_thr=None, loss_weights=(1.0, 1.0, 1.0)):
+                 lr_multipliers=None, prior_wh=None, ignore_regions=False, ign_thr=None, loss_weights=(1.0, 1.0, 1.0),
+                 ema_decay=None, ema_warmup=True):
+        # ema_decay: None = no averaged model (no extra buffers, sgd() launches od_sgd_step_multi); 0 < ema_decay < 1 keeps
+        # an exponential moving average of the masters (self.ema) and of the BatchNorm running statistics
+        # (self.ema_run_stats), updated inside sgd() with the decay ema_decay_at(self.ema_updates, ema_decay, ema_warmup)
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be None or lie in (0, 1), got {ema_decay!r}")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
         self.ctx = Context.get(device)
         self.lib = self.ctx.lib
         self.device = torch.device(device)
@@ -121,6 +142,11 @@ class Trainer:
         self.run_stats_saved = torch.empty_like(self.run_stats)
         self.run_mean = {n: self.run_stats[o:o + self.specs[n][2]] for n, o in rviews.items()}
         self.run_var = {n: self.run_stats[o + desc.pad_to(self.specs[n][2], 4):][:self.specs[n][2]] for n, o in rviews.items()}
+        self._run_off = rviews  # layer -> offset of its (mean, var) pair in run_stats
+        # the averaged model: same layouts, starts as a copy.  ema_updates counts sgd() calls, skipped steps included
+        self.ema = self.params.clone() if self.ema_decay is not None else None
+        self.ema_run_stats = self.run_stats.clone() if self.ema_decay is not None else None
+        self.ema_updates = 0
         # per-channel stand-ins (scale / shift / bias / sink) cover every layer's Cout, read in whole 256-channel pads: the
         # prediction conv of a many-class head has Cout = 8 * (NC + 6), beyond the backbone's widths from NC = 251
         maxpad = max(2048, max(desc.pad_to(s[2], 256) for s in self.specs.values()))
@@ -547,15 +573,30 @@ class Trainer:
                 sg.weight_decay = self.weight_decay if kind == "w" else 0.0
                 segs.append(sg)
             self._sgd_table, self._sgd_n, self._sgd_key = self._device_table(segs), len(segs), key
-        _lib.check(self.lib.od_sgd_step_multi(self.ctx.handle, self.params.data_ptr(), self.mom.data_ptr(),
-                                              self.grads.data_ptr(), self._sgd_table.data_ptr(), self._sgd_n,
-                                              self.momentum, inv, self.nonfinite.data_ptr(), _stream_ptr()),
-                   "od_sgd_step_multi")
+        if self.ema_decay is None:
+            _lib.check(self.lib.od_sgd_step_multi(self.ctx.handle, self.params.data_ptr(), self.mom.data_ptr(),
+                                                  self.grads.data_ptr(), self._sgd_table.data_ptr(), self._sgd_n,
+                                                  self.momentum, inv, self.nonfinite.data_ptr(), _stream_ptr()),
+                       "od_sgd_step_multi")
+        else:
+            # the decay follows the number of sgd() calls made so far, skipped steps INCLUDED: the host learns of a skip
+            # one or two steps late (_poll_nonfinite), and a schedule that waited for it would differ between a run and
+            # its replay, and between ranks that poll at different moments.  The device skips the update itself.
+            omd = float(ema_omd(self.ema_updates, self.ema_decay, self.ema_warmup))
+            _lib.check(self.lib.od_sgd_step_multi_ema(self.ctx.handle, self.params.data_ptr(), self.mom.data_ptr(),
+                                                      self.grads.data_ptr(), self.ema.data_ptr(), self._sgd_table.data_ptr(),
+                                                      self._sgd_n, self.momentum, inv, omd, self.nonfinite.data_ptr(),
+                                                      _stream_ptr()), "od_sgd_step_multi_ema")
         # a skipped step also takes back what its forward pass did to the BatchNorm running statistics: when the Inf / NaN
         # came from an f16 overflow in z (not from a loss-scaled dz) the batch statistics folded into them are non-finite
         _lib.check(self.lib.od_copy_if_nonzero(self.ctx.handle, self.run_stats.data_ptr(), self.run_stats_saved.data_ptr(),
                                                self.run_stats.numel(), self.nonfinite.data_ptr(), _stream_ptr()),
                    "od_copy_if_nonzero")
+        if self.ema_decay is not None:  # behind the restore; a skipped step leaves the averaged statistics alone too
+            _lib.check(self.lib.od_ema_update(self.ctx.handle, self.ema_run_stats.data_ptr(), self.run_stats.data_ptr(),
+                                              self.run_stats.numel(), omd, self.nonfinite.data_ptr(), _stream_ptr()),
+                       "od_ema_update")
+            self.ema_updates += 1
         self._repack()  # (a skipped step re-packs unchanged masters: harmless, and keeps the launch sequence fixed)
         host = self._flag_pool.pop() if self._flag_pool else torch.zeros(1, dtype=torch.int32).pin_memory()
         host.copy_(self.nonfinite, non_blocking=True)
@@ -606,16 +647,17 @@ class Trainer:
         self.sgd()
         return self.losses
 
-    def fit(self, batches, steps, lr_schedule=None, log_every=0, log=print):
+    def fit(self, batches, steps, lr_schedule=None, log_every=0, log=print, start_step=0):
         """Run `steps` training steps from an iterator of (x_u8 [B,H,W,3] device tensor, y_target [B,P,C] device tensor or
         list of annotations) -- what od_gen.Generator(on_device=True).flow(...) yields (the reference's unseen `fit`:
         generator -> encode_truth -> losses, check_assign.py:21-22).  lr_schedule(step) -> learning rate.  Returns the
         per-step losses [steps, 4] (objectness, class, box, total) as a numpy array; losses stay on the device until the
-        end, so the loop never synchronises."""
+        end, so the loop never synchronises.  start_step: a continued run (load_state_dict) -- the schedule is asked for
+        start_step + i, and the history covers the `steps` steps run here."""
         hist = torch.zeros((steps, 4), dtype=torch.float32, device=self.device)
         for i, (xb, yb) in zip(range(steps), batches):
             if lr_schedule is not None:
-                self.lr = float(lr_schedule(i))
+                self.lr = float(lr_schedule(start_step + i))
             if isinstance(yb, torch.Tensor):
                 self.step(xb, y_target=yb)
             else:
@@ -626,25 +668,94 @@ class Trainer:
                     f"training diverged: {self._consecutive_skips} consecutive steps produced non-finite values (step {i + 1}, loss "
                     f"scale {self.loss_scale:g}); the forward pass itself overflows f16 -- lower the learning rate (it scales "
                     f"with the batch size) or lengthen the warm-up; the weights of the last good step are intact")
-            if log_every and (i + 1) % log_every == 0:
+            if log_every and (start_step + i + 1) % log_every == 0:
                 l = hist[i].cpu().numpy()
-                log(f"step {i + 1}/{steps} lr {self.lr:.4g} loss {l[3]:.4f} (obj {l[0]:.4f} cls {l[1]:.4f} box {l[2]:.4f}) "
+                log(f"step {start_step + i + 1}/{start_step + steps} lr {self.lr:.4g} loss {l[3]:.4f} (obj {l[0]:.4f} cls {l[1]:.4f} box {l[2]:.4f}) "
                     f"loss_scale {self.loss_scale:g} skipped {self.skipped_steps}")
         self._poll_nonfinite(wait=True)
         return hist.cpu().numpy()
 
-    def export_params(self):
-        """-> dict in the weights.py format (masters + BatchNorm running statistics) for ObjectDetector(params, ...)."""
-        host = self.params.cpu().numpy()
+    def export_params(self, ema=False):
+        """-> dict in the weights.py format (masters + BatchNorm running statistics) for ObjectDetector(params, ...).
+        ema=True: the same keys and shapes from the averaged model (Trainer(ema_decay=...))."""
+        if ema and self.ema_decay is None:
+            raise ValueError("export_params(ema=True): this trainer keeps no averaged model (ema_decay=None)")
+        host = (self.ema if ema else self.params).cpu().numpy()
         out = {}
         for (name, kind), (o, n) in self.seg.items():
             _n, cin, cout, k, _s, _bn = self.specs[name]
             a = host[o:o + n]
             out[f"{name}.{kind}"] = a.reshape(cout, k, k, cin).copy() if kind == "w" else a.copy()
-        for name in self.run_mean:
-            out[name + ".mean"] = self.run_mean[name].cpu().numpy()
-            out[name + ".var"] = self.run_var[name].cpu().numpy()
+        if not ema:
+            for name in self.run_mean:
+                out[name + ".mean"] = self.run_mean[name].cpu().numpy()
+                out[name + ".var"] = self.run_var[name].cpu().numpy()
+            return out
+        rhost = self.ema_run_stats.cpu().numpy()
+        for name, o in self._run_off.items():
+            c = self.specs[name][2]
+            cp = desc.pad_to(c, 4)
+            out[name + ".mean"] = rhost[o:o + c].copy()
+            out[name + ".var"] = rhost[o + cp:o + cp + c].copy()
         return out
+
+    # ---- resumable state ------------------------------------------------------------------------------------------
+    _STATE_SCALARS = ("loss_scale", "_good_steps", "skipped_steps", "_consecutive_skips", "ema_updates")
+
+    def _layout(self):
+        """What a state's flat buffers mean: the segments of params / mom / ema in buffer order and the BatchNorm layers
+        of run_stats, as arrays an .npz can hold."""
+        keys = list(self.seg)
+        return {"layout.names": np.array([k[0] for k in keys]), "layout.kinds": np.array([k[1] for k in keys]),
+                "layout.offsets": np.array([self.seg[k][0] for k in keys], np.int64),
+                "layout.counts": np.array([self.seg[k][1] for k in keys], np.int64),
+                "layout.run_names": np.array(list(self._run_off)),
+                "layout.run_offsets": np.array(list(self._run_off.values()), np.int64),
+                "layout.sizes": np.array([self.n_flat, self.run_stats.numel()], np.int64)}
+
+    def state_dict(self):
+        """Everything a continued run needs, as host numpy arrays and scalars (weights.save_state writes it): masters,
+        momentum, BatchNorm running statistics, the averaged model when there is one, the loss-scale control's counters
+        and the layout record that load_state_dict checks.  Waits for the flags of the steps in flight first."""
+        self._poll_nonfinite(wait=True)
+        sd = {"params": self.params.cpu().numpy(), "mom": self.mom.cpu().numpy(), "run_stats": self.run_stats.cpu().numpy()}
+        if self.ema_decay is not None:
+            sd["ema"], sd["ema_run_stats"] = self.ema.cpu().numpy(), self.ema_run_stats.cpu().numpy()
+        sd["loss_scale"] = float(self.loss_scale)
+        for k in self._STATE_SCALARS[1:]:
+            sd[k] = int(getattr(self, k))
+        sd["ema_decay"] = self.ema_decay  # None = no averaged model (weights.save_state leaves a None out of the file)
+        sd.update(self._layout())
+        return sd
+
+    def load_state_dict(self, sd):
+        """Continue from a state_dict() of a trainer with the same layout and the same EMA switch (ValueError otherwise):
+        uploads every buffer, sets the counters, re-packs the f16 weights, and has the next sgd() rebuild its table."""
+        mine = self._layout()
+        for k, v in mine.items():
+            if k not in sd or not np.array_equal(np.asarray(sd[k]), v):
+                raise ValueError(f"load_state_dict: the state's {k} is not this trainer's (another architecture or class count)")
+        has_ema = "ema" in sd
+        if has_ema != (self.ema_decay is not None):
+            raise ValueError("load_state_dict: the state " + ("has" if has_ema else "has no") + " averaged model, the trainer "
+                             + ("has none (ema_decay=None)" if has_ema else "keeps one"))
+        bufs = [("params", self.params), ("mom", self.mom), ("run_stats", self.run_stats)]
+        if has_ema:
+            bufs += [("ema", self.ema), ("ema_run_stats", self.ema_run_stats)]
+        for k, t in bufs:
+            a = np.ascontiguousarray(sd[k], np.float32)
+            if a.shape != tuple(t.shape):
+                raise ValueError(f"load_state_dict: {k} has shape {a.shape}, expected {tuple(t.shape)}")
+        self._poll_nonfinite(wait=True)  # flags of this trainer's own earlier steps must not touch the loaded counters
+        for k, t in bufs:
+            t.copy_(torch.from_numpy(np.ascontiguousarray(sd[k], np.float32)))
+        self.loss_scale = float(sd["loss_scale"])
+        for k in self._STATE_SCALARS[1:]:
+            setattr(self, k, int(sd[k]))
+        if has_ema:
+            self.ema_decay = float(sd["ema_decay"])
+        self._repack()
+        self._sgd_key = None
 
 
 def make_buckets(layers, n_flat, min_elems):

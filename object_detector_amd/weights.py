@@ -87,6 +87,20 @@ def load(path):
     return params, meta
 
 
+def save_state(path, sd):
+    """Trainer.state_dict() (flat f32 buffers, scalars, the layout record) -> ONE .npz at exactly `path`.  A value of None
+    (ema_decay of a trainer without an averaged model) is left out."""
+    with open(pathlib.Path(path), "wb") as f:  # a file object: np.savez appends ".npz" to a bare name without it
+        np.savez(f, **{k: np.asarray(v) for k, v in sd.items() if v is not None})
+
+
+def load_state(path):
+    """-> the dict save_state wrote: arrays as arrays, scalars as 0-d arrays (int(), float() read them).  numpy .npz,
+    allow_pickle=False."""
+    with np.load(pathlib.Path(path), allow_pickle=False) as z:
+        return {k: z[k] for k in z.files}
+
+
 # ---- Darknet backbone import (SURVEY.md §8f rank 2) --------------------------------------------------------------
 # The reference's base network is "Darknet53 (YOLOv3's base network)" (docs/MODEL.md:15-17); its public pre-trained file is
 # `darknet53.conv.74`.  Layout of a Darknet weights file [published format, pjreddie/darknet `parser.c::load_weights`]:

@@ -64,6 +64,16 @@ def build_parser():
     p.add_argument("--shapes-difficult", default=0.0, type=float, help="--shapes: share of objects marked difficult")
     p.add_argument("--shapes-crowd", default=0.0, type=float, help="--shapes: share of images with a crowd region")
     p.add_argument("--prefetch", default=2, type=int, help="batches the generator thread runs ahead (0 = in the training thread)")
+    p.add_argument("--ema", default=None, type=float, metavar="D",
+                   help="keep an exponential moving average of the weights with decay D (0 < D < 1, warmed up from 0.1) and "
+                        "write it to <out stem>_ema.npz beside the usual file")
+    p.add_argument("--save-state-every", default=0, type=int, metavar="N",
+                   help="every N steps rank 0 writes <result-dir>/state.npz (masters, momentum, BatchNorm statistics, the "
+                        "average, loss scale, step) for --resume")
+    p.add_argument("--resume", default=None, type=pathlib.Path, metavar="FILE",
+                   help="continue from a state file at the step it recorded, up to --steps in total.  The generator is "
+                        "seeded from (seed, rank, that step), so the batches that follow are NOT those an uninterrupted run "
+                        "would have drawn")
     return p
 
 
@@ -141,34 +151,65 @@ def _run(args):
         log.info(f"fitted prior sizes (grid-cell units), level 0: {np.round(prior_wh[0], 2).tolist()}")
     tr = Trainer(params, args.batch_size, tuple(args.input_size), device=dev, lr=args.lr, momentum=args.momentum,
                  weight_decay=args.weight_decay, comm=comm, world_size=world, lr_multipliers=mult, prior_wh=prior_wh, box_mode=args.box_loss,
-                 ignore_regions=args.ignore_regions, loss_weights=(1.0, 1.0, args.box_weight))
-    gen = od_gen.create_generator(tuple(args.input_size), preprocess_input=None, encode_truth=tr.pb.encode_truth_device,
+                 ignore_regions=args.ignore_regions, loss_weights=(1.0, 1.0, args.box_weight),
+                 **({} if args.ema is None else {"ema_decay": args.ema}))
+    start, flow_seed = 0, args.seed + rank
+    if args.resume is not None:
+        sd = W.load_state(args.resume)
+        tr.load_state_dict(sd)
+        start = int(sd["step"])
+        if start >= args.steps:
+            raise SystemExit(f"{args.resume} is at step {start}: nothing left of --steps {args.steps}")
+        flow_seed = int(np.random.SeedSequence([args.seed, rank, start]).generate_state(1)[0] >> 1)
+        log.info(f"resumed from {args.resume}: starting at step {start}, loss scale {tr.loss_scale:g}, "
+                 f"ema_updates {tr.ema_updates}")
+    gen =od_gen.create_generator(tuple(args.input_size), preprocess_input=None, encode_truth=tr.pb.encode_truth_device,
                                   device=dev, on_device=True, device_cache=not args.no_device_cache, mosaic=args.mosaic,
                                   ignore_regions=args.ignore_regions)
-    batches, per_epoch = gen.flow(X, y, batch_size=args.batch_size, data_augmentation=True, shuffle=True, seed=args.seed + rank,
+    batches, per_epoch = gen.flow(X, y, batch_size=args.batch_size, data_augmentation=True, shuffle=True, seed=flow_seed,
                                   prefetch=args.prefetch)
     log.info(f"{n} images on rank {rank} of {world}, {per_epoch} steps per epoch, {args.steps} steps, lr {args.lr}, "
              f"multipliers {mult}")
     t0 = time.perf_counter()
-    hist = tr.fit(batches, args.steps, lr_schedule=cosine_schedule(args.lr, args.steps, args.warmup), log_every=args.log_every,
-                  log=log.info)
+    schedule = cosine_schedule(args.lr, args.steps, args.warmup)
+    hists, done = [], start
+    while done < args.steps:  # one fit() for the whole run, or one per --save-state-every steps
+        k = args.steps - done if args.save_state_every <= 0 else min(args.save_state_every, args.steps - done)
+        hists.append(tr.fit(batches, k, lr_schedule=schedule, log_every=args.log_every, log=log.info, start_step=done))
+        done += k
+        if args.save_state_every > 0 and tk.dl.is_main_process():
+            state = args.result_dir / "state.npz"
+            tmp = state.with_name("state.npz.tmp")
+            W.save_state(tmp, dict(tr.state_dict(), step=done))
+            tmp.replace(state)  # a run killed while writing leaves the previous state file whole
+            log.info(f"state of step {done} written to {state}")
+    hist = np.concatenate(hists)
+    ran = args.steps - start
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if args.mosaic > 0:
         log.info(f"mosaic: {json.dumps(gen.stats)}")
     batches.close()  # ends the generator's prefetch thread (a thread still issuing GPU work at interpreter exit aborts)
-    k = max(1, min(20, args.steps // 10))
+    k = max(1, min(20, ran // 10))
     log.info(f"loss first {k} steps {hist[:k, 3].mean():.4f} -> last {k} steps {hist[-k:, 3].mean():.4f}; "
-             f"{args.steps} steps in {dt:.1f} s ({args.steps * args.batch_size * world / dt:.0f} images/s), "
+             f"{ran} steps in {dt:.1f} s ({ran * args.batch_size * world / dt:.0f} images/s), "
              f"skipped {tr.skipped_steps}, loss scale {tr.loss_scale:g}")
+    if tr.ema_decay is not None:
+        log.info(f"weight average: decay {tr.ema_decay:g}, ema_updates {tr.ema_updates}")
     if tk.dl.is_main_process():
         out = args.out or (args.result_dir / "trained.npz")
         out.parent.mkdir(parents=True, exist_ok=True)
         meta = {"prior_wh": np.asarray(tr.pb.prior_wh), "loss_history": hist[:, 3]}
         if class_names is not None:
             meta["class_names"] = np.asarray(class_names)
+        if tr.ema_decay is not None:
+            meta["ema_decay"] = np.float64(tr.ema_decay)
         W.save(out, tr.export_params(), meta=meta)
         log.info(f"weights written to {out}")
+        if tr.ema_decay is not None:
+            out_ema = out.with_name(out.stem + "_ema.npz")
+            W.save(out_ema, tr.export_params(ema=True), meta=meta)
+            log.info(f"weight average written to {out_ema}")
 
 
 if __name__ == "__main__":

@@ -1,0 +1,251 @@
+"""GPU: the trainer's averaged model (Trainer(ema_decay=...): od_sgd_step_multi_ema + od_ema_update inside sgd()), its export,
+and the resumable training state (state_dict / load_state_dict / weights.save_state), against tests/optim_ref.py and
+tests/ema_ref.py.
+
+As in test_gpu_trainer_update.py the flat buffers are compared WHOLE as uint32 with no tolerance, around real steps at
+2 x 96^2: masters and momentum after sgd() are sgd_ref of the buffers right before it, the averages are ema_ref of their
+value before and the masters / running statistics after, with the decay of ema_ref.omd_ref(number of sgd() calls so far).
+"""
+import numpy as np
+import pytest
+import torch
+
+import ema_ref as E
+import optim_ref as R
+
+pytestmark = pytest.mark.gpu
+
+B, S = 2, 96
+DECAY = 0.999
+
+
+def _setup(seed=2, num_classes=20):
+    from object_detector_amd import weights as W
+    from object_detector_amd.pb import ObjectsAnnotation
+    from oracle import network as onet
+    params = W.random_init(seed, num_classes=num_classes)
+    x = onet.synthetic_images(B, S, seed=0)
+    rng = np.random.default_rng(3)
+    anns = []
+    for _ in range(B):
+        n = int(rng.integers(1, 4))
+        c = rng.uniform(0.2, 0.8, (n, 2)); wh = rng.uniform(0.15, 0.6, (n, 2))
+        anns.append(ObjectsAnnotation(None, S, S, rng.integers(0, 20, n),
+                                      np.clip(np.concatenate([c - wh / 2, c + wh / 2], 1), 0, 1).astype(np.float32)))
+    return params, x, anns
+
+
+@pytest.fixture(scope="module")
+def setup():
+    return _setup()
+
+
+def _trainer(cuda, params, **kw):
+    from object_detector_amd.trainer import Trainer
+    kw = dict(dict(lr=0.02, momentum=0.9, weight_decay=1e-4, loss_scale=256.0, ema_decay=DECAY), **kw)
+    return Trainer(params, B, (S, S), device=cuda, **kw)
+
+
+def _host(t):
+    return t.detach().cpu().numpy().copy()
+
+
+def _u32(a):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(a, np.float32).view(np.uint32).reshape(-1)
+
+
+def _same(got, want, what):
+    got, want = _u32(got), _u32(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, f"{what}: {bad.size} of {got.size} differ, first at {bad[0]}: got {got[bad[0]]:#x} want {want[bad[0]]:#x}"
+
+
+def _until_sgd(tr, xt, y, inject=False):
+    tr._poll_nonfinite()
+    tr.forward(xt)
+    tr.loss(y)
+    if inject:
+        tr.grad_pred[0, 5, 3] = float("inf")  # what an overflowing loss gradient looks like
+    tr.backward()
+    tr.allreduce()
+
+
+def _pads(tr):
+    covered = np.zeros(tr.n_flat, bool)
+    for o, n in tr.seg.values():
+        covered[o:o + n] = True
+    return ~covered
+
+
+def test_trajectory_of_the_average(cuda, setup):
+    """Four real steps; after each sgd() masters, momentum, both averages, the pads and the counter are the restated ones.
+    Then a step with an Inf injected into the loss gradient: nothing moves but the counter, run_stats is put back."""
+    params, x, anns = setup
+    tr = _trainer(cuda, params)
+    assert tr.ema_updates == 0 and tr.ema.data_ptr() != tr.params.data_ptr()
+    _same(tr.ema, tr.params, "the average starts as a copy of the masters")
+    _same(tr.ema_run_stats, tr.run_stats, "the averaged statistics start as a copy")
+    xt = torch.from_numpy(x).to(cuda)
+    y, _npos, _ = tr.pb.encode_batch(anns, return_device=True)
+    pads = _pads(tr)
+    for i, lr in enumerate((0.02, 0.02, 0.005, 0.013)):
+        tr.lr = lr
+        _until_sgd(tr, xt, y)
+        torch.cuda.synchronize()
+        w0, m0, g0, e0, re0 = (_host(t) for t in (tr.params, tr.mom, tr.grads, tr.ema, tr.ema_run_stats))
+        inv = np.float32(1.0 / tr.loss_scale)
+        omd = E.omd_ref(i, DECAY, True)
+        assert omd == np.float32(1.0 - min(DECAY, (1.0 + i) / (10.0 + i)))
+        tr.sgd()
+        torch.cuda.synchronize()
+        assert int(tr.nonfinite.item()) == 0 and tr.ema_updates == i + 1
+        we, me, ee = w0.copy(), m0.copy(), e0.copy()
+        for (name, kind), (o, n) in tr.seg.items():
+            lr_seg = np.float32(tr.lr * R.lr_mult_ref(name))
+            we[o:o + n], me[o:o + n] = R.sgd_ref(w0[o:o + n], m0[o:o + n], g0[o:o + n], lr_seg, 0.9, 1e-4 if kind == "w" else 0.0, inv)
+            ee[o:o + n] = E.ema_ref(e0[o:o + n], we[o:o + n], omd)
+        _same(tr.params, we, f"step {i}: params")
+        _same(tr.mom, me, f"step {i}: momentum")
+        _same(tr.grads, g0, f"step {i}: gradients")
+        _same(tr.ema, ee, f"step {i}: ema")
+        _same(tr.ema_run_stats, E.ema_ref(re0, _host(tr.run_stats), omd), f"step {i}: ema_run_stats")
+        for t, name in ((tr.params, "params"), (tr.mom, "mom"), (tr.ema, "ema")):
+            assert not _u32(t)[pads].any(), f"step {i}: a pad of {name} is not +0"
+        moved = sum(bool((_u32(tr.ema)[o:o + n] != _u32(e0)[o:o + n]).any()) for o, n in tr.seg.values())
+        assert moved == len(tr.seg), f"step {i}: the average of only {moved} of {len(tr.seg)} segments moved"
+    assert (_u32(tr.ema) != _u32(tr.params)).any() and (_u32(tr.ema_run_stats) != _u32(tr.run_stats)).any()
+    # ---- a skipped step
+    tr._poll_nonfinite(wait=True)
+    keep = {k: _host(getattr(tr, k)) for k in ("params", "mom", "ema", "ema_run_stats", "run_stats")}
+    _until_sgd(tr, xt, y, inject=True)
+    torch.cuda.synchronize()
+    assert (_u32(tr.run_stats) != _u32(keep["run_stats"])).any()  # the forward pass folded its batch statistics in
+    tr.sgd()
+    tr._poll_nonfinite(wait=True)
+    assert int(tr.nonfinite.item()) == 1 and tr.skipped_steps == 1
+    for k, v in keep.items():
+        _same(getattr(tr, k), v, f"skipped step: {k}")
+    assert tr.ema_updates == 5  # attempted steps count: the schedule does not wait for the host to learn of the skip
+
+
+def test_ema_off_is_the_plain_trainer_and_bad_decays_are_refused(cuda, setup):
+    from object_detector_amd.trainer import Trainer
+    params, x, anns = setup
+    tr = _trainer(cuda, params, ema_decay=None)
+    assert tr.ema is None and tr.ema_run_stats is None and tr.ema_decay is None and tr.ema_updates == 0
+    with pytest.raises(ValueError):
+        tr.export_params(ema=True)
+    for bad in (0.0, 1.0, -0.1, 1.5, float("nan")):
+        with pytest.raises(ValueError):
+            Trainer(params, B, (S, S), device=cuda, ema_decay=bad)
+
+
+@pytest.fixture(scope="module")
+def trained(cuda, setup):
+    """A trainer three steps into a run, shared by the tests below (the round-trip test takes it one sgd() further; no test
+    depends on where it stands)."""
+    params, x, anns = setup
+    tr = _trainer(cuda, params)
+    xt = torch.from_numpy(x).to(cuda)
+    for _ in range(3):
+        tr.step(xt, anns)
+    tr._poll_nonfinite(wait=True)
+    return tr, xt, anns
+
+
+def test_export_of_the_average_drives_a_detector(cuda, trained):
+    from object_detector_amd.detector import ObjectDetector
+    tr, xt, _anns = trained
+    plain, avg = tr.export_params(), tr.export_params(ema=True)
+    assert list(plain) == list(avg)
+    e, rs = _host(tr.ema), _host(tr.ema_run_stats)
+    differs = 0
+    for k in plain:
+        assert avg[k].shape == plain[k].shape and avg[k].dtype == plain[k].dtype == np.float32, k
+        differs += bool((avg[k] != plain[k]).any())
+    assert differs == len(plain)
+    for (name, kind), (o, n) in tr.seg.items():
+        _same(avg[f"{name}.{kind}"], e[o:o + n], f"{name}.{kind}")
+    for name in tr.run_mean:
+        c = tr.specs[name][2]
+        o = tr.run_mean[name].data_ptr() - tr.run_stats.data_ptr() >> 2
+        o2 = tr.run_var[name].data_ptr() - tr.run_stats.data_ptr() >> 2
+        _same(avg[name + ".mean"], rs[o:o + c], name + ".mean")
+        _same(avg[name + ".var"], rs[o2:o2 + c], name + ".var")
+    od = ObjectDetector(avg, B, (S, S), device=cuda)
+    keep, cnt = od.predict_batch_device(xt, conf_threshold=0.01)
+    torch.cuda.synchronize()
+    assert torch.isfinite(od.net.pred).all() and int(cnt.min()) >= 0
+    assert torch.isfinite(od.post.conf).all() and torch.isfinite(od.post.boxes).all()
+
+
+def test_state_round_trip_continues_bit_for_bit(cuda, trained, tmp_path):
+    """state_dict -> save_state -> load_state -> load_state_dict into a trainer built from OTHER random weights: buffers,
+    scalars and f16 packs are the first trainer's, and the same gradients then move both alike."""
+    from object_detector_amd import weights as W
+    tr, _xt, _anns = trained
+    tr.loss_scale, tr._good_steps, tr.skipped_steps, tr._consecutive_skips = 128.0, 17, 3, 2
+    sd = tr.state_dict()
+    assert not tr._flag_queue
+    assert set(sd) >= {"params", "mom", "run_stats", "ema", "ema_run_stats", "loss_scale", "_good_steps", "skipped_steps",
+                       "_consecutive_skips", "ema_updates", "ema_decay", "layout.names", "layout.kinds", "layout.offsets",
+                       "layout.counts"}
+    assert all(isinstance(sd[k], np.ndarray) for k in ("params", "mom", "run_stats", "ema", "ema_run_stats"))
+    assert [tuple(v) for v in zip(sd["layout.names"], sd["layout.kinds"])] == list(tr.seg)
+    assert [tuple(int(a) for a in v) for v in zip(sd["layout.offsets"], sd["layout.counts"])] == list(tr.seg.values())
+    W.save_state(tmp_path / "state.npz", sd)
+    other = _trainer(cuda, _setup(seed=7)[0], lr=0.5)
+    assert (_u32(other.params) != _u32(tr.params)).any()
+    other._sgd_key = "stale"
+    other.load_state_dict(W.load_state(tmp_path / "state.npz"))
+    assert other._sgd_key is None
+    for k in ("params", "mom", "run_stats", "ema", "ema_run_stats"):
+        _same(getattr(other, k), getattr(tr, k), k)
+    for k in ("loss_scale", "_good_steps", "skipped_steps", "_consecutive_skips", "ema_updates", "ema_decay"):
+        assert getattr(other, k) == getattr(tr, k) and type(getattr(other, k)) is type(getattr(tr, k)), k
+    assert (other.loss_scale, other._good_steps, other.skipped_steps, other._consecutive_skips, other.ema_updates) == (128.0, 17, 3, 2, 3)
+    torch.cuda.synchronize()
+    w = _host(other.params)
+    for name in ("b.s3.0.a", "b.down3", "h.out"):
+        _n, cin, cout, k, _s, _bn = other.specs[name]
+        o, n = other.seg[(name, "w")]
+        dims = R.pack_dims(cout, cin, k)
+        wf, wt = R.pack_ref(w[o:o + n].reshape(cout, k * k * cin), cout, cin, k, *dims, 0)
+        assert np.array_equal(other.wf[name].cpu().numpy().view(np.uint16), wf), name
+        assert np.array_equal(other.wb[name].cpu().numpy().view(np.uint16), wt), name
+    # the same gradients into both
+    rng = np.random.default_rng(11)
+    g = torch.from_numpy(R.values(rng, tr.n_flat, -4, 0)).to(cuda)
+    for t in (tr, other):
+        t.lr = 0.02
+        t.grads.copy_(g)
+        t.sgd()
+    torch.cuda.synchronize()
+    for k in ("params", "mom", "ema", "ema_run_stats"):
+        _same(getattr(other, k), getattr(tr, k), f"after one more sgd(): {k}")
+    assert (_u32(other.params) != w.view(np.uint32)).any() and other.ema_updates == tr.ema_updates == 4
+
+
+def test_state_of_another_layout_or_switch_is_refused(cuda, trained):
+    tr, _xt, _anns = trained
+    sd = tr.state_dict()
+    before = {k: _host(getattr(tr, k)) for k in ("params", "mom", "ema")}
+    wide = _trainer(cuda, _setup(num_classes=21)[0])
+    with pytest.raises(ValueError):
+        tr.load_state_dict(wide.state_dict())
+    with pytest.raises(ValueError):
+        wide.load_state_dict(sd)
+    plain = _trainer(cuda, _setup()[0], ema_decay=None)
+    with pytest.raises(ValueError):
+        plain.load_state_dict(sd)  # a state with an average into a trainer without
+    with pytest.raises(ValueError):
+        tr.load_state_dict(plain.state_dict())
+    for k, v in before.items():
+        _same(getattr(tr, k), v, f"a refused state leaves {k} alone")
+    # a plain trainer's state goes into a plain trainer
+    sd0 = plain.state_dict()
+    assert "ema" not in sd0 and sd0["ema_decay"] is None
+    plain.load_state_dict(sd0)
