@@ -565,6 +565,51 @@ int od_rgb_resize(od_ctx* ctx, const od_img_desc* descs_host, const od_img_desc*
                   long long blob_bytes, void* workspace, long long ws_bytes, uint8_t* out, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sliced inference (BUILD-DEFINED; DESIGN.md "Sliced inference"): ObjectDetector(slices=(ny, nx)) cuts every image into
+ * T overlapping tiles (+ the whole image as the last tile), runs them as T rows of the network batch and merges the T
+ * candidate lists of an image in ONE NMS + box voting.  object_detector_amd/slicing.py defines the rectangles.
+ *
+ * od_tiles_resize: row n of out uint8 [N,H,W,3] = the rectangle (x0, y0, x1, y1) of tile n's source image resized to W x H
+ * = PIL crop((x0, y0, x1, y1)).resize((W, H), BILINEAR), byte for byte (resize of the crop, not resize(box=)).  The source
+ * sits once in `blob` at full resolution: packed uint8 rows of src_w pixels, `pitch` bytes apart (any pitch >= 3 * src_w),
+ * pixel (0, 0) at src_off (no alignment needed).  hcoef / vcoef: the tables of od_img_desc for (x1 - x0 -> W) and
+ * (y1 - y0 -> H), 4-byte aligned.  Passes, their order (vertical first for a tile more than 100 times as tall as wide that
+ * shrinks vertically) and the skipping of a pass whose length does not change are Image.resize's.  No source byte outside
+ * the rectangle is read.  od_tiles_workspace_plan lays the intermediate images out (tmp_ws) and returns the workspace
+ * size (it may be 0; pass a valid pointer all the same).  Rows of out from N on are not touched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct od_tile_desc {
+  int64_t src_off; /* byte offset of the source image in blob */
+  int64_t pitch;   /* source row pitch in bytes */
+  int32_t src_w, src_h;
+  int32_t x0, y0, x1, y1; /* 0 <= x0 < x1 <= src_w, 0 <= y0 < y1 <= src_h */
+  int32_t hk, vk;         /* taps per row of the two tables */
+  int64_t hcoef_off, vcoef_off;
+  int64_t tmp_ws;
+} od_tile_desc;
+int od_tiles_workspace_plan(od_tile_desc* descs_host, int N, int H, int W, long long* workspace_bytes);
+int od_tiles_resize(od_ctx* ctx, const od_tile_desc* descs_host, const od_tile_desc* descs, int N, const uint8_t* blob,
+                    long long blob_bytes, void* workspace, long long ws_bytes, uint8_t* out, int H, int W, void* stream);
+
+/* od_slice_merge: image g of G owns the batch rows g*T .. g*T + T - 1 (1 <= T <= 16) of what od_detect_candidates (clip = 1)
+ * produced for the whole batch: keys u64 [.,K] sorted descending, counts i32 [.], boxes f32 [.,P,4] in tile coordinates.
+ * tiles f32 [G*T,4] = (ox, oy, sx, sy), the tile's origin and size as fractions of its image; edges i32 [G*T]: bit 0 / 1 /
+ * 2 / 3 = the tile's left / top / right / bottom side is interior (not on the image border).  All f32, one rounding per op:
+ *   candidate (t, r), r < counts[g*T + t], box (x1, y1, x2, y2): dropped when cut at a seam, i.e. when edge_lo >= 0 and
+ *       (left interior and x1 <= edge_lo) or (top interior and y1 <= edge_lo) or (right interior and x2 >= edge_hi) or
+ *       (bottom interior and y2 >= edge_hi);  edge_lo < 0 disables the rule
+ *   a survivor's box in image coordinates: X = min(max(ox + sx * x, 0), 1), Y = min(max(oy + sy * y, 0), 1)
+ *   merged order: conf bits desc, tile asc, flat asc; the first Km = min(K, survivors) are kept
+ *   then exactly od_tta_merge: greedy NMS, box voting (vote_iou), the record block `out` f32 [G][1 + 6*max_det] with the
+ *       class in word 0 of a row, src i32 [G,max_det,2] (may be NULL) = (tile, flat index in that row), keep_count i32 [G].
+ * K <= 1024.  workspace: od_slice_merge_workspace_bytes(G, T, K), needs no initialisation. */
+size_t od_slice_merge_workspace_bytes(int G, int T, int K);
+int od_slice_merge(od_ctx* ctx, const uint64_t* keys, const int32_t* counts, const float* boxes, const float* tiles,
+                   const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo, float edge_hi,
+                   float iou_threshold, int strict, int max_det, float vote_iou, float* out, int32_t* src,
+                   int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K16: COCO bbox evaluation (tk.data.coco.evaluate; object_detector_amd/cocoeval.py states the protocol and packs the
  * inputs).  pycocotools COCOeval parameters, fixed: T IoU thresholds, A area ranges, R recall thresholds, M maxDets.
  * All f64 arithmetic is the exact op sequence of the protocol (no contraction), so results are bit-identical to numpy.

@@ -120,7 +120,14 @@ class TtaView(C.Structure):
     _fields_ = [("keys", C.c_void_p), ("counts", C.c_void_p), ("boxes", C.c_void_p), ("P", C.c_int32), ("flip", C.c_int32)]
 
 
-STRUCTS = (TtaView, ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
+class TileDesc(C.Structure):
+    C_NAME = "od_tile_desc"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
+    _fields_ = [("src_off", C.c_int64), ("pitch", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("src_w", "src_h", "x0", "y0", "x1", "y1", "hk", "vk")] + \
+               [(n, C.c_int64) for n in ("hcoef_off", "vcoef_off", "tmp_ws")]
+
+
+STRUCTS = (TileDesc, TtaView, ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
 
 
 class OdError(RuntimeError):
@@ -254,6 +261,13 @@ _PROTOS = {
                                         C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "od_rgb_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p,
                                 C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "od_tiles_workspace_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "od_tiles_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p,
+                                  C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "od_slice_merge_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "od_slice_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "od_coco_match_workspace_bytes": (C.c_size_t, [C.c_longlong]),
     "od_coco_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -121,6 +121,11 @@ const std::vector<StructInfo>& od_struct_table() {
         OD_F(od_img_desc, sub_off), OD_F(od_img_desc, huff_off), OD_F(od_img_desc, quant_off), OD_F(od_img_desc, src_off),
         OD_F(od_img_desc, hcoef_off), OD_F(od_img_desc, vcoef_off), OD_F(od_img_desc, coef_ws),
         OD_F(od_img_desc, plane_ws), OD_F(od_img_desc, rgb_ws), OD_F(od_img_desc, tmp_ws), OD_F(od_img_desc, state_ws)}},
+      {"od_tile_desc", sizeof(od_tile_desc),
+       {OD_F(od_tile_desc, src_off), OD_F(od_tile_desc, pitch), OD_F(od_tile_desc, src_w), OD_F(od_tile_desc, src_h),
+        OD_F(od_tile_desc, x0), OD_F(od_tile_desc, y0), OD_F(od_tile_desc, x1), OD_F(od_tile_desc, y1),
+        OD_F(od_tile_desc, hk), OD_F(od_tile_desc, vk), OD_F(od_tile_desc, hcoef_off), OD_F(od_tile_desc, vcoef_off),
+        OD_F(od_tile_desc, tmp_ws)}},
       {"od_plan_op", sizeof(od_plan_op),
        {OD_F(od_plan_op, kind), OD_F(od_plan_op, pad_), OD_F(od_plan_op, conv), OD_F(od_plan_op, bneck),
         OD_F(od_plan_op, stem), OD_F(od_plan_op, wide)}},

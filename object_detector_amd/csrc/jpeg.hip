@@ -8,11 +8,11 @@
 //   od_jpeg_idct_k   libjpeg jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2, its range limit), one thread per block
 //   od_jpeg_color_k  libjpeg-turbo's default upsampling (fancy h2v1 / h2v2, replication for chroma <= 2 wide) and
 //                    jdcolor's YCbCr->RGB tables (SCALEBITS 16)
-//   od_img_hpass_k / od_img_vpass_k   Pillow's fixed-point BILINEAR passes (22 fraction bits), letterbox zeros;
+//   od_img_hpass_k / od_img_vpass_k   Pillow's fixed-point BILINEAR passes (22 fraction bits; resample_common.h), letterbox zeros;
 //                    horizontal then vertical, the other way round where Image.resize does so (vertical_first)
 // Bounds: every stream read is clipped to its restart interval, every coefficient write to the interval's blocks, and
 // the host checks every offset of the descriptors against the blob and workspace sizes before a launch.
-#include "common.h"
+#include "resample_common.h"
 
 namespace {
 
@@ -421,29 +421,10 @@ __device__ __forceinline__ const uint8_t* img_src(const uint8_t* blob, const uin
   return d.kind == OD_IMG_JPEG ? ws + d.rgb_ws : blob + d.src_off;
 }
 
-__device__ __forceinline__ uint8_t clip8(int64_t acc) {
-  return (uint8_t)min(max(acc >> 22, (int64_t)0), (int64_t)255);
-}
-
 // Image.resize runs the vertical pass first for an image more than 100 times as tall as wide that shrinks vertically
 // (the intermediate image is then the small one); the rounding to 8 bits between the passes makes the order visible
 __host__ __device__ __forceinline__ bool vertical_first(const od_img_desc& d) {
   return d.height > (int64_t)100 * d.width && d.out_h < d.height;
-}
-
-// one output pixel of a pass: taps of table row t over source pixels `step` bytes apart
-__device__ __forceinline__ void resample_px(const uint8_t* s, int64_t step, const int* t, uint8_t* o) {
-  const int nt = t[1];
-  int64_t a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
-  for (int k = 0; k < nt; ++k) {
-    const int64_t w = t[2 + k];
-    a0 += s[k * step] * w;
-    a1 += s[k * step + 1] * w;
-    a2 += s[k * step + 2] * w;
-  }
-  o[0] = clip8(a0);
-  o[1] = clip8(a1);
-  o[2] = clip8(a2);
 }
 
 // first pass into tmp.  Horizontal: source [height, width] -> tmp [height, out_w], skipped when out_w == width.

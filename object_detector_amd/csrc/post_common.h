@@ -229,3 +229,16 @@ int od_nms_greedy_launch(void* nms_workspace, const int32_t* counts, int B, int 
                          int32_t* keep_flat, int32_t* keep_count, hipStream_t stream);
 // nms.hip: where od_nms keeps the sorted keys / gathered boxes / classes inside its workspace (KP = next power of two >= K)
 void od_nms_sorted_buffers(void* nms_workspace, int B, int K, unsigned long long** skeys, f32x4** sbox, int** scls, int* KP);
+// tta.hip: the workspace of a merged candidate table (od_tta_merge, od_slice_merge) -- od_nms's workspace, the merged count
+// [B], the (list, flat) source of every merged rank [B,KP,2] and the scan's kept list [B,K] -- and what follows the rank
+// kernel that fills it: od_nms_greedy_k, then the vote-and-gather kernel
+struct OdMergeWs {
+  void* nms;
+  int* mcount;
+  int* msrc;
+  int* keepf;
+};
+size_t od_merge_workspace_bytes(int B, int K);
+OdMergeWs od_merge_workspace(void* workspace, int B, int K);
+int od_merge_nms_vote_launch(const OdMergeWs& w, int B, int NC, int K, float iou_threshold, int strict, int max_det,
+                             float vote_iou, float* out, int32_t* src, int32_t* keep_count, hipStream_t s);

@@ -257,6 +257,29 @@ TtaLayout tta_layout(int B, int K) {
 
 }  // namespace
 
+size_t od_merge_workspace_bytes(int B, int K) { return tta_layout(B, K).total; }
+
+OdMergeWs od_merge_workspace(void* workspace, int B, int K) {
+  const TtaLayout l = tta_layout(B, K);
+  char* ws = (char*)workspace;
+  return OdMergeWs{ws + l.nms, (int*)(ws + l.mcount), (int*)(ws + l.msrc), (int*)(ws + l.keepf)};
+}
+
+int od_merge_nms_vote_launch(const OdMergeWs& w, int B, int NC, int K, float iou_threshold, int strict, int max_det,
+                             float vote_iou, float* out, int32_t* src, int32_t* keep_count, hipStream_t s) {
+  u64* skeys;
+  f32x4* sbox;
+  int* scls;
+  int KP;
+  od_nms_sorted_buffers(w.nms, B, K, &skeys, &sbox, &scls, &KP);
+  const int md = max_det < K ? max_det : K;  // at most Km <= K are ever kept: the scan's list needs no more slots
+  if (int rc = od_nms_greedy_launch(w.nms, w.mcount, B, K, iou_threshold, strict, md, w.keepf, keep_count, s)) return rc;
+  hipLaunchKernelGGL(od_tta_vote_gather, dim3(B), dim3(1024), 0, s, skeys, sbox, scls, w.msrc, w.mcount, w.keepf, keep_count, NC,
+                     KP, md, max_det, vote_iou, out, src);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
 extern "C" int od_hflip_u8(od_ctx* ctx, const uint8_t* src, uint8_t* dst, int B, int H, int W, void* stream) {
   OD_REQUIRE(ctx && src && dst, "od_hflip_u8: null argument");
   OD_REQUIRE(B > 0 && H > 0 && W > 0, "od_hflip_u8: bad dims");
@@ -278,7 +301,7 @@ extern "C" int od_hflip_u8(od_ctx* ctx, const uint8_t* src, uint8_t* dst, int B,
 
 extern "C" size_t od_tta_merge_workspace_bytes(int B, int V, int K) {
   if (B <= 0 || V < 1 || V > TTA_MAX_VIEWS || K <= 0 || K > TTA_MAX_K) return 0;
-  return tta_layout(B, K).total;  // the merged table holds K candidates however many views feed it
+  return od_merge_workspace_bytes(B, K);  // the merged table holds K candidates however many views feed it
 }
 
 extern "C" int od_tta_merge(od_ctx* ctx, const od_tta_view* views, int V, int B, int NC, int K, float iou_threshold,
@@ -299,28 +322,19 @@ extern "C" int od_tta_merge(od_ctx* ctx, const od_tta_view* views, int V, int B,
     vw.P[v] = views[v].P;
     vw.flip[v] = views[v].flip != 0;
   }
-  const TtaLayout l = tta_layout(B, K);
-  if (workspace_bytes < l.total) {
-    od_set_error("od_tta_merge: workspace %zu < %zu bytes", workspace_bytes, l.total);
+  const size_t need = od_merge_workspace_bytes(B, K);
+  if (workspace_bytes < need) {
+    od_set_error("od_tta_merge: workspace %zu < %zu bytes", workspace_bytes, need);
     return OD_ERR_WORKSPACE;
   }
-  char* ws = (char*)workspace;
-  void* nms_ws = ws + l.nms;
-  int* mcount = (int*)(ws + l.mcount);
-  int* msrc = (int*)(ws + l.msrc);
-  int* keepf = (int*)(ws + l.keepf);
+  const OdMergeWs w = od_merge_workspace(workspace, B, K);
   u64* skeys;
   f32x4* sbox;
   int* scls;
   int KP;
-  od_nms_sorted_buffers(nms_ws, B, K, &skeys, &sbox, &scls, &KP);
+  od_nms_sorted_buffers(w.nms, B, K, &skeys, &sbox, &scls, &KP);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(od_tta_merge_rank, dim3(B), dim3(1024), 0, s, vw, NC, K, KP, skeys, sbox, scls, msrc, mcount);
+  hipLaunchKernelGGL(od_tta_merge_rank, dim3(B), dim3(1024), 0, s, vw, NC, K, KP, skeys, sbox, scls, w.msrc, w.mcount);
   OD_CHECK_LAUNCH();
-  const int md = max_det < K ? max_det : K;  // at most Km <= K are ever kept: the scan's list needs no more slots
-  if (int rc = od_nms_greedy_launch(nms_ws, mcount, B, K, iou_threshold, strict, md, keepf, keep_count, s)) return rc;
-  hipLaunchKernelGGL(od_tta_vote_gather, dim3(B), dim3(1024), 0, s, skeys, sbox, scls, msrc, mcount, keepf, keep_count, NC, KP, md,
-                     max_det, vote_iou, out, src);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
+  return od_merge_nms_vote_launch(w, B, NC, K, iou_threshold, strict, max_det, vote_iou, out, src, keep_count, s);
 }

@@ -16,6 +16,7 @@ import pathlib
 import numpy as np
 import torch
 
+from . import slicing
 from . import weights as W
 from .net import Net
 from .pb import ObjectsAnnotation, PriorBoxes
@@ -138,9 +139,10 @@ def stream_queue_sets(device, n, candidates=6, seed_streams=(), beside=None):
 class _Pipeline:
     """One batch in flight: its own activation buffers (Net), post-processing buffers and HIP stream."""
 
-    def __init__(self, net, post, stream, tta=None):
+    def __init__(self, net, post, stream, tta=None, slc=None):
         self.net, self.post, self.stream = net, post, stream
         self.tta = tta  # TtaPostprocessor beside `post` when the detector runs test-time augmentation
+        self.slc = slc  # slicing.SlicePostprocessor beside `post` when the detector runs sliced inference
         self.done = torch.cuda.Event()
         self.decoder = None  # devdecode.BatchDecoder of image_decode="device", made on first use
 
@@ -148,11 +150,17 @@ class _Pipeline:
 class ObjectDetector:
     def __init__(self, params, batch_size=16, input_size=(320, 320), keep_aspect=False, strict_nms=False,
                  use_multi_gpu=True, device=None, prior_wh=None, n_inflight=None, precision=None, image_decode="host",
-                 tta=None, tta_vote_iou=VOTE_IOU):
+                 tta=None, tta_vote_iou=VOTE_IOU, slices=None, slice_overlap=0.2, slice_full_view=True, slice_edge=0.01,
+                 slice_vote_iou=VOTE_IOU):
         # test-time augmentation: None = off (the plain path, unchanged); () = the identity view alone (box voting only);
         # ("flip",) = identity + horizontal mirror, merged on the device (tta.py).  Checked before anything touches the GPU.
         self.tta = normalize_views(tta)
         self.tta_vote_iou = float(tta_vote_iou)
+        # sliced inference: None = off (the plain path, unchanged); (ny, nx) = every image is cut into ny x nx overlapping
+        # tiles (+ the whole image), T rows of the network batch each, merged on the device (slicing.py).  Also checked here.
+        self.slices = slicing.normalize(slices, slice_overlap, slice_full_view, slice_edge, batch_size=batch_size, tta=tta,
+                                        keep_aspect=keep_aspect)
+        self.slice_vote_iou = float(slice_vote_iou)
         if device is None:  # one process per GPU; the modulo only matters when several ranks rehearse on one GPU
             device = f"cuda:{int(os.environ.get('LOCAL_RANK', 0)) % max(1, torch.cuda.device_count())}"
         if not torch.cuda.is_available():
@@ -185,14 +193,16 @@ class ObjectDetector:
         # tails, epilogue write bursts and the small post-processing kernels of one batch overlap the convolutions of the
         # next (measured +23 % images/s at batch 32 with 2-3 in flight, profiles/r01/inflight_sweep.txt).  Pipeline 0 =
         # (self.net, self.post) on the caller's stream is what predict_batch_device uses.
-        self._pipes = [_Pipeline(self.net, self.post, torch.cuda.Stream(device=self.device), self._make_tta(self.post))]
+        self._pipes = [_Pipeline(self.net, self.post, torch.cuda.Stream(device=self.device), self._make_tta(self.post),
+                                 self._make_slc(self.net, self.post))]
         for _ in range(max(1, n) - 1):
             net = Net(params, self.batch_size, self.input_size, device=self.device, overlapped=True,
                       share_weights_with=self.net, precision=self.precision, stream_stages=self.net.stream_stages,
                       split=self.net.split, wide_fpn=self.net.wide_fpn)
             post = Postprocessor(self.batch_size, net.P, self.num_classes, self.pb.pb_locs, device=self.device,
                                  strict_nms=self.strict_nms, loc_scale=self.pb.loc_scale)
-            self._pipes.append(_Pipeline(net, post, torch.cuda.Stream(device=self.device), self._make_tta(post)))
+            self._pipes.append(_Pipeline(net, post, torch.cuda.Stream(device=self.device), self._make_tta(post),
+                                         self._make_slc(net, post)))
         self._next = 0
         self._calibrated = len(self._pipes) < 2 or os.environ.get("OD_INFLIGHT_CALIBRATE", "1") == "0"
 
@@ -200,6 +210,21 @@ class ObjectDetector:
         if self.tta is None:
             return None
         return TtaPostprocessor(post, self.net.input.shape, self.tta, self.tta_vote_iou)
+
+    def _make_slc(self, net, post):
+        if self.slices is None:
+            return None
+        slc = slicing.SlicePostprocessor(post, self.slices, self.slice_vote_iou)
+        net.input[slc.G * slc.T:].zero_()  # rows no image's tile ever lands in: zeroed once, their candidates are never read
+        torch.cuda.current_stream(self.device).synchronize()  # the pipelines write this buffer on their own streams
+        return slc
+
+    def _no_batch_entry_with_slices(self, what, graph=False):
+        if self.slices is not None:
+            if graph:
+                raise ValueError("graph=True is not available with slices: the sliced step is not one captured plan")
+            raise ValueError(f"{what} takes a ready-made batch and a sliced batch needs its tile rectangles: "
+                             f"with slices, predict() is the public route")
 
     @staticmethod
     def _no_graph_with_tta(graph):
@@ -233,7 +258,9 @@ class ObjectDetector:
     def predict_batch_device(self, x_u8: torch.Tensor, conf_threshold=DEFAULT_CONF_THRESHOLD, graph=False):
         """uint8 [B,H,W,3] on device -> (keep_flat [B,max_det], keep_count [B]) on device.  The timed hot path.
         With tta: -> (det f32 [B, 1 + 6*max_det], keep_count [B]) on device; det is od_tta_merge's record block (word 0 =
-        keep count, row r = {class (int bits), conf, x1, y1, x2, y2}): a merged detection has no single flat index."""
+        keep count, row r = {class (int bits), conf, x1, y1, x2, y2}): a merged detection has no single flat index.
+        With slices: ValueError (predict() is the route)."""
+        self._no_batch_entry_with_slices("predict_batch_device", graph)
         torch.cuda.current_stream(self.device).wait_stream(self._pipes[0].stream)  # pipeline 0's buffers may be in flight
         if self.tta is not None:
             self._no_graph_with_tta(graph)
@@ -249,7 +276,9 @@ class ObjectDetector:
     def submit(self, x_u8: torch.Tensor, conf_threshold=DEFAULT_CONF_THRESHOLD, graph=False, gather=False) -> int:
         """Queue one batch on the next pipeline's stream and return its ticket.  Never blocks the host: a pipeline's new
         batch is stream-ordered behind its previous one (whose results it overwrites -- collect() them first).
-        With tta every view runs on that stream and the merged record block is always copied to the host (`gather` is moot)."""
+        With tta every view runs on that stream and the merged record block is always copied to the host (`gather` is moot).
+        With slices: ValueError (predict() is the route)."""
+        self._no_batch_entry_with_slices("submit", graph)
         if self.tta is not None:
             self._no_graph_with_tta(graph)
         if not self._calibrated:
@@ -309,7 +338,8 @@ class ObjectDetector:
 
     def collect(self, ticket: int):
         """Wait for the batch submitted with `ticket`; -> (keep_flat [B,max_det], keep_count [B]) on device.
-        With tta: -> (det [B, 1 + 6*max_det], keep_count [B]), as predict_batch_device."""
+        With tta: -> (det [B, 1 + 6*max_det], keep_count [B]), as predict_batch_device.  With slices: ValueError."""
+        self._no_batch_entry_with_slices("collect")
         p = self._pipes[ticket]
         p.done.synchronize()
         if p.tta is not None:
@@ -366,11 +396,15 @@ class ObjectDetector:
 
     def predict(self, X, conf_threshold=DEFAULT_CONF_THRESHOLD, verbose=0, image_decode=None):
         """X: sequence of image paths or uint8 arrays -> list[ObjectsPrediction] in input order.
-        image_decode: "host" / "device" for this call (None = the detector's setting)."""
+        image_decode: "host" / "device" for this call (None = the detector's setting).
+        With slices every image is cut into tiles that share a network batch (_predict_sliced): bboxes are in [0,1]
+        coordinates of the whole image and flat_indices is None."""
         X = list(X)
         route = self.image_decode if image_decode is None else image_decode
         if route not in ("host", "device"):
             raise ValueError(f"image_decode must be 'host' or 'device', got {route!r}")
+        if self.slices is not None:
+            return self._predict_sliced(X, conf_threshold, route)
         rank, world = dist_info(self.use_multi_gpu)
         mine = shard_indices(len(X), rank, world)
         results = {}
@@ -477,6 +511,108 @@ class ObjectDetector:
         finally:
             if own_pool is not None:
                 own_pool.shutdown(wait=True)
+        for entry in pending:
+            drain(entry)
+        results = gather_results(results, world)
+        return [results[i] for i in range(len(X))]
+
+    # -- sliced inference -------------------------------------------------------------------------------------------
+    def _submit_sliced(self, conf_threshold, x_u8=None, sizes=None, images=None, cut_only=False) -> int:
+        """Queue one sliced batch (at most G = batch_size // T images) on the next pipeline's stream; -> its ticket.
+        Host route: x_u8 uint8 [B,H,W,3] holds the tiles (row g*T + t = tile t of image g), sizes the images' (w, h).
+        Device route: images = the uint8 [h,w,3] arrays; one upload, then od_tiles_resize writes the pipeline's Net.input.
+        cut_only: the images are the ones the pipeline's decoder uploaded last (scripts/bench_slices.py)."""
+        if not self._calibrated:
+            self._pick_streams()
+        i = self._next
+        self._next = (i + 1) % len(self._pipes)
+        p = self._pipes[i]
+        p.stream.wait_stream(torch.cuda.current_stream(self.device))  # x_u8 was produced on the caller's stream
+        with torch.cuda.stream(p.stream):
+            if images is not None:
+                if p.decoder is None:
+                    from .devdecode import BatchDecoder
+                    p.decoder = BatchDecoder(self.device)
+                if cut_only:
+                    p.decoder.cut_tiles(p.net.input)
+                else:
+                    sizes = p.decoder.run_tiles(images, self.slices, p.net.input)
+            p.slc.run(p.net, x_u8, sizes, conf_threshold)
+            p.done.record()
+        if x_u8 is not None:
+            x_u8.record_stream(p.stream)
+        return i
+
+    def _predict_sliced(self, X, conf_threshold, route):
+        """predict() with slices: G = batch_size // T images per network batch.  Same shape as the plain route: images are
+        sharded by index over the ranks, pool threads prepare the next batches while this one runs, a pipeline's results are
+        read before it is reused.  Host route: the threads crop and resize every tile with PIL into pinned staging.  Device
+        route: the threads decode every image ONCE at its own size (files count as "fallback" in decode_stats -- the device
+        JPEG decoder does not feed the tile cutter), the device cuts the tiles.  The pool is always threads (OD_DECODE_PROCS
+        is for the plain route)."""
+        from concurrent.futures import ThreadPoolExecutor
+        grid = self.slices
+        T, B = grid.T, self.batch_size
+        G = B // T
+        rank, world = dist_info(self.use_multi_gpu)
+        mine = shard_indices(len(X), rank, world)
+        batches = [mine[s:s + G] for s in range(0, len(mine), G)]
+        results = {}
+        pending = []  # (ticket, image indices)
+
+        def drain(entry):
+            ticket, idx = entry
+            p = self._pipes[ticket]
+            p.done.synchronize()
+            for i, (k, confs, bxs) in zip(idx, p.slc.detections_host(len(idx))):
+                results[i] = ObjectsPrediction(k, confs, bxs, None)  # word 0 of a merged record is the class
+
+        ahead = 2
+        nb = ahead + 2  # a staging buffer is busy from the start of its decode until its upload has completed
+        nthreads = int(os.environ.get("OD_DECODE_THREADS", "0")) or min(8, os.cpu_count() or 1)
+        pool = ThreadPoolExecutor(max_workers=max(1, nthreads))
+        if route == "device":
+            def start(bi):
+                return [pool.submit(slicing.load_native, X[i]) for i in batches[bi]]
+
+            def finish(bi, items):
+                ticket = self._submit_sliced(conf_threshold, images=[it[0] for it in items])
+                for it in items:
+                    self.decode_stats["fallback" if it[1] else "array"] += 1
+                return ticket
+        else:
+            if getattr(self, "_hbufs", None) is None:
+                self._hbufs = [[torch.zeros((B,) + tuple(self.input_size) + (3,), dtype=torch.uint8).pin_memory(), None]
+                               for _ in range(nb)]
+
+            def load_into(x, dst):  # worker thread: decode, then crop + resize every tile into pinned memory
+                return slicing.host_tiles(slicing.load_native(x)[0], grid, self.input_size, dst)
+
+            def start(bi):
+                hb = self._hbufs[bi % nb]
+                if hb[1] is not None:
+                    hb[1].synchronize()  # the upload that last read this pinned buffer
+                    hb[1] = None
+                host = hb[0].numpy()
+                return [pool.submit(load_into, X[i], host[j * T:(j + 1) * T]) for j, i in enumerate(batches[bi])]
+
+            def finish(bi, sizes):
+                hb = self._hbufs[bi % nb]
+                x = hb[0].to(self.device, non_blocking=True)
+                hb[1] = torch.cuda.Event()
+                hb[1].record(torch.cuda.current_stream(self.device))
+                return self._submit_sliced(conf_threshold, x_u8=x, sizes=sizes)
+        try:
+            futs = {bi: start(bi) for bi in range(min(ahead + 1, len(batches)))}
+            for bi, idx in enumerate(batches):
+                if bi + ahead + 1 < len(batches):
+                    futs[bi + ahead + 1] = start(bi + ahead + 1)
+                res = [f.result() for f in futs.pop(bi)]
+                if len(pending) == len(self._pipes):  # the pipeline about to be reused still holds unread results
+                    drain(pending.pop(0))
+                pending.append((finish(bi, res), idx))
+        finally:
+            pool.shutdown(wait=True)
         for entry in pending:
             drain(entry)
         results = gather_results(results, world)

@@ -32,12 +32,25 @@ def add_tta_arguments(p):
     p.add_argument("--vote-iou", default=0.5, type=float, help="box-voting overlap under --tta (<= 0: no voting)")
 
 
+def add_slice_arguments(p):
+    """--slices NY NX [--slice-overlap F] [--no-slice-full-view] of the evaluation scripts (ObjectDetector(slices=...))."""
+    p.add_argument("--slices", default=None, type=int, nargs=2, metavar=("NY", "NX"),
+                   help="sliced inference: every image is cut into NY x NX overlapping tiles (+ the whole image), each tile "
+                        "is one row of the network batch, the tiles' detections are merged on the GPU; absent = off")
+    p.add_argument("--slice-overlap", default=0.2, type=float, help="overlap of neighbouring tiles under --slices, 0 .. 0.5")
+    p.add_argument("--no-slice-full-view", action="store_true",
+                   help="under --slices: leave the whole-image tile out (objects larger than the overlap can then be lost)")
+
+
 def make_detector(tk, args, batch_size, input_size=(320, 320), device_decode=False, **kw):
     """device_decode: JPEG decode and resize of predict()'s inputs on the GPU (image_decode="device")."""
     OD = tk.dl.od.ObjectDetector
     kw["image_decode"] = "device" if device_decode else "host"
     if getattr(args, "tta", None) is not None:
         kw["tta"], kw["tta_vote_iou"] = tuple(args.tta), args.vote_iou
+    if getattr(args, "slices", None) is not None:
+        kw["slices"], kw["slice_overlap"] = tuple(args.slices), args.slice_overlap
+        kw["slice_full_view"] = not args.no_slice_full_view
     if args.synthetic:
         return OD.synthetic(batch_size, input_size, **kw)
     return OD.load_voc(batch_size=batch_size, input_size=input_size, weights=args.weights, **kw)
@@ -51,8 +64,10 @@ SHAPE_CLASSES = (1, 6, 7, 11, 14)  # bicycle, car, cat, dog, person
 SHAPE_COLOURS = ((220, 40, 40), (40, 200, 60), (50, 80, 230), (230, 210, 40), (200, 60, 210))
 
 
-def shapes_dataset(n, seed=0, size_range=(240, 400), difficult_frac=0.0, crowd_frac=0.0):
+def shapes_dataset(n, seed=0, size_range=(240, 400), difficult_frac=0.0, crowd_frac=0.0, object_scale=1.0):
     """-> (X: object array of uint8 [h,w,3] images, y: object array of ObjectsAnnotation).
+    size_range: image sides in pixels; object_scale: the objects' sides (0.15 .. 0.6 of the image) are multiplied by it --
+    large images with small objects are the test set of sliced inference.  The defaults draw what they always drew.
     difficult_frac: this share of the objects is marked `difficult` and drawn half faded into the background (VOC's hard
     objects); crowd_frac: this share of the images gets a "crowd" -- a cluster of 6-12 small shapes of one class under ONE
     loose box marked difficult, the way COCO annotates iscrowd regions.  Both are drawn from a generator of their own: the
@@ -72,7 +87,7 @@ def shapes_dataset(n, seed=0, size_range=(240, 400), difficult_frac=0.0, crowd_f
         boxes, classes = [], []
         for _obj in range(int(rng.integers(1, 4))):
             for _try in range(20):
-                bw, bh = rng.uniform(0.15, 0.6, 2)
+                bw, bh = rng.uniform(0.15, 0.6, 2) * object_scale
                 x1, y1 = rng.uniform(0.02, 0.98 - bw), rng.uniform(0.02, 0.98 - bh)
                 b = np.array([x1, y1, x1 + bw, y1 + bh])
                 if all(_iou(b, o) < 0.15 for o in boxes):

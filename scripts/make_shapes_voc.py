@@ -18,8 +18,13 @@ def _main():
                    help="mark this share of the objects <difficult>1</difficult> (drawn half faded)")
     p.add_argument("--crowd", default=0.0, type=float, metavar="FRAC",
                    help="give this share of the images a cluster of small shapes under one loose box marked difficult")
+    p.add_argument("--image-size", default=(240, 400), type=int, nargs=2, metavar=("LO", "HI"),
+                   help="image sides are drawn from LO..HI pixels")
+    p.add_argument("--object-scale", default=1.0, type=float,
+                   help="multiply the objects' sides (0.15 .. 0.6 of the image) by this: small objects in large images")
     args = p.parse_args()
-    X, y = _common.shapes_dataset(args.n, seed=args.seed, difficult_frac=args.difficult, crowd_frac=args.crowd)
+    X, y = _common.shapes_dataset(args.n, seed=args.seed, size_range=tuple(args.image_size), difficult_frac=args.difficult,
+                                  crowd_frac=args.crowd, object_scale=args.object_scale)
     base = _common.write_voc_layout(args.vocdevkit_dir, X, y, image_set=args.image_set, fmt=args.format)
     print(f"{args.n} images -> {base}")
 
