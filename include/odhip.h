@@ -297,6 +297,46 @@ int od_tta_merge(od_ctx* ctx, const od_tta_view* views, int V, int B, int NC, in
                  size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Soft-NMS (Bodla et al. 2017; BUILD-DEFINED, DESIGN.md "Soft-NMS" freezes the semantics): the suppression stage decays the
+ * scores of a kept box's neighbours instead of deleting them.  One image's n <= K <= 1024 candidates in rank order (box_j,
+ * cls_j, s_j = the f32 in the key's high word), all f32, one rounding per op, no contraction:
+ *   while kept < max_det:  i = the live j with the largest s_j (ties: the smaller rank); stop unless s_i > min_conf;
+ *     emit i with score s_i and remove it; for every live j with (strict or cls_j == cls_i) and inter(i,j) > 0, inter / uni
+ *     as od_nms computes them:   hard:     inter > thr * uni: remove j
+ *                                linear:   inter > thr * uni: s_j = s_j * (1 - inter / uni)
+ *                                gaussian: iou = inter / uni; s_j = s_j * od_exp_neg((iou * iou) / sigma)
+ *   (od_exp_neg: a fixed-order f32 exp(-x)).  Detections come out in SCORE order with the rescored confidence;
+ *   method = hard keeps exactly od_nms's indices.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct od_soft_nms_cfg {
+  int32_t method;      /* 0 hard, 1 linear, 2 gaussian */
+  int32_t strict;
+  int32_t max_det;
+  float iou_threshold;
+  float sigma;         /* > 0, gaussian */
+  float min_conf;      /* >= 1e-6 */
+} od_soft_nms_cfg;
+
+/* The counterpart of od_nms (same boxes / keys / counts, workspace = od_nms_workspace_bytes(B, K)): its sort launch, then
+ * the soft scan, one workgroup per image.
+ *   keep_flat i32 [B,max_det] in emission order, -1 padded;  keep_conf f32 [B,max_det], 0 padded;  keep_count i32 [B]
+ *   det (may be NULL) f32 [B][1 + 6*max_det] in od_gather_detections' layout, conf = the rescored one. */
+int od_soft_nms(od_ctx* ctx, const float* boxes, const uint64_t* keys, const int32_t* counts, int B, int P, int NC, int K,
+                const od_soft_nms_cfg* cfg, int32_t* keep_flat, float* keep_conf, int32_t* keep_count, float* det,
+                void* workspace, size_t workspace_bytes, void* stream);
+/* The counterpart of od_detect: od_detect_candidates' launches (either dispatch), then the soft scan on the rank-ordered
+ * candidates they leave in the NMS workspace.  Same workspaces as od_detect, left ready for the next call of either. */
+int od_detect_soft(od_ctx* ctx, const float* pred, const float* priors, int B, int P, int NC, float loc_scale, int clip,
+                   float conf_threshold, int K, const od_soft_nms_cfg* cfg, float* boxes, float* conf, uint64_t* keys,
+                   int32_t* counts, int32_t* keep_flat, float* keep_conf, int32_t* keep_count, float* det, void* workspace,
+                   size_t workspace_bytes, void* nms_workspace, size_t nms_workspace_bytes, void* stream);
+/* od_tta_merge with the soft scan in place of the greedy one: same merged order, same box voting (members weighted by their
+ * ORIGINAL confidences); the kept list, its order and the reported confidence are the soft scan's.  Same workspace. */
+int od_tta_merge_soft(od_ctx* ctx, const od_tta_view* views, int V, int B, int NC, int K, const od_soft_nms_cfg* cfg,
+                      float vote_iou, float* out, int32_t* src, int32_t* keep_count, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * K9: prior-box assignment + target encoding = od.pb.encode_truth (reference check_assign.py:21,25-27).
  *   priors f32 [P,4]; gt_boxes f32 [B,Gmax,4] corner form, normalised; gt_classes i32 [B,Gmax]; gt_counts i32 [B]
  *   y f32 [B,P,2+NC+4]: col 0 = background, col 1 = assigned ("y[:,1]==1", :25), cols 2..2+NC one-hot class (:26),
@@ -608,6 +648,11 @@ int od_slice_merge(od_ctx* ctx, const uint64_t* keys, const int32_t* counts, con
                    const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo, float edge_hi,
                    float iou_threshold, int strict, int max_det, float vote_iou, float* out, int32_t* src,
                    int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream);
+/* od_slice_merge with the soft scan (od_soft_nms_cfg above) in place of the greedy one, as od_tta_merge_soft. */
+int od_slice_merge_soft(od_ctx* ctx, const uint64_t* keys, const int32_t* counts, const float* boxes, const float* tiles,
+                        const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo, float edge_hi,
+                        const od_soft_nms_cfg* cfg, float vote_iou, float* out, int32_t* src, int32_t* keep_count,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K16: COCO bbox evaluation (tk.data.coco.evaluate; object_detector_amd/cocoeval.py states the protocol and packs the

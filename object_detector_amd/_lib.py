@@ -127,7 +127,16 @@ class TileDesc(C.Structure):
                [(n, C.c_int64) for n in ("hcoef_off", "vcoef_off", "tmp_ws")]
 
 
-STRUCTS = (TileDesc, TtaView, ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
+OD_NMS_HARD, OD_NMS_SOFT_LINEAR, OD_NMS_SOFT_GAUSSIAN = 0, 1, 2
+
+
+class SoftNmsCfg(C.Structure):
+    C_NAME = "od_soft_nms_cfg"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
+    _fields_ = [("method", C.c_int32), ("strict", C.c_int32), ("max_det", C.c_int32), ("iou_threshold", C.c_float),
+                ("sigma", C.c_float), ("min_conf", C.c_float)]
+
+
+STRUCTS = (SoftNmsCfg, TileDesc, TtaView, ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
 
 
 class OdError(RuntimeError):
@@ -184,6 +193,15 @@ _PROTOS = {
     "od_tta_merge_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "od_tta_merge": (C.c_int, [C.c_void_p, C.POINTER(TtaView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
                                C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "od_soft_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                              C.POINTER(SoftNmsCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                              C.c_void_p]),
+    "od_detect_soft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
+                                 C.c_int, C.POINTER(SoftNmsCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
+    "od_tta_merge_soft": (C.c_int, [C.c_void_p, C.POINTER(TtaView), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SoftNmsCfg),
+                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "od_assign_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "od_assign_anchors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
@@ -268,6 +286,9 @@ _PROTOS = {
     "od_slice_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "od_slice_merge_soft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(SoftNmsCfg), C.c_float,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "od_coco_match_workspace_bytes": (C.c_size_t, [C.c_longlong]),
     "od_coco_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

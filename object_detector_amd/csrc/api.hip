@@ -109,6 +109,9 @@ const std::vector<StructInfo>& od_struct_table() {
       {"od_tta_view", sizeof(od_tta_view),
        {OD_F(od_tta_view, keys), OD_F(od_tta_view, counts), OD_F(od_tta_view, boxes), OD_F(od_tta_view, P),
         OD_F(od_tta_view, flip)}},
+      {"od_soft_nms_cfg", sizeof(od_soft_nms_cfg),
+       {OD_F(od_soft_nms_cfg, method), OD_F(od_soft_nms_cfg, strict), OD_F(od_soft_nms_cfg, max_det),
+        OD_F(od_soft_nms_cfg, iou_threshold), OD_F(od_soft_nms_cfg, sigma), OD_F(od_soft_nms_cfg, min_conf)}},
       {"od_mosaic_params", sizeof(od_mosaic_params),
        {OD_F(od_mosaic_params, split_x), OD_F(od_mosaic_params, split_y), OD_F(od_mosaic_params, tile),
         OD_F(od_mosaic_params, n_erase), OD_F(od_mosaic_params, pad_), OD_F(od_mosaic_params, erase),

@@ -82,6 +82,21 @@ void od_nms_sorted_buffers(void* nms_workspace, int B, int K, unsigned long long
   *KP = kp;
 }
 
+float* od_nms_scratch(void* nms_workspace, int B, int K) {
+  return (float*)((char*)nms_workspace + nms_layout(B, next_pow2(K)).mask);
+}
+
+int od_nms_sort_launch(void* nms_workspace, const float* boxes, const unsigned long long* keys, const int32_t* counts, int B, int P,
+                       int NC, int K, hipStream_t s) {
+  const int KP = next_pow2(K);
+  const NmsLayout l = nms_layout(B, KP);
+  char* ws = (char*)nms_workspace;
+  hipLaunchKernelGGL(od_nms_sort, dim3(B), dim3(1024), 0, s, boxes, (const u64*)keys, counts, P, NC, K, KP, (u64*)(ws + l.skeys),
+                     (f32x4*)(ws + l.sbox), (int*)(ws + l.scls));
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
 int od_nms_greedy_launch(void* nms_workspace, const int32_t* counts, int B, int K, float iou_threshold, int strict, int max_det,
                          int32_t* keep_flat, int32_t* keep_count, hipStream_t s) {
   const int KP = next_pow2(K);
@@ -111,13 +126,7 @@ extern "C" int od_nms(od_ctx* ctx, const float* boxes, const uint64_t* keys, con
     od_set_error("od_nms: workspace %zu < %zu bytes", workspace_bytes, l.total);
     return OD_ERR_WORKSPACE;
   }
-  char* ws = (char*)workspace;
-  u64* skeys = (u64*)(ws + l.skeys);
-  f32x4* sbox = (f32x4*)(ws + l.sbox);
-  int* scls = (int*)(ws + l.scls);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(od_nms_sort, dim3(B), dim3(1024), 0, s, boxes, (const u64*)keys, counts, P, NC, K, KP, skeys, sbox,
-                     scls);
-  OD_CHECK_LAUNCH();
+  if (int rc = od_nms_sort_launch(workspace, boxes, (const unsigned long long*)keys, counts, B, P, NC, K, s)) return rc;
   return od_nms_greedy_launch(workspace, counts, B, K, iou_threshold, strict, max_det, keep_flat, keep_count, s);
 }

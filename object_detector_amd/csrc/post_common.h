@@ -240,5 +240,18 @@ struct OdMergeWs {
 };
 size_t od_merge_workspace_bytes(int B, int K);
 OdMergeWs od_merge_workspace(void* workspace, int B, int K);
+// soft non-null: the soft scan (cfg->iou_threshold / strict / max_det in place of the three scalars) and its rescored confidences
 int od_merge_nms_vote_launch(const OdMergeWs& w, int B, int NC, int K, float iou_threshold, int strict, int max_det,
-                             float vote_iou, float* out, int32_t* src, int32_t* keep_count, hipStream_t s);
+                             float vote_iou, float* out, int32_t* src, int32_t* keep_count, hipStream_t s,
+                             const od_soft_nms_cfg* soft = nullptr);
+// nms.hip: od_nms's sort launch (keys -> the rank-ordered keys / boxes / classes of the workspace)
+int od_nms_sort_launch(void* nms_workspace, const float* boxes, const unsigned long long* keys, const int32_t* counts, int B, int P,
+                       int NC, int K, hipStream_t s);
+// nms.hip: the part of the NMS workspace behind the rank-ordered buffers, >= B * KP * 8 bytes that no scan reads or writes:
+// where the soft merges keep the kept rows' rescored confidences between the scan and the vote-and-gather kernel
+float* od_nms_scratch(void* nms_workspace, int B, int K);
+// soft_nms.hip: the argument checks every soft entry shares (OD_OK or OD_ERR_*, error text set), and the soft scan's launch on
+// the rank-ordered buffers of the NMS workspace (det may be null)
+int od_soft_cfg_check(const char* who, const od_soft_nms_cfg* cfg, int K);
+int od_soft_scan_launch(void* nms_workspace, const int32_t* counts, int B, int K, const od_soft_nms_cfg& cfg, int32_t* keep_flat,
+                        float* keep_conf, int32_t* keep_count, float* det, hipStream_t s);

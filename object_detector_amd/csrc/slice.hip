@@ -15,7 +15,8 @@
 //         prefix over the 16 waves), so the lists stay sorted and a survivor's merged rank (conf bits desc, tile asc, flat
 //         asc) is its compacted position plus a binary-searched count per other list -- a dropped entry is in no list and
 //         cannot disturb a rank.  The first Km = min(K, survivors) are written as od_nms_sort leaves a table behind.
-//   od_nms_greedy_k, then od_tta_vote_gather (tta.hip), unchanged, through od_merge_nms_vote_launch.
+//   od_nms_greedy_k, then od_tta_vote_gather (tta.hip), unchanged, through od_merge_nms_vote_launch
+//   (od_slice_merge_soft: the soft scan of soft_nms.hip in place of od_nms_greedy_k).
 // Compiled with -ffp-contract=off: the map to image coordinates is one rounding per op, as numpy's.
 #include "post_common.h"
 #include "resample_common.h"
@@ -270,18 +271,19 @@ extern "C" size_t od_slice_merge_workspace_bytes(int G, int T, int K) {
   return od_merge_workspace_bytes(G, K);  // the merged table holds K candidates however many tiles feed it
 }
 
-extern "C" int od_slice_merge(od_ctx* ctx, const uint64_t* keys, const int32_t* counts, const float* boxes, const float* tiles,
-                              const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo, float edge_hi,
-                              float iou_threshold, int strict, int max_det, float vote_iou, float* out, int32_t* src,
-                              int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream) {
-  OD_REQUIRE(ctx && keys && counts && boxes && tiles && edges && out && keep_count && workspace, "od_slice_merge: null argument");
-  OD_REQUIRE(T >= 1 && T <= SL_MAX_T, "od_slice_merge: T = %d outside 1..%d", T, SL_MAX_T);
-  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "od_slice_merge: NC = %d outside the supported class counts 1..%d", NC, OD_MAX_NC);
-  OD_REQUIRE(G > 0 && G <= 65535 && K > 0 && K <= SL_MAX_K && max_det > 0, "od_slice_merge: bad dims (K <= 1024)");
-  OD_REQUIRE(P > 0 && (long long)P * NC < (1LL << 31), "od_slice_merge: P * NC must fit 31 bits");
+// od_slice_merge (soft null) and od_slice_merge_soft: the rank kernel, then the greedy or the soft scan, then vote-and-gather
+static int slice_merge(const char* who, od_ctx* ctx, const uint64_t* keys, const int32_t* counts, const float* boxes,
+                       const float* tiles, const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo, float edge_hi,
+                       float iou_threshold, int strict, int max_det, const od_soft_nms_cfg* soft, float vote_iou, float* out,
+                       int32_t* src, int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream) {
+  OD_REQUIRE(ctx && keys && counts && boxes && tiles && edges && out && keep_count && workspace, "%s: null argument", who);
+  OD_REQUIRE(T >= 1 && T <= SL_MAX_T, "%s: T = %d outside 1..%d", who, T, SL_MAX_T);
+  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "%s: NC = %d outside the supported class counts 1..%d", who, NC, OD_MAX_NC);
+  OD_REQUIRE(G > 0 && G <= 65535 && K > 0 && K <= SL_MAX_K && max_det > 0, "%s: bad dims (K <= 1024)", who);
+  OD_REQUIRE(P > 0 && (long long)P * NC < (1LL << 31), "%s: P * NC must fit 31 bits", who);
   const size_t need = od_merge_workspace_bytes(G, K);
   if (workspace_bytes < need) {
-    od_set_error("od_slice_merge: workspace %zu < %zu bytes", workspace_bytes, need);
+    od_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
     return OD_ERR_WORKSPACE;
   }
   const OdMergeWs w = od_merge_workspace(workspace, G, K);
@@ -294,5 +296,23 @@ extern "C" int od_slice_merge(od_ctx* ctx, const uint64_t* keys, const int32_t* 
   hipLaunchKernelGGL(od_slice_rank, dim3(G), dim3(1024), 0, s, (const u64*)keys, counts, boxes, tiles, edges, T, P, NC, K, KP,
                      edge_lo, edge_hi, skeys, sbox, scls, w.msrc, w.mcount);
   OD_CHECK_LAUNCH();
-  return od_merge_nms_vote_launch(w, G, NC, K, iou_threshold, strict, max_det, vote_iou, out, src, keep_count, s);
+  return od_merge_nms_vote_launch(w, G, NC, K, iou_threshold, strict, max_det, vote_iou, out, src, keep_count, s, soft);
+}
+
+extern "C" int od_slice_merge(od_ctx* ctx, const uint64_t* keys, const int32_t* counts, const float* boxes, const float* tiles,
+                              const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo, float edge_hi,
+                              float iou_threshold, int strict, int max_det, float vote_iou, float* out, int32_t* src,
+                              int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream) {
+  return slice_merge("od_slice_merge", ctx, keys, counts, boxes, tiles, edges, G, T, P, NC, K, edge_lo, edge_hi, iou_threshold,
+                     strict, max_det, nullptr, vote_iou, out, src, keep_count, workspace, workspace_bytes, stream);
+}
+
+extern "C" int od_slice_merge_soft(od_ctx* ctx, const uint64_t* keys, const int32_t* counts, const float* boxes,
+                                   const float* tiles, const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo,
+                                   float edge_hi, const od_soft_nms_cfg* cfg, float vote_iou, float* out, int32_t* src,
+                                   int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = od_soft_cfg_check("od_slice_merge_soft", cfg, K)) return rc;
+  return slice_merge("od_slice_merge_soft", ctx, keys, counts, boxes, tiles, edges, G, T, P, NC, K, edge_lo, edge_hi,
+                     cfg->iou_threshold, cfg->strict, cfg->max_det, cfg, vote_iou, out, src, keep_count, workspace,
+                     workspace_bytes, stream);
 }

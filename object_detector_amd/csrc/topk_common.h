@@ -263,3 +263,159 @@ __device__ __forceinline__ void od_nms_greedy(const f32x4* lb, const int* lc, co
   for (int i = total + tid; i < max_det; i += 1024) keep_flat[i] = -1;
   if (tid == 0) *keep_count = total;
 }
+
+// ---- Soft-NMS (DESIGN.md "Soft-NMS") ---------------------------------------------------------------------------------------
+// exp(-x) for x >= 0 in a fixed f32 op order (Cephes' expf reduction and polynomial, every mul and add rounded on its own:
+// the TU is -ffp-contract=off), so that tests/soft_nms_ref.py's numpy restatement has the same bits.  expf / __expf do not.
+__device__ __forceinline__ float od_exp_neg(float x) {
+  if (x > 80.f) return 0.f;
+  const float n = rintf(1.44269504f * x);
+  const float r = (x - n * 0.693359375f) - n * (-2.12194440e-4f);
+  const float y = -r;
+  float p = 1.9875691500e-4f;
+  p = p * y + 1.3981999507e-3f;
+  p = p * y + 8.3334519073e-3f;
+  p = p * y + 4.1665795894e-2f;
+  p = p * y + 1.6666665459e-1f;
+  p = p * y + 5.0000001201e-1f;
+  const float e = ((p * (y * y)) + y) + 1.f;
+  return e * __uint_as_float((unsigned)(127 - (int)n) << 23);
+}
+
+// The score of live column c (class cc) after row a (class ca, area_a) has been emitted; 0 = no longer a candidate (removed,
+// or not > min_conf any more).  inter / uni are od_iou_exceeds' (same ops, same order).
+__device__ __forceinline__ float od_soft_rescore(const f32x4 a, float area_a, int ca, const f32x4 c, int cc, float s,
+                                                 const od_soft_nms_cfg& cfg) {
+  if (!(cfg.strict || cc == ca)) return s;
+  const float ix1 = fmaxf(a[0], c[0]), iy1 = fmaxf(a[1], c[1]);
+  const float ix2 = fminf(a[2], c[2]), iy2 = fminf(a[3], c[3]);
+  const float iw = fmaxf(ix2 - ix1, 0.f), ih = fmaxf(iy2 - iy1, 0.f);
+  const float inter = iw * ih;
+  if (!(inter > 0.f)) return s;
+  const float area_c = (c[2] - c[0]) * (c[3] - c[1]);
+  const float uni = (area_a + area_c) - inter;
+  if (cfg.method == 2) {
+    const float iou = inter / uni;
+    s = s * od_exp_neg((iou * iou) / cfg.sigma);
+  } else if (inter > cfg.iou_threshold * uni) {
+    s = cfg.method == 1 ? s * (1.f - inter / uni) : 0.f;
+  }
+  return s > cfg.min_conf ? s : 0.f;
+}
+
+// max of a 64-bit key over the wave, valid in LANE 63: six DPP steps in registers (row_shr 1 / 2 / 4 / 8 inside the rows of 16
+// lanes, then row_bcast 15 and 31 across them), no LDS traffic -- the shuffle form (ds_bpermute) measured 1.5x slower per
+// round.  A lane the step does not reach keeps its own value (old = v), which max() absorbs.
+template <int CTRL>
+__device__ __forceinline__ u64 od_dpp_max64(u64 v) {
+  const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+  const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xf, 0xf, false);
+  const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xf, 0xf, false);
+  const u64 o = ((u64)ohi << 32) | olo;
+  return o > v ? o : v;
+}
+__device__ __forceinline__ u64 od_wave_max64_lane63(u64 v) {
+  v = od_dpp_max64<0x111>(v);  // row_shr:1
+  v = od_dpp_max64<0x112>(v);  // row_shr:2
+  v = od_dpp_max64<0x114>(v);  // row_shr:4
+  v = od_dpp_max64<0x118>(v);  // row_shr:8 -> lane 15 of every row holds the row's max
+  v = od_dpp_max64<0x142>(v);  // row_bcast:15 -> lanes 31 / 63 hold the max of their half
+  v = od_dpp_max64<0x143>(v);  // row_bcast:31 -> lane 63 holds the wave's
+  return v;
+}
+
+// Soft-NMS of one image's n <= NT * CPL candidates in rank order by one workgroup of NT threads (a power of two >= 64), CPL
+// candidates per thread in registers (candidate j = tid + q * NT): box, class and the running score (0 = not live).  A round
+// emits the live candidate with the largest (score bits, inverted rank) key -- the wave's max by DPP steps, the workgroup's
+// through one LDS slot per wave, double-buffered so that a round costs ONE barrier (none for NT = 64) -- and rescores the
+// live candidates against it (od_soft_rescore).  The emitted ranks / scores are collected in LDS and written at the end:
+// keep_flat [max_det] (flat index of the key, -1 padded), keep_conf [max_det] (0 padded), *keep_count, and when det is
+// non-null the image's record block [1 + 6 * max_det] in od_gather_detections' layout with the rescored confidence.
+// lb / lc / skeys [n]: the candidates' boxes / classes / keys in LDS, published by the caller's barrier.  No atomics, no
+// dependence on scheduling: every thread computes the same winner from the same 64-bit keys.
+template <int NT, int CPL>
+__device__ __forceinline__ void od_soft_nms_scan(const f32x4* lb, const int* lc, const u64* skeys, int n,
+                                                 const od_soft_nms_cfg cfg, int* __restrict__ keep_flat,
+                                                 float* __restrict__ keep_conf, int* __restrict__ keep_count,
+                                                 float* __restrict__ det) {
+  constexpr int NW = NT / 64;
+  __shared__ int e_rank[NT * CPL];    // emitted ranks, in emission order
+  __shared__ float e_conf[NT * CPL];  // and their scores at emission
+  __shared__ u64 part[2][NW];
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
+  f32x4 box[CPL];
+  int cls[CPL];
+  float sc[CPL];
+#pragma unroll
+  for (int q = 0; q < CPL; ++q) {
+    const int j = tid + q * NT;
+    const bool ok = j < n;
+    box[q] = ok ? lb[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+    cls[q] = ok ? lc[j] : -1;
+    const float s = ok ? __uint_as_float(od_key_score_bits(skeys[j])) : 0.f;
+    sc[q] = s > cfg.min_conf ? s : 0.f;
+  }
+  const int limit = min(cfg.max_det, n);
+  int kept = 0;
+  while (kept < limit) {
+    u64 best = 0ull;
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) {
+      const u64 k = sc[q] > 0.f ? od_make_key(__float_as_uint(sc[q]), (unsigned)(tid + q * NT)) : 0ull;
+      best = k > best ? k : best;
+    }
+    best = od_wave_max64_lane63(best);
+    if (NW > 1) {
+      u64* pp = part[kept & 1];
+      if (lane == 63) pp[wv] = best;
+      __syncthreads();
+      best = pp[0];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) {
+        const u64 o = pp[w];
+        best = o > best ? o : best;
+      }
+    } else {
+      best = od_readlane64(best, 63);
+    }
+    if (!best) break;  // workgroup-uniform
+    const int i = (int)od_key_flat(best);
+    const float si = __uint_as_float(od_key_score_bits(best));
+    if (tid == 0) {
+      e_rank[kept] = i;
+      e_conf[kept] = si;
+    }
+    ++kept;
+    const f32x4 a = lb[i];
+    const int ca = lc[i];
+    const float area_a = (a[2] - a[0]) * (a[3] - a[1]);
+#pragma unroll
+    for (int q = 0; q < CPL; ++q) {
+      if (tid + q * NT == i) sc[q] = 0.f;
+      else if (sc[q] > 0.f) sc[q] = od_soft_rescore(a, area_a, ca, box[q], cls[q], sc[q], cfg);
+    }
+  }
+  __syncthreads();  // e_rank / e_conf
+  for (int r = tid; r < cfg.max_det; r += NT) {
+    const bool ok = r < kept;
+    const int i = ok ? e_rank[r] : 0;
+    const int flat = ok ? (int)od_key_flat(skeys[i]) : -1;
+    const float conf = ok ? e_conf[r] : 0.f;
+    keep_flat[r] = flat;
+    keep_conf[r] = conf;
+    if (det) {
+      float* rec = det + 1 + 6 * (size_t)r;
+      const f32x4 bx = ok ? lb[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+      rec[0] = __int_as_float(flat);
+      rec[1] = conf;
+      rec[2] = bx[0];
+      rec[3] = bx[1];
+      rec[4] = bx[2];
+      rec[5] = bx[3];
+    }
+  }
+  if (tid == 0) {
+    *keep_count = kept;
+    if (det) det[0] = __int_as_float(kept);
+  }
+}

@@ -12,6 +12,8 @@
 //   vote   (od_tta_vote_gather)  one workgroup per image, the merged table in LDS: the waves ballot every kept candidate's
 //          member set, then one thread per kept candidate accumulates conf_j and conf_j * box_j over its members in ascending
 //          rank; writes the record block, the (view, flat) sources and the padding
+// od_tta_merge_soft is the same three launches with the soft scan (od_soft_scan_k, soft_nms.hip) in the middle: the vote kernel
+// then reports the scan's rescored confidence for every kept row (its votes still weigh the original confidences).
 // Nothing in the workspace carries over from call to call (every word that is read was written by this call).
 // Compiled with -ffp-contract=off: the mirror, the IoU predicate and the voting sums are one rounding per op, as numpy's.
 #include "post_common.h"
@@ -140,13 +142,16 @@ __global__ __launch_bounds__(1024) void od_tta_merge_rank(TtaViews vw, int NC, i
 // waves share the round's kept detections; a wave tests 64 merged candidates per step against its detection and ballots the
 // membership word, so the 1024 predicates of a detection are 16 steps instead of a serial loop.  Phase 2: one kept detection
 // per thread walks ONLY its members, in ascending rank (the order that fixes the rounding), and writes record, source, padding.
+// keep_conf (optional) [B, keep_stride]: the confidence to report for every kept row instead of its key's (the soft scan's
+// rescored one); the votes are weighted by the keys' confidences either way.
 constexpr int TTA_ROUND = 256;
 constexpr int TTA_MW = TTA_MAX_K / 64 + 1;  // mask row pitch in words: 17 spreads a column of rows over the LDS banks
 
 __global__ __launch_bounds__(1024) void od_tta_vote_gather(const u64* __restrict__ skeys, const f32x4* __restrict__ sbox,
                                                            const int* __restrict__ scls, const int* __restrict__ msrc,
                                                            const int* __restrict__ mcount, const int* __restrict__ keepf,
-                                                           const int* __restrict__ keep_count, int NC, int KP, int keep_stride,
+                                                           const int* __restrict__ keep_count,
+                                                           const float* __restrict__ keep_conf, int NC, int KP, int keep_stride,
                                                            int max_det, float vote_iou, float* __restrict__ out,
                                                            int* __restrict__ src) {
   __shared__ f32x4 lb[TTA_MAX_K];
@@ -210,7 +215,7 @@ __global__ __launch_bounds__(1024) void od_tta_vote_gather(const u64* __restrict
           bx = f32x4{s0 / sw, s1 / sw, s2 / sw, s3 / sw};
         }
         rec[0] = __int_as_float(lc[i]);
-        rec[1] = lw[i];
+        rec[1] = keep_conf ? keep_conf[(long long)b * keep_stride + r] : lw[i];  // the soft scan's rescored confidence
         rec[2] = bx[0];
         rec[3] = bx[1];
         rec[4] = bx[2];
@@ -266,16 +271,26 @@ OdMergeWs od_merge_workspace(void* workspace, int B, int K) {
 }
 
 int od_merge_nms_vote_launch(const OdMergeWs& w, int B, int NC, int K, float iou_threshold, int strict, int max_det,
-                             float vote_iou, float* out, int32_t* src, int32_t* keep_count, hipStream_t s) {
+                             float vote_iou, float* out, int32_t* src, int32_t* keep_count, hipStream_t s,
+                             const od_soft_nms_cfg* soft) {
   u64* skeys;
   f32x4* sbox;
   int* scls;
   int KP;
   od_nms_sorted_buffers(w.nms, B, K, &skeys, &sbox, &scls, &KP);
   const int md = max_det < K ? max_det : K;  // at most Km <= K are ever kept: the scan's list needs no more slots
-  if (int rc = od_nms_greedy_launch(w.nms, w.mcount, B, K, iou_threshold, strict, md, w.keepf, keep_count, s)) return rc;
-  hipLaunchKernelGGL(od_tta_vote_gather, dim3(B), dim3(1024), 0, s, skeys, sbox, scls, w.msrc, w.mcount, w.keepf, keep_count, NC,
-                     KP, md, max_det, vote_iou, out, src);
+  const float* keep_conf = nullptr;
+  if (soft) {
+    od_soft_nms_cfg cfg = *soft;
+    cfg.max_det = md;
+    float* kc = od_nms_scratch(w.nms, B, K);  // [B, md]
+    if (int rc = od_soft_scan_launch(w.nms, w.mcount, B, K, cfg, w.keepf, kc, keep_count, nullptr, s)) return rc;
+    keep_conf = kc;
+  } else if (int rc = od_nms_greedy_launch(w.nms, w.mcount, B, K, iou_threshold, strict, md, w.keepf, keep_count, s)) {
+    return rc;
+  }
+  hipLaunchKernelGGL(od_tta_vote_gather, dim3(B), dim3(1024), 0, s, skeys, sbox, scls, w.msrc, w.mcount, w.keepf, keep_count,
+                     keep_conf, NC, KP, md, max_det, vote_iou, out, src);
   OD_CHECK_LAUNCH();
   return OD_OK;
 }
@@ -304,18 +319,19 @@ extern "C" size_t od_tta_merge_workspace_bytes(int B, int V, int K) {
   return od_merge_workspace_bytes(B, K);  // the merged table holds K candidates however many views feed it
 }
 
-extern "C" int od_tta_merge(od_ctx* ctx, const od_tta_view* views, int V, int B, int NC, int K, float iou_threshold,
-                            int strict, int max_det, float vote_iou, float* out, int32_t* src, int32_t* keep_count,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-  OD_REQUIRE(ctx && views && out && keep_count && workspace, "od_tta_merge: null argument");
-  OD_REQUIRE(V >= 1 && V <= TTA_MAX_VIEWS, "od_tta_merge: V = %d outside 1..%d", V, TTA_MAX_VIEWS);
-  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "od_tta_merge: NC = %d outside the supported class counts 1..%d", NC, OD_MAX_NC);
-  OD_REQUIRE(B > 0 && B <= 65535 && K > 0 && K <= TTA_MAX_K && max_det > 0, "od_tta_merge: bad dims (K <= 1024)");
+// od_tta_merge (soft null) and od_tta_merge_soft: the rank kernel, then the greedy or the soft scan, then vote-and-gather
+static int tta_merge(const char* who, od_ctx* ctx, const od_tta_view* views, int V, int B, int NC, int K, float iou_threshold,
+                     int strict, int max_det, const od_soft_nms_cfg* soft, float vote_iou, float* out, int32_t* src,
+                     int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream) {
+  OD_REQUIRE(ctx && views && out && keep_count && workspace, "%s: null argument", who);
+  OD_REQUIRE(V >= 1 && V <= TTA_MAX_VIEWS, "%s: V = %d outside 1..%d", who, V, TTA_MAX_VIEWS);
+  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "%s: NC = %d outside the supported class counts 1..%d", who, NC, OD_MAX_NC);
+  OD_REQUIRE(B > 0 && B <= 65535 && K > 0 && K <= TTA_MAX_K && max_det > 0, "%s: bad dims (K <= 1024)", who);
   TtaViews vw = {};
   vw.V = V;
   for (int v = 0; v < V; ++v) {
-    OD_REQUIRE(views[v].keys && views[v].counts && views[v].boxes, "od_tta_merge: view %d has a null pointer", v);
-    OD_REQUIRE(views[v].P > 0 && (long long)views[v].P * NC < (1LL << 31), "od_tta_merge: view %d: P * NC must fit 31 bits", v);
+    OD_REQUIRE(views[v].keys && views[v].counts && views[v].boxes, "%s: view %d has a null pointer", who, v);
+    OD_REQUIRE(views[v].P > 0 && (long long)views[v].P * NC < (1LL << 31), "%s: view %d: P * NC must fit 31 bits", who, v);
     vw.keys[v] = (const u64*)views[v].keys;
     vw.counts[v] = views[v].counts;
     vw.boxes[v] = views[v].boxes;
@@ -324,7 +340,7 @@ extern "C" int od_tta_merge(od_ctx* ctx, const od_tta_view* views, int V, int B,
   }
   const size_t need = od_merge_workspace_bytes(B, K);
   if (workspace_bytes < need) {
-    od_set_error("od_tta_merge: workspace %zu < %zu bytes", workspace_bytes, need);
+    od_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
     return OD_ERR_WORKSPACE;
   }
   const OdMergeWs w = od_merge_workspace(workspace, B, K);
@@ -336,5 +352,20 @@ extern "C" int od_tta_merge(od_ctx* ctx, const od_tta_view* views, int V, int B,
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(od_tta_merge_rank, dim3(B), dim3(1024), 0, s, vw, NC, K, KP, skeys, sbox, scls, w.msrc, w.mcount);
   OD_CHECK_LAUNCH();
-  return od_merge_nms_vote_launch(w, B, NC, K, iou_threshold, strict, max_det, vote_iou, out, src, keep_count, s);
+  return od_merge_nms_vote_launch(w, B, NC, K, iou_threshold, strict, max_det, vote_iou, out, src, keep_count, s, soft);
+}
+
+extern "C" int od_tta_merge(od_ctx* ctx, const od_tta_view* views, int V, int B, int NC, int K, float iou_threshold,
+                            int strict, int max_det, float vote_iou, float* out, int32_t* src, int32_t* keep_count,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+  return tta_merge("od_tta_merge", ctx, views, V, B, NC, K, iou_threshold, strict, max_det, nullptr, vote_iou, out, src,
+                   keep_count, workspace, workspace_bytes, stream);
+}
+
+extern "C" int od_tta_merge_soft(od_ctx* ctx, const od_tta_view* views, int V, int B, int NC, int K, const od_soft_nms_cfg* cfg,
+                                 float vote_iou, float* out, int32_t* src, int32_t* keep_count, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  if (int rc = od_soft_cfg_check("od_tta_merge_soft", cfg, K)) return rc;
+  return tta_merge("od_tta_merge_soft", ctx, views, V, B, NC, K, cfg->iou_threshold, cfg->strict, cfg->max_det, cfg, vote_iou,
+                   out, src, keep_count, workspace, workspace_bytes, stream);
 }

@@ -20,7 +20,7 @@ from . import slicing
 from . import weights as W
 from .net import Net
 from .pb import ObjectsAnnotation, PriorBoxes
-from .postprocess import Postprocessor
+from .postprocess import SOFT_SIGMA, Postprocessor, check_nms_args
 from .tta import VOTE_IOU, TtaPostprocessor, normalize_views
 
 DEFAULT_CONF_THRESHOLD = 0.01  # [BUILD-DEFINED]: mAP needs the low-confidence tail (voc_evaluate.py:27 passes 0.6)
@@ -151,7 +151,11 @@ class ObjectDetector:
     def __init__(self, params, batch_size=16, input_size=(320, 320), keep_aspect=False, strict_nms=False,
                  use_multi_gpu=True, device=None, prior_wh=None, n_inflight=None, precision=None, image_decode="host",
                  tta=None, tta_vote_iou=VOTE_IOU, slices=None, slice_overlap=0.2, slice_full_view=True, slice_edge=0.01,
-                 slice_vote_iou=VOTE_IOU):
+                 slice_vote_iou=VOTE_IOU, nms="hard", soft_sigma=SOFT_SIGMA, soft_min_conf=None):
+        # the suppression stage: "hard" (greedy NMS, the default path, unchanged), "soft-linear" or "soft-gaussian" (Soft-NMS:
+        # neighbours' scores decay instead of being deleted; soft_min_conf=None = the call's conf_threshold).  On every
+        # route: plain, tta, slices.  Checked before anything touches the GPU.
+        self.nms, self.soft_sigma, self.soft_min_conf = check_nms_args(nms, soft_sigma, soft_min_conf)
         # test-time augmentation: None = off (the plain path, unchanged); () = the identity view alone (box voting only);
         # ("flip",) = identity + horizontal mirror, merged on the device (tta.py).  Checked before anything touches the GPU.
         self.tta = normalize_views(tta)
@@ -188,7 +192,7 @@ class ObjectDetector:
         self.precision = self.net.precision
         assert self.net.P == len(self.pb)
         self.post = Postprocessor(self.batch_size, self.net.P, self.num_classes, self.pb.pb_locs, device=self.device,
-                                  strict_nms=self.strict_nms, loc_scale=self.pb.loc_scale)
+                                  strict_nms=self.strict_nms, loc_scale=self.pb.loc_scale, **self._nms_kw())
         # Batches in flight (submit / collect): every pipeline has its own buffers and stream, so the launch ramps, tile
         # tails, epilogue write bursts and the small post-processing kernels of one batch overlap the convolutions of the
         # next (measured +23 % images/s at batch 32 with 2-3 in flight, profiles/r01/inflight_sweep.txt).  Pipeline 0 =
@@ -200,11 +204,14 @@ class ObjectDetector:
                       share_weights_with=self.net, precision=self.precision, stream_stages=self.net.stream_stages,
                       split=self.net.split, wide_fpn=self.net.wide_fpn)
             post = Postprocessor(self.batch_size, net.P, self.num_classes, self.pb.pb_locs, device=self.device,
-                                 strict_nms=self.strict_nms, loc_scale=self.pb.loc_scale)
+                                 strict_nms=self.strict_nms, loc_scale=self.pb.loc_scale, **self._nms_kw())
             self._pipes.append(_Pipeline(net, post, torch.cuda.Stream(device=self.device), self._make_tta(post),
                                          self._make_slc(net, post)))
         self._next = 0
         self._calibrated = len(self._pipes) < 2 or os.environ.get("OD_INFLIGHT_CALIBRATE", "1") == "0"
+
+    def _nms_kw(self):
+        return {"nms": self.nms, "soft_sigma": self.soft_sigma, "soft_min_conf": self.soft_min_conf}
 
     def _make_tta(self, post):
         if self.tta is None:

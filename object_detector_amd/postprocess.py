@@ -18,11 +18,36 @@ PRE_NMS_TOPK = 1024
 MAX_DETECTIONS = 200
 LOC_SCALE = 0.1
 MAX_CLASSES = 1024  # od_detect / od_head_postprocess / od_loss_fwd_bwd: 1 <= NC <= 1024
+# the suppression stage: greedy NMS, or Soft-NMS with linear / Gaussian score decay (DESIGN.md "Soft-NMS")
+NMS_METHODS = {"hard": _lib.OD_NMS_HARD, "soft-linear": _lib.OD_NMS_SOFT_LINEAR, "soft-gaussian": _lib.OD_NMS_SOFT_GAUSSIAN}
+SOFT_SIGMA = 0.5
+SOFT_MIN_CONF_FLOOR = 1e-6  # od_soft_nms_cfg.min_conf >= 1e-6
+
+
+def check_nms_args(nms="hard", soft_sigma=SOFT_SIGMA, soft_min_conf=None):
+    """The `nms=` / `soft_sigma=` / `soft_min_conf=` arguments of Postprocessor and ObjectDetector -> (nms, sigma, min_conf
+    or None), or ValueError.  Touches no device."""
+    if nms not in NMS_METHODS:
+        raise ValueError(f"nms must be one of {tuple(NMS_METHODS)}, got {nms!r}")
+    sigma = float(soft_sigma)
+    if not sigma > 0:
+        raise ValueError(f"soft_sigma must be > 0, got {soft_sigma!r}")
+    if soft_min_conf is not None:
+        soft_min_conf = float(soft_min_conf)
+        if not soft_min_conf >= SOFT_MIN_CONF_FLOOR:
+            raise ValueError(f"soft_min_conf must be >= {SOFT_MIN_CONF_FLOOR}, got {soft_min_conf!r}")
+    return nms, sigma, soft_min_conf
 
 
 class Postprocessor:
     def __init__(self, batch_size, num_priors, num_classes, priors, device="cuda:0", topk=PRE_NMS_TOPK,
-                 max_det=MAX_DETECTIONS, iou_threshold=IOU_THRESHOLD, strict_nms=False, loc_scale=LOC_SCALE):
+                 max_det=MAX_DETECTIONS, iou_threshold=IOU_THRESHOLD, strict_nms=False, loc_scale=LOC_SCALE, nms="hard",
+                 soft_sigma=SOFT_SIGMA, soft_min_conf=None):
+        # nms="hard" (default): the greedy scan, exactly the calls below.  "soft-linear" / "soft-gaussian": the soft scan
+        # (od_detect_soft / od_soft_nms / the _soft merges); soft_min_conf=None means the call's conf_threshold.
+        self.nms_method, self.soft_sigma, self.soft_min_conf = check_nms_args(nms, soft_sigma, soft_min_conf)
+        self.soft = self.nms_method != "hard"
+        self._conf_threshold = None  # of the last run() / candidates call: the soft scan's min_conf when none is given
         self.ctx = Context.get(device)
         self.lib = self.ctx.lib
         dev = torch.device(device)
@@ -45,6 +70,7 @@ class Postprocessor:
         self.counts = torch.empty((B,), dtype=torch.int32, device=dev)
         self.keep_flat = torch.empty((B, self.max_det), dtype=torch.int32, device=dev)
         self.keep_count = torch.empty((B,), dtype=torch.int32, device=dev)
+        self.keep_conf = torch.empty((B, self.max_det), dtype=torch.float32, device=dev) if self.soft else None
         self.ws_topk_bytes = self.lib.od_topk_workspace_bytes(B, P * NC, K)
         self.ws_nms_bytes = self.lib.od_nms_workspace_bytes(B, K)
         # kept detections of the batch as one record block + its pinned host mirror: ONE device->host copy per batch
@@ -88,12 +114,31 @@ class Postprocessor:
 
     def topk(self, conf: torch.Tensor, conf_threshold: float):
         assert conf.dtype == torch.float32 and conf.is_contiguous()
+        self._conf_threshold = float(conf_threshold)
         _lib.check(self.lib.od_topk_scores(self.ctx.handle, conf.data_ptr(), self.B, self.P * self.NC, self.K,
                                            float(conf_threshold), self.keys.data_ptr(), self.counts.data_ptr(),
                                            self.ws_topk.data_ptr(), self.ws_topk_bytes, _stream_ptr()), "od_topk_scores")
         return self.keys, self.counts
 
+    def soft_cfg(self, conf_threshold=None):
+        """The od_soft_nms_cfg of this post-processor; min_conf = soft_min_conf, or the given / last conf_threshold."""
+        if conf_threshold is None:
+            conf_threshold = self._conf_threshold
+        mc = self.soft_min_conf
+        if mc is None:
+            if conf_threshold is None:
+                raise _lib.OdError("Postprocessor.soft_cfg: no conf_threshold yet and no soft_min_conf")
+            mc = max(float(conf_threshold), SOFT_MIN_CONF_FLOOR)
+        return _lib.SoftNmsCfg(NMS_METHODS[self.nms_method], self.strict, self.max_det, self.iou_threshold, self.soft_sigma, mc)
+
     def nms(self, boxes: torch.Tensor, keys: torch.Tensor, counts: torch.Tensor):
+        if self.soft:
+            cfg = self.soft_cfg()
+            _lib.check(self.lib.od_soft_nms(self.ctx.handle, boxes.data_ptr(), keys.data_ptr(), counts.data_ptr(), self.B,
+                                            self.P, self.NC, self.K, C.byref(cfg), self.keep_flat.data_ptr(),
+                                            self.keep_conf.data_ptr(), self.keep_count.data_ptr(), self.det.data_ptr(),
+                                            self.ws_nms.data_ptr(), self.ws_nms_bytes, _stream_ptr()), "od_soft_nms")
+            return self.keep_flat, self.keep_count
         _lib.check(self.lib.od_nms(self.ctx.handle, boxes.data_ptr(), keys.data_ptr(), counts.data_ptr(), self.B,
                                    self.P, self.NC, self.K, self.iou_threshold, self.strict, self.max_det,
                                    self.keep_flat.data_ptr(), self.keep_count.data_ptr(), self.ws_nms.data_ptr(),
@@ -102,7 +147,11 @@ class Postprocessor:
 
     def gather(self):
         """Queue the gather of this batch's kept detections (od_gather_detections) and its copy into the pinned host block
-        on the current stream; read with detections_host() after the stream / event has been waited for."""
+        on the current stream; read with detections_host() after the stream / event has been waited for.  A soft
+        post-processor's scan has written the record block already, with the rescored confidences: only the copy is queued."""
+        if self.soft:
+            self.det_host.copy_(self.det, non_blocking=True)
+            return
         _lib.check(self.lib.od_gather_detections_pred(self.ctx.handle, self._pred.data_ptr(), self.boxes.data_ptr(),
                                                       self.keep_flat.data_ptr(), self.keep_count.data_ptr(), self.B, self.P,
                                                       self.NC, self.max_det, self.det.data_ptr(), _stream_ptr()),
@@ -126,6 +175,18 @@ class Postprocessor:
         if not self.fused:
             return self.run_unfused(pred, conf_threshold)
         assert pred.dtype == torch.float32 and pred.is_contiguous() and tuple(pred.shape) == (self.B, self.P, self.NC + 6)
+        self._conf_threshold = float(conf_threshold)
+        if self.soft:
+            cfg = self.soft_cfg()
+            _lib.check(self.lib.od_detect_soft(self.ctx.handle, pred.data_ptr(), self.priors.data_ptr(), self.B, self.P, self.NC,
+                                               self.loc_scale, 1, float(conf_threshold), self.K, C.byref(cfg),
+                                               self.boxes.data_ptr(), None, self.keys.data_ptr(), self.counts.data_ptr(),
+                                               self.keep_flat.data_ptr(), self.keep_conf.data_ptr(),
+                                               self.keep_count.data_ptr(), self.det.data_ptr(), self.ws_det.data_ptr(),
+                                               self.ws_det_bytes, self.ws_nms.data_ptr(), self.ws_nms_bytes, _stream_ptr()),
+                       "od_detect_soft")
+            self._pred, self._conf_valid = pred, False
+            return self.keep_flat, self.keep_count
         _lib.check(self.lib.od_detect(self.ctx.handle, pred.data_ptr(), self.priors.data_ptr(), self.B, self.P, self.NC,
                                       self.loc_scale, 1, float(conf_threshold), self.K, self.iou_threshold, self.strict,
                                       self.max_det, self.boxes.data_ptr(), None, self.keys.data_ptr(), self.counts.data_ptr(),

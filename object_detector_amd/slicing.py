@@ -181,6 +181,7 @@ class SlicePostprocessor:
         from .net import _stream_ptr
         p = self.post
         assert pred.dtype == torch.float32 and pred.is_contiguous() and tuple(pred.shape) == (p.B, p.P, p.NC + 6)
+        p._conf_threshold = float(conf_threshold)
         _lib.check(self.lib.od_detect_candidates(self.ctx.handle, pred.data_ptr(), p.priors.data_ptr(), p.B, p.P, p.NC,
                                                  p.loc_scale, 1, float(conf_threshold), p.K, self.boxes.data_ptr(), None,
                                                  self.keys.data_ptr(), self.counts.data_ptr(), p.ws_det.data_ptr(),
@@ -194,6 +195,16 @@ class SlicePostprocessor:
         from .net import _stream_ptr
         p = self.post
         lo, hi = self.grid.edge_lo_hi
+        if p.soft:  # the soft scan in place of the greedy one; the report carries the rescored confidences
+            import ctypes as C
+            cfg = p.soft_cfg()
+            _lib.check(self.lib.od_slice_merge_soft(self.ctx.handle, self.keys.data_ptr(), self.counts.data_ptr(),
+                                                    self.boxes.data_ptr(), self.tiles.data_ptr(), self.edges.data_ptr(), self.G,
+                                                    self.T, p.P, p.NC, p.K, lo, hi, C.byref(cfg), self.vote_iou,
+                                                    self.det.data_ptr(), self.src.data_ptr(), self.keep_count.data_ptr(),
+                                                    self.ws.data_ptr(), self.ws_bytes, _stream_ptr()), "od_slice_merge_soft")
+            self.det_host.copy_(self.det, non_blocking=True)
+            return self.det, self.keep_count
         _lib.check(self.lib.od_slice_merge(self.ctx.handle, self.keys.data_ptr(), self.counts.data_ptr(), self.boxes.data_ptr(),
                                            self.tiles.data_ptr(), self.edges.data_ptr(), self.G, self.T, p.P, p.NC, p.K, lo, hi,
                                            p.iou_threshold, p.strict, p.max_det, self.vote_iou, self.det.data_ptr(),

@@ -32,6 +32,16 @@ def add_tta_arguments(p):
     p.add_argument("--vote-iou", default=0.5, type=float, help="box-voting overlap under --tta (<= 0: no voting)")
 
 
+def add_nms_arguments(p):
+    """--nms METHOD / --soft-sigma S / --soft-min-conf C of the evaluation scripts (ObjectDetector(nms=..., ...))."""
+    p.add_argument("--nms", default="hard", choices=("hard", "soft-linear", "soft-gaussian"),
+                   help="suppression stage: greedy NMS, or Soft-NMS with linear / Gaussian score decay on the GPU")
+    p.add_argument("--soft-sigma", default=0.5, type=float, help="sigma of --nms soft-gaussian")
+    p.add_argument("--soft-min-conf", default=None, type=float,
+                   help="under Soft-NMS a detection whose decayed score is not above this is dropped (default: the "
+                        "confidence threshold of the run)")
+
+
 def add_slice_arguments(p):
     """--slices NY NX [--slice-overlap F] [--no-slice-full-view] of the evaluation scripts (ObjectDetector(slices=...))."""
     p.add_argument("--slices", default=None, type=int, nargs=2, metavar=("NY", "NX"),
@@ -51,6 +61,8 @@ def make_detector(tk, args, batch_size, input_size=(320, 320), device_decode=Fal
     if getattr(args, "slices", None) is not None:
         kw["slices"], kw["slice_overlap"] = tuple(args.slices), args.slice_overlap
         kw["slice_full_view"] = not args.no_slice_full_view
+    if getattr(args, "nms", "hard") != "hard":
+        kw["nms"], kw["soft_sigma"], kw["soft_min_conf"] = args.nms, args.soft_sigma, args.soft_min_conf
     if args.synthetic:
         return OD.synthetic(batch_size, input_size, **kw)
     return OD.load_voc(batch_size=batch_size, input_size=input_size, weights=args.weights, **kw)

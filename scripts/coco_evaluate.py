@@ -24,6 +24,7 @@ def _main():
     p.add_argument("--device-decode", action="store_true",
                    help="decode JPEGs and resize every input on the GPU (ObjectDetector(image_decode='device'))")
     _common.add_tta_arguments(p)
+    _common.add_nms_arguments(p)
     _common.add_slice_arguments(p)
     p.add_argument("--conf-threshold", default=None, type=float,
                    help="detections below this confidence are dropped (default: the detector's DEFAULT_CONF_THRESHOLD)")
