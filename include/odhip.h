@@ -359,6 +359,22 @@ int od_assign_anchors_ign(od_ctx* ctx, const float* priors, const float* gt_boxe
                           int NC, float pos_thr, float neg_thr, float loc_scale, float* y, int32_t* assigned_gt,
                           int32_t* npos, void* workspace, size_t workspace_bytes, void* stream);
 
+/* K9b: the same target rows under the ATSS rule (Zhang et al., CVPR 2020), the opt-in assigner [BUILD-DEFINED; the frozen
+ * rule is the header comment of csrc/assign_atss.hip, restated by tests/atss_ref.py].  Per box the candidates are all
+ * priors_per_cell priors of the min(topk, gh*gw) cells nearest to the box centre on each of the n_levels pyramid levels; a
+ * candidate is positive when its IoU (on a 2^-20 lattice) reaches mean + population std of the candidates' IoUs and its cell
+ * centre lies strictly inside the box; a box with no positive force-takes its best candidate; a prior claimed twice goes to
+ * a forced claim, then to the larger IoU, then to the lower box index.  No IoU ignore band: assigned_gt is never -2.
+ *   priors f32 [P,4] in row order (level, y, x, prior); grid_hw i32 [n_levels,2] = (gh, gw) per level, HOST memory, read
+ *   before the call returns; sum gh*gw*priors_per_cell == P; 1 <= n_levels <= 4; 1 <= priors_per_cell <= 8; 1 <= topk <= 32.
+ *   gt_flags may be NULL (no ignore regions); otherwise as in od_assign_anchors_ign, with ign_thr > 0.  Gmax <= 128.
+ *   workspace: od_assign_atss_workspace_bytes.  Other arguments and outputs as od_assign_anchors. */
+size_t od_assign_atss_workspace_bytes(int B, int P, int Gmax);
+int od_assign_atss(od_ctx* ctx, const float* priors, const int32_t* grid_hw, int n_levels, int priors_per_cell,
+                   const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts, const int32_t* gt_flags,
+                   float ign_thr, int topk, int B, int P, int Gmax, int NC, float loc_scale, float* y, int32_t* assigned_gt,
+                   int32_t* npos, void* workspace, size_t workspace_bytes, void* stream);
+
 /* K10: loss forward + gradient (reference docs/MODEL.md:33-52): focal(objectness, 2-class softmax) +
  * softmax-CE(classes, assigned priors) + box loss (box_mode 0 smooth-L1 / 1 MSE, assigned priors), each weighted and
  * divided by max(1, #assigned).  pred, y, grad f32 [B,P,2+NC+4]; losses f32 [4] = obj, cls, box, total.  1 <= NC <= 1024. */

@@ -12,42 +12,9 @@
 //   3. a prior that came out of 1 + 2 as BACKGROUND becomes "ignore" (all-zero row, assigned_gt -3) when
 //      inter(prior, r) / area(prior) >= ign_thr for any flagged box r.  Positives stay positive; -2 rows stay -2.
 // HBM-bound elementwise work; IoU uses IEEE f32 division; compiled with -ffp-contract=off => bit-exact vs numpy.
-#include "common.h"
+#include "assign_common.h"
 
 namespace {
-
-typedef unsigned long long u64;
-constexpr int GMAX = 128;
-
-__device__ __forceinline__ float iou_f32(const f32x4 a, const f32x4 c) {
-  const float ix1 = fmaxf(a[0], c[0]), iy1 = fmaxf(a[1], c[1]);
-  const float ix2 = fminf(a[2], c[2]), iy2 = fminf(a[3], c[3]);
-  const float iw = fmaxf(ix2 - ix1, 0.f), ih = fmaxf(iy2 - iy1, 0.f);
-  const float inter = iw * ih;
-  const float area_a = (a[2] - a[0]) * (a[3] - a[1]);
-  const float area_c = (c[2] - c[0]) * (c[3] - c[1]);
-  const float uni = (area_a + area_c) - inter;
-  return uni > 0.f ? inter / uni : 0.f;
-}
-
-// share of prior c that lies inside region a: intersection over the PRIOR's area (>= IoU)
-__device__ __forceinline__ float cover_f32(const f32x4 a, const f32x4 c) {
-  const float ix1 = fmaxf(a[0], c[0]), iy1 = fmaxf(a[1], c[1]);
-  const float ix2 = fminf(a[2], c[2]), iy2 = fminf(a[3], c[3]);
-  const float iw = fmaxf(ix2 - ix1, 0.f), ih = fmaxf(iy2 - iy1, 0.f);
-  const float inter = iw * ih;
-  const float area_c = (c[2] - c[0]) * (c[3] - c[1]);
-  return area_c > 0.f ? inter / area_c : 0.f;
-}
-
-// IGN: bit g of smask[g >> 6] <- bit 0 of flags[g] for g < G (G <= 128: waves 0 and 1 of the block, one ballot each)
-__device__ __forceinline__ void stage_flags(const int* __restrict__ flags, int G, int tid, u64* smask) {
-  if (tid < GMAX) {
-    const bool f = tid < G && (flags[tid] & 1);
-    const u64 m = __ballot(f);
-    if ((tid & 63) == 0) smask[tid >> 6] = m;
-  }
-}
 
 // the per-prior loop of pass 1 over the boxes in LDS; SKIP: a flagged box (bit g of smask) owns no prior
 template <bool SKIP>
@@ -136,25 +103,14 @@ __global__ __launch_bounds__(256) void od_assign_encode(const float* __restrict_
     bool region = false;
     if (IGN && g < 0 && !ignore && (smask[0] | smask[1])) {  // background prior of an image that has regions
       const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
-      for (int w = 0; w < GMAX / 64; ++w)
-        for (u64 m = smask[w]; m; m &= m - 1) {  // the flagged boxes only; the address is the same for the whole block
-          const int r = w * 64 + __builtin_ctzll(m);
-          region |= cover_f32(*(const f32x4*)(gt_boxes + ((long long)b * Gmax + r) * 4), pr) >= ign_thr;
-        }
+      region = region_covers(gt_boxes + (long long)b * Gmax * 4, smask, pr, ign_thr);
     }
     float* row = y + ((long long)b * P + p) * C;
     for (int c = 0; c < C; ++c) row[c] = 0.f;
     if (g >= 0) {
       const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
       const f32x4 gb = *(const f32x4*)(gt_boxes + ((long long)b * Gmax + g) * 4);
-      const float pw = pr[2] - pr[0], ph = pr[3] - pr[1];
-      row[1] = 1.f;
-      const int cls = gt_classes[(long long)b * Gmax + g];
-      if (cls >= 0 && cls < NC) row[2 + cls] = 1.f;
-      row[2 + NC + 0] = ((gb[0] - pr[0]) / pw) / loc_scale;
-      row[2 + NC + 1] = ((gb[1] - pr[1]) / ph) / loc_scale;
-      row[2 + NC + 2] = ((gb[2] - pr[2]) / pw) / loc_scale;
-      row[2 + NC + 3] = ((gb[3] - pr[3]) / ph) / loc_scale;
+      write_owned_row(row, NC, pr, gb, gt_classes[(long long)b * Gmax + g], loc_scale);
       atomicAdd(&scount, 1);
     } else if (!ignore && !region) {
       row[0] = 1.f;

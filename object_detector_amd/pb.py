@@ -7,6 +7,12 @@
 a sliver a mosaic tile border left of an object) marks ignore regions, as both evaluators treat them.  Such a box owns no
 prior, and a prior that would be background is not trained on (all-zero target row) when at least `ign_thr` of ITS area lies
 inside a region (od_assign_anchors_ign).  IGN_THR = 0.5 is a policy value of this build, not a tolerance.
+
+`PriorBoxes(..., assigner="atss", atss_topk=9)` [BUILD-DEFINED, opt-in]: Adaptive Training Sample Selection (Zhang et al.,
+CVPR 2020) decides which priors learn which object instead of the fixed IoU thresholds: the priors of the `atss_topk` cells
+nearest to the object's centre on every level are candidates, and the IoU threshold is the candidates' own mean + standard
+deviation (od_assign_atss; the frozen rule is the header comment of csrc/assign_atss.hip).  `pos_thr` / `neg_thr` are unused
+there; `ignore_regions` works as above.  The default "max-iou" is the rule of od_assign_anchors.
 """
 from __future__ import annotations
 
@@ -21,6 +27,17 @@ from .net import Context, _stream_ptr
 POS_THR, NEG_THR, LOC_SCALE = 0.5, 0.4, 0.1
 IGN_THR = 0.5
 GMAX = 128
+ASSIGNERS = ("max-iou", "atss")
+ATSS_TOPK, ATSS_MAX_TOPK = 9, 32
+
+
+def check_assigner(assigner, atss_topk):
+    """ValueError for an assigner or a top-k that od_assign_atss would refuse (host-only: no library is loaded)."""
+    if assigner not in ASSIGNERS:
+        raise ValueError(f"assigner must be one of {ASSIGNERS}, got {assigner!r}")
+    if isinstance(atss_topk, bool) or int(atss_topk) != atss_topk or not 1 <= int(atss_topk) <= ATSS_MAX_TOPK:
+        raise ValueError(f"atss_topk must be an integer in 1..{ATSS_MAX_TOPK}, got {atss_topk!r}")
+    return assigner, int(atss_topk)
 
 
 class ObjectsAnnotation:
@@ -51,7 +68,9 @@ class ObjectsAnnotation:
 
 class PriorBoxes:
     def __init__(self, input_size=(320, 320), num_classes=20, prior_wh=PR.DEFAULT_PRIOR_WH, device="cuda:0",
-                 pos_thr=POS_THR, neg_thr=NEG_THR, loc_scale=LOC_SCALE, ignore_regions=False, ign_thr=IGN_THR):
+                 pos_thr=POS_THR, neg_thr=NEG_THR, loc_scale=LOC_SCALE, ignore_regions=False, ign_thr=IGN_THR,
+                 assigner="max-iou", atss_topk=ATSS_TOPK):
+        self.assigner, self.atss_topk = check_assigner(assigner, atss_topk)
         self.input_size = tuple(int(v) for v in input_size)
         self.num_classes = int(num_classes)
         self.prior_wh = np.asarray(prior_wh, np.float64)
@@ -95,7 +114,7 @@ class PriorBoxes:
     def encode_batch(self, annotations, return_device=False):
         """list[ObjectsAnnotation] -> y f32 [B,P,2+NC+4] (+ npos [B], assigned [B,P]) through od_assign_anchors, or, with
         ignore_regions=True, through od_assign_anchors_ign with `difficults` as the region flags (assigned -3 = ignored by a
-        region)."""
+        region).  assigner="atss": through od_assign_atss, with the same flags."""
         ctx = self._ensure()
         B, P, NC = len(annotations), len(self.pb_locs), self.num_classes
         gmax = max(1, max((a.num_objects for a in annotations), default=1))
@@ -115,22 +134,31 @@ class PriorBoxes:
         y = torch.empty((B, P, NC + 6), dtype=torch.float32, device=dev)
         npos = torch.empty((B,), dtype=torch.int32, device=dev)
         assigned = torch.empty((B, P), dtype=torch.int32, device=dev)
-        wsb = ctx.lib.od_assign_workspace_bytes(B, P, gmax)
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
-        if gf is not None:
-            gf_t = torch.from_numpy(gf).to(dev)
-            _lib.check(ctx.lib.od_assign_anchors_ign(ctx.handle, self._priors_dev.data_ptr(), gb_t.data_ptr(), gc_t.data_ptr(),
-                                                     gn_t.data_ptr(), gf_t.data_ptr(), self.ign_thr, B, P, gmax, NC,
-                                                     self.pos_thr, self.neg_thr, self.loc_scale, y.data_ptr(),
-                                                     assigned.data_ptr(), npos.data_ptr(), ws.data_ptr(), wsb, _stream_ptr()),
-                       "od_assign_anchors_ign")
-            if return_device:
-                return y, npos, assigned
-            return y.cpu().numpy(), npos.cpu().numpy(), assigned.cpu().numpy()
-        _lib.check(ctx.lib.od_assign_anchors(ctx.handle, self._priors_dev.data_ptr(), gb_t.data_ptr(), gc_t.data_ptr(),
-                                             gn_t.data_ptr(), B, P, gmax, NC, self.pos_thr, self.neg_thr,
-                                             self.loc_scale, y.data_ptr(), assigned.data_ptr(), npos.data_ptr(),
-                                             ws.data_ptr(), wsb, _stream_ptr()), "od_assign_anchors")
+        gf_t = torch.from_numpy(gf).to(dev) if gf is not None else None
+        if self.assigner == "atss":
+            levels = PR.level_shapes(self.input_size)
+            grid_hw = (C.c_int32 * (2 * len(levels)))(*[v for hw in levels for v in hw])
+            wsb = ctx.lib.od_assign_atss_workspace_bytes(B, P, gmax)
+            ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+            _lib.check(ctx.lib.od_assign_atss(ctx.handle, self._priors_dev.data_ptr(), grid_hw, len(levels), PR.NUM_PRIORS,
+                                              gb_t.data_ptr(), gc_t.data_ptr(), gn_t.data_ptr(),
+                                              None if gf_t is None else gf_t.data_ptr(), self.ign_thr, self.atss_topk,
+                                              B, P, gmax, NC, self.loc_scale, y.data_ptr(), assigned.data_ptr(),
+                                              npos.data_ptr(), ws.data_ptr(), wsb, _stream_ptr()), "od_assign_atss")
+        else:
+            wsb = ctx.lib.od_assign_workspace_bytes(B, P, gmax)
+            ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+            if gf_t is not None:
+                _lib.check(ctx.lib.od_assign_anchors_ign(ctx.handle, self._priors_dev.data_ptr(), gb_t.data_ptr(),
+                                                         gc_t.data_ptr(), gn_t.data_ptr(), gf_t.data_ptr(), self.ign_thr, B, P,
+                                                         gmax, NC, self.pos_thr, self.neg_thr, self.loc_scale, y.data_ptr(),
+                                                         assigned.data_ptr(), npos.data_ptr(), ws.data_ptr(), wsb,
+                                                         _stream_ptr()), "od_assign_anchors_ign")
+            else:
+                _lib.check(ctx.lib.od_assign_anchors(ctx.handle, self._priors_dev.data_ptr(), gb_t.data_ptr(), gc_t.data_ptr(),
+                                                     gn_t.data_ptr(), B, P, gmax, NC, self.pos_thr, self.neg_thr,
+                                                     self.loc_scale, y.data_ptr(), assigned.data_ptr(), npos.data_ptr(),
+                                                     ws.data_ptr(), wsb, _stream_ptr()), "od_assign_anchors")
         if return_device:
             return y, npos, assigned
         return y.cpu().numpy(), npos.cpu().numpy(), assigned.cpu().numpy()

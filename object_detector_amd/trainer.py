@@ -20,7 +20,7 @@ import torch
 from . import _lib, desc, weights as W
 from .net import Context, _stream_ptr
 from .ops import BOX_MODES
-from .pb import PriorBoxes
+from .pb import ATSS_TOPK, PriorBoxes, check_assigner
 
 BN_MOMENTUM = 0.99  # Keras default
 
@@ -61,7 +61,7 @@ class Trainer:
                  weight_decay=0.0, loss_scale=1024.0, box_mode="smooth_l1", backbone_act=("leaky", 0.1),
                  head_act=("elu", 1.0), comm=None, world_size=1, grad_payload=None, dynamic_loss_scale=True,
                  lr_multipliers=None, prior_wh=None, ignore_regions=False, ign_thr=None, loss_weights=(1.0, 1.0, 1.0),
-                 ema_decay=None, ema_warmup=True):
+                 ema_decay=None, ema_warmup=True, assigner="max-iou", atss_topk=ATSS_TOPK):
         # ema_decay: None = no averaged model (no extra buffers, sgd() launches od_sgd_step_multi); 0 < ema_decay < 1 keeps
         # an exponential moving average of the masters (self.ema) and of the BatchNorm running statistics
         # (self.ema_run_stats), updated inside sgd() with the decay ema_decay_at(self.ema_updates, ema_decay, ema_warmup)
@@ -69,6 +69,7 @@ class Trainer:
             raise ValueError(f"ema_decay must be None or lie in (0, 1), got {ema_decay!r}")
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
+        check_assigner(assigner, atss_topk)  # a bad assigner fails here, before the device is touched
         self.ctx = Context.get(device)
         self.lib = self.ctx.lib
         self.device = torch.device(device)
@@ -104,7 +105,9 @@ class Trainer:
         # docs/MODEL.md:29-31); None = the frozen default table
         # ignore_regions / ign_thr: handed to the PriorBoxes (pb.py): annotations' `difficults` become ignore regions in
         # step(x, annotations=...) and in tr.pb.encode_truth_device, the generator callback
+        # assigner / atss_topk: "max-iou" (od_assign_anchors) or "atss" (od_assign_atss), handed to the PriorBoxes as well
         self.pb = PriorBoxes((self.H0, self.W0), self.num_classes, device=self.device, ignore_regions=ignore_regions,
+                             assigner=assigner, atss_topk=atss_topk,
                              **({} if prior_wh is None else {"prior_wh": prior_wh}),
                              **({} if ign_thr is None else {"ign_thr": ign_thr}))
         self.P = len(self.pb)

@@ -20,6 +20,9 @@ def _main():
     p.add_argument("--ignore-regions", action="store_true",
                    help="treat difficult / iscrowd boxes as ignore regions; the priors they switch off are drawn as class 0 "
                         "boxes of their own image <i>_ignored.jpg")
+    p.add_argument("--assigner", default="max-iou", choices=("max-iou", "atss"),
+                   help="the rule that gives priors to objects: fixed IoU thresholds, or ATSS (od_assign_atss)")
+    p.add_argument("--atss-topk", default=9, type=int, metavar="K", help="--assigner atss: nearest cells per level")
     args = p.parse_args()
     if args.synthetic:
         X_val, y_val = _common.synthetic_dataset(1)
@@ -29,6 +32,8 @@ def _main():
     # as the reference does (check_assign.py:19,21): the detector at ITS default input size, the generator at 512 x 512 --
     # prior boxes live in normalised image coordinates, so encode_truth / decode_locs do not depend on the image size
     od = _common.make_detector(tk, args, 1, use_multi_gpu=False)
+    from object_detector_amd.pb import check_assigner
+    od.pb.assigner, od.pb.atss_topk = check_assigner(args.assigner, args.atss_topk)
     if args.ignore_regions:
         od.pb.ignore_regions = True
         y_val[0].difficults[-1:] = True  # so that there is a region to look at: the image's last box

@@ -61,6 +61,10 @@ def build_parser():
                    help="probability that a training image is a mosaic of four (od_augment_mosaic; off by default)")
     p.add_argument("--ignore-regions", action="store_true",
                    help="difficult / iscrowd boxes and the slivers a mosaic leaves are ignore regions instead of positives")
+    p.add_argument("--assigner", default="max-iou", choices=("max-iou", "atss"),
+                   help="the rule that gives priors to objects: fixed IoU thresholds (0.5 / 0.4) with a forced best match, or "
+                        "ATSS: the priors nearest to the object's centre on every level, IoU threshold = their mean + std")
+    p.add_argument("--atss-topk", default=9, type=int, metavar="K", help="--assigner atss: nearest cells per level (1..32)")
     p.add_argument("--shapes-difficult", default=0.0, type=float, help="--shapes: share of objects marked difficult")
     p.add_argument("--shapes-crowd", default=0.0, type=float, help="--shapes: share of images with a crowd region")
     p.add_argument("--prefetch", default=2, type=int, help="batches the generator thread runs ahead (0 = in the training thread)")
@@ -151,7 +155,8 @@ def _run(args):
         log.info(f"fitted prior sizes (grid-cell units), level 0: {np.round(prior_wh[0], 2).tolist()}")
     tr = Trainer(params, args.batch_size, tuple(args.input_size), device=dev, lr=args.lr, momentum=args.momentum,
                  weight_decay=args.weight_decay, comm=comm, world_size=world, lr_multipliers=mult, prior_wh=prior_wh, box_mode=args.box_loss,
-                 ignore_regions=args.ignore_regions, loss_weights=(1.0, 1.0, args.box_weight),
+                 ignore_regions=args.ignore_regions, loss_weights=(1.0, 1.0, args.box_weight), assigner=args.assigner,
+                 atss_topk=args.atss_topk,
                  **({} if args.ema is None else {"ema_decay": args.ema}))
     start, flow_seed = 0, args.seed + rank
     if args.resume is not None:
@@ -163,7 +168,15 @@ def _run(args):
         flow_seed = int(np.random.SeedSequence([args.seed, rank, start]).generate_state(1)[0] >> 1)
         log.info(f"resumed from {args.resume}: starting at step {start}, loss scale {tr.loss_scale:g}, "
                  f"ema_updates {tr.ema_updates}")
-    gen =od_gen.create_generator(tuple(args.input_size), preprocess_input=None, encode_truth=tr.pb.encode_truth_device,
+    positives = {"sum": torch.zeros((), dtype=torch.int64, device=dev), "images": 0}
+
+    def encode_truth(anns):  # tr.pb.encode_truth_device, and the positives it made are counted (on the device: no sync)
+        anns = list(anns)
+        target, npos, _assigned = tr.pb.encode_batch(anns, return_device=True)
+        positives["sum"] += npos.sum()
+        positives["images"] += len(anns)
+        return target
+    gen =od_gen.create_generator(tuple(args.input_size), preprocess_input=None, encode_truth=encode_truth,
                                   device=dev, on_device=True, device_cache=not args.no_device_cache, mosaic=args.mosaic,
                                   ignore_regions=args.ignore_regions)
     batches, per_epoch = gen.flow(X, y, batch_size=args.batch_size, data_augmentation=True, shuffle=True, seed=flow_seed,
@@ -194,6 +207,9 @@ def _run(args):
     log.info(f"loss first {k} steps {hist[:k, 3].mean():.4f} -> last {k} steps {hist[-k:, 3].mean():.4f}; "
              f"{ran} steps in {dt:.1f} s ({ran * args.batch_size * world / dt:.0f} images/s), "
              f"skipped {tr.skipped_steps}, loss scale {tr.loss_scale:g}")
+    torch.cuda.synchronize()  # the generator's thread counted on its own stream
+    log.info(f"assigner {tr.pb.assigner}: {int(positives['sum']) / max(1, positives['images']):.2f} positive priors per image "
+             f"over {positives['images']} encoded images")
     if tr.ema_decay is not None:
         log.info(f"weight average: decay {tr.ema_decay:g}, ema_updates {tr.ema_updates}")
     if tk.dl.is_main_process():
