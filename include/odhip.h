@@ -375,6 +375,27 @@ int od_assign_atss(od_ctx* ctx, const float* priors, const int32_t* grid_hw, int
                    float ign_thr, int topk, int B, int P, int Gmax, int NC, float loc_scale, float* y, int32_t* assigned_gt,
                    int32_t* npos, void* workspace, size_t workspace_bytes, void* stream);
 
+/* K9c: the same target rows under the task-aligned rule (TOOD, Feng et al., ICCV 2021), the prediction-aware opt-in assigner
+ * [BUILD-DEFINED; the frozen rule is the header comment of csrc/assign_tal.hip, restated by tests/tal_ref.py].  pred f32
+ * [B,P,2+NC+4] are the network's raw outputs of THIS step (16-byte aligned).  Per prior: la = log P(object) from the two
+ * objectness logits, lse = log-sum-exp of the class logits, pbox = od_decode_locs of its offsets (no clip, corners sorted).
+ * Per unflagged box the candidates are the priors whose cell centre lies strictly inside the box and whose
+ * u = IoU(box, pbox) > 0; the box claims the min(topk, #candidates) of the largest
+ * l = alpha * (la + z_class - lse) + beta * log u (ties: lower prior index; a class outside 0..NC-1 drops the class term).
+ * A box without a candidate force-takes the prior of its largest static IoU > 0.  A prior claimed twice goes to a forced
+ * claim, then to the larger IoU (u, or the static one of a forced claim), then to the lower box index.  Targets are hard
+ * (objectness 1, one-hot class), rows / ignore regions / assigned_gt / npos exactly as od_assign_atss.
+ *   alpha, beta finite and > 0 (TOOD: 1, 6); 1 <= topk <= 32 (TOOD: 13); 1 <= NC <= 1024; grid_hw, n_levels,
+ *   priors_per_cell, gt_flags, ign_thr, Gmax as od_assign_atss.
+ *   metric f32 [B,P] (may be NULL): l of the winning normal claim; 0 for background, ignored and forced rows.
+ *   workspace: od_assign_tal_workspace_bytes = 32 bytes per prior of the batch (16-byte aligned); it does not grow with Gmax. */
+size_t od_assign_tal_workspace_bytes(int B, int P, int Gmax);
+int od_assign_tal(od_ctx* ctx, const float* priors, const int32_t* grid_hw, int n_levels, int priors_per_cell,
+                  const float* pred, const float* gt_boxes, const int32_t* gt_classes, const int32_t* gt_counts,
+                  const int32_t* gt_flags, float ign_thr, float alpha, float beta, int topk, int B, int P, int Gmax, int NC,
+                  float loc_scale, float* y, int32_t* assigned_gt, int32_t* npos, float* metric, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* K10: loss forward + gradient (reference docs/MODEL.md:33-52): focal(objectness, 2-class softmax) +
  * softmax-CE(classes, assigned priors) + box loss (box_mode 0 smooth-L1 / 1 MSE, assigned priors), each weighted and
  * divided by max(1, #assigned).  pred, y, grad f32 [B,P,2+NC+4]; losses f32 [4] = obj, cls, box, total.  1 <= NC <= 1024. */

@@ -27,11 +27,6 @@ struct AtssLevels {
   int gh[ATSS_MAX_LEVELS], gw[ATSS_MAX_LEVELS], base[ATSS_MAX_LEVELS];  // base: index of the level's first prior
 };
 
-// claim key: forced | IoU bits | 255 - g.  IoU >= 0, so its bits order like its value; 255 - g >= 128 keeps a key nonzero.
-__device__ __forceinline__ u64 claim_key(bool forced, float v, int g) {
-  return ((u64)forced << 40) | ((u64)__float_as_uint(v) << 8) | (u64)(255 - g);
-}
-
 __device__ __forceinline__ u64 wave_min_u64(u64 v) {
   for (int o = 32; o; o >>= 1) {
     const u64 t = __shfl_xor(v, o, 64);
@@ -182,45 +177,6 @@ __global__ __launch_bounds__(256) void od_atss_select(const float* __restrict__ 
   }
 }
 
-// encode pass: one thread per prior reads its claim and writes the row, assigned_gt and npos
-template <bool IGN>
-__global__ __launch_bounds__(256) void od_atss_encode(const float* __restrict__ priors, const float* __restrict__ gt_boxes,
-                                                      const int* __restrict__ gt_classes,
-                                                      const int* __restrict__ gt_counts, const int* __restrict__ gt_flags,
-                                                      int P, int Gmax, int NC, float ign_thr, float loc_scale,
-                                                      const u64* __restrict__ claim, float* __restrict__ y,
-                                                      int* __restrict__ assigned_gt, int* __restrict__ npos) {
-  __shared__ int scount;
-  __shared__ u64 smask[GMAX / 64];
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const int G = min(gt_counts[b], Gmax);
-  if (IGN) stage_flags(gt_flags + (long long)b * Gmax, G, tid, smask);
-  if (tid == 0) scount = 0;
-  __syncthreads();
-  const int p = blockIdx.x * 256 + tid;
-  if (p < P) {
-    const int C = NC + 6;
-    const u64 k = claim[(long long)b * P + p];
-    const int g = k ? 255 - (int)(k & 255ull) : -1;
-    const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
-    bool region = false;
-    if (IGN && g < 0 && (smask[0] | smask[1]))  // background prior of an image that has regions
-      region = region_covers(gt_boxes + (long long)b * Gmax * 4, smask, pr, ign_thr);
-    float* row = y + ((long long)b * P + p) * C;
-    for (int c = 0; c < C; ++c) row[c] = 0.f;
-    if (g >= 0) {
-      const f32x4 gb = *(const f32x4*)(gt_boxes + ((long long)b * Gmax + g) * 4);
-      write_owned_row(row, NC, pr, gb, gt_classes[(long long)b * Gmax + g], loc_scale);
-      atomicAdd(&scount, 1);
-    } else if (!region) {
-      row[0] = 1.f;
-    }
-    if (assigned_gt) assigned_gt[(long long)b * P + p] = g >= 0 ? g : (region ? -3 : -1);
-  }
-  __syncthreads();
-  if (tid == 0 && scount) atomicAdd(&npos[b], scount);
-}
-
 }  // namespace
 
 extern "C" size_t od_assign_atss_workspace_bytes(int B, int P, int Gmax) {
@@ -266,10 +222,10 @@ extern "C" int od_assign_atss(od_ctx* ctx, const float* priors, const int32_t* g
   OD_CHECK_LAUNCH();
   dim3 grid(od_ceil_div(P, 256), B);
   if (gt_flags)
-    hipLaunchKernelGGL(od_atss_encode<true>, grid, dim3(256), 0, s, priors, gt_boxes, gt_classes, gt_counts, gt_flags, P,
+    hipLaunchKernelGGL(od_claim_encode<true>, grid, dim3(256), 0, s, priors, gt_boxes, gt_classes, gt_counts, gt_flags, P,
                        Gmax, NC, ign_thr, loc_scale, (const u64*)workspace, y, assigned_gt, npos);
   else
-    hipLaunchKernelGGL(od_atss_encode<false>, grid, dim3(256), 0, s, priors, gt_boxes, gt_classes, gt_counts, gt_flags, P,
+    hipLaunchKernelGGL(od_claim_encode<false>, grid, dim3(256), 0, s, priors, gt_boxes, gt_classes, gt_counts, gt_flags, P,
                        Gmax, NC, ign_thr, loc_scale, (const u64*)workspace, y, assigned_gt, npos);
   OD_CHECK_LAUNCH();
   return OD_OK;

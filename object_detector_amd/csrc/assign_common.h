@@ -1,5 +1,6 @@
-// Device helpers shared by the prior-box assigners (assign.hip: max-IoU rule; assign_atss.hip: ATSS rule): the f32 IoU and
-// cover, the flag staging and the target row.  Every f32 sequence here is mirrored op for op by oracle/assign.py and
+// Device helpers shared by the prior-box assigners (assign.hip: max-IoU rule; assign_atss.hip: ATSS rule; assign_tal.hip:
+// task-aligned rule): the f32 IoU and cover, the flag staging, the target row, and the claim key and encode pass of the two
+// claim-table assigners.  Every f32 sequence here is mirrored op for op by oracle/assign.py and
 // tests/assign_ign_ref.py, so these TUs are compiled with -ffp-contract=off.
 #pragma once
 #include "common.h"
@@ -61,6 +62,51 @@ __device__ __forceinline__ void write_owned_row(float* row, int NC, const f32x4 
   row[2 + NC + 1] = ((gb[1] - pr[1]) / ph) / loc_scale;
   row[2 + NC + 2] = ((gb[2] - pr[2]) / pw) / loc_scale;
   row[2 + NC + 3] = ((gb[3] - pr[3]) / ph) / loc_scale;
+}
+
+// claim key: forced | IoU bits | 255 - g.  IoU >= 0, so its bits order like its value; 255 - g >= 128 keeps a key nonzero.
+__device__ __forceinline__ u64 claim_key(bool forced, float v, int g) {
+  return ((u64)forced << 40) | ((u64)__float_as_uint(v) << 8) | (u64)(255 - g);
+}
+
+// encode pass of the claim-table assigners (assign_atss.hip, assign_tal.hip): one thread per prior reads its claim and writes
+// the row, assigned_gt and npos
+template <bool IGN>
+__global__ __launch_bounds__(256) void od_claim_encode(const float* __restrict__ priors, const float* __restrict__ gt_boxes,
+                                                       const int* __restrict__ gt_classes,
+                                                       const int* __restrict__ gt_counts, const int* __restrict__ gt_flags,
+                                                       int P, int Gmax, int NC, float ign_thr, float loc_scale,
+                                                       const u64* __restrict__ claim, float* __restrict__ y,
+                                                       int* __restrict__ assigned_gt, int* __restrict__ npos) {
+  __shared__ int scount;
+  __shared__ u64 smask[GMAX / 64];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int G = min(gt_counts[b], Gmax);
+  if (IGN) stage_flags(gt_flags + (long long)b * Gmax, G, tid, smask);
+  if (tid == 0) scount = 0;
+  __syncthreads();
+  const int p = blockIdx.x * 256 + tid;
+  if (p < P) {
+    const int C = NC + 6;
+    const u64 k = claim[(long long)b * P + p];
+    const int g = k ? 255 - (int)(k & 255ull) : -1;
+    const f32x4 pr = *(const f32x4*)(priors + (long long)p * 4);
+    bool region = false;
+    if (IGN && g < 0 && (smask[0] | smask[1]))  // background prior of an image that has regions
+      region = region_covers(gt_boxes + (long long)b * Gmax * 4, smask, pr, ign_thr);
+    float* row = y + ((long long)b * P + p) * C;
+    for (int c = 0; c < C; ++c) row[c] = 0.f;
+    if (g >= 0) {
+      const f32x4 gb = *(const f32x4*)(gt_boxes + ((long long)b * Gmax + g) * 4);
+      write_owned_row(row, NC, pr, gb, gt_classes[(long long)b * Gmax + g], loc_scale);
+      atomicAdd(&scount, 1);
+    } else if (!region) {
+      row[0] = 1.f;
+    }
+    if (assigned_gt) assigned_gt[(long long)b * P + p] = g >= 0 ? g : (region ? -3 : -1);
+  }
+  __syncthreads();
+  if (tid == 0 && scount) atomicAdd(&npos[b], scount);
 }
 
 }  // namespace

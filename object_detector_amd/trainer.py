@@ -20,7 +20,7 @@ import torch
 from . import _lib, desc, weights as W
 from .net import Context, _stream_ptr
 from .ops import BOX_MODES
-from .pb import ATSS_TOPK, PriorBoxes, check_assigner
+from .pb import ATSS_TOPK, TAL_ALPHA, TAL_BETA, TAL_TOPK, PriorBoxes, check_assigner, check_tal
 
 BN_MOMENTUM = 0.99  # Keras default
 
@@ -61,7 +61,8 @@ class Trainer:
                  weight_decay=0.0, loss_scale=1024.0, box_mode="smooth_l1", backbone_act=("leaky", 0.1),
                  head_act=("elu", 1.0), comm=None, world_size=1, grad_payload=None, dynamic_loss_scale=True,
                  lr_multipliers=None, prior_wh=None, ignore_regions=False, ign_thr=None, loss_weights=(1.0, 1.0, 1.0),
-                 ema_decay=None, ema_warmup=True, assigner="max-iou", atss_topk=ATSS_TOPK):
+                 ema_decay=None, ema_warmup=True, assigner="max-iou", atss_topk=ATSS_TOPK, tal_topk=TAL_TOPK,
+                 tal_alpha=TAL_ALPHA, tal_beta=TAL_BETA):
         # ema_decay: None = no averaged model (no extra buffers, sgd() launches od_sgd_step_multi); 0 < ema_decay < 1 keeps
         # an exponential moving average of the masters (self.ema) and of the BatchNorm running statistics
         # (self.ema_run_stats), updated inside sgd() with the decay ema_decay_at(self.ema_updates, ema_decay, ema_warmup)
@@ -70,6 +71,7 @@ class Trainer:
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         check_assigner(assigner, atss_topk)  # a bad assigner fails here, before the device is touched
+        check_tal(tal_topk, tal_alpha, tal_beta)
         self.ctx = Context.get(device)
         self.lib = self.ctx.lib
         self.device = torch.device(device)
@@ -106,8 +108,11 @@ class Trainer:
         # ignore_regions / ign_thr: handed to the PriorBoxes (pb.py): annotations' `difficults` become ignore regions in
         # step(x, annotations=...) and in tr.pb.encode_truth_device, the generator callback
         # assigner / atss_topk: "max-iou" (od_assign_anchors) or "atss" (od_assign_atss), handed to the PriorBoxes as well
+        # assigner "tal" (od_assign_tal; tal_topk / tal_alpha / tal_beta): assignment from this step's predictions, so step()
+        # encodes BEHIND the forward pass and takes annotations only
         self.pb = PriorBoxes((self.H0, self.W0), self.num_classes, device=self.device, ignore_regions=ignore_regions,
-                             assigner=assigner, atss_topk=atss_topk,
+                             assigner=assigner, atss_topk=atss_topk, tal_topk=tal_topk, tal_alpha=tal_alpha,
+                             tal_beta=tal_beta,
                              **({} if prior_wh is None else {"prior_wh": prior_wh}),
                              **({} if ign_thr is None else {"ign_thr": ign_thr}))
         self.P = len(self.pb)
@@ -187,6 +192,8 @@ class Trainer:
         self.pred = torch.zeros((self.B, self.P, self.C), dtype=torch.float32, device=dev)
         self.grad_pred = torch.zeros_like(self.pred)
         self.losses = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.last_npos = None  # positives per image [B] (device, i32) of the last step that encoded annotations
+        self.last_target = None  # the target [B,P,C] the last step's loss was taken on (device; the caller's y_target or the encode's)
         self.loss_ws = torch.empty(self.lib.od_loss_workspace_bytes(self.B, self.P), dtype=torch.uint8, device=dev)
         mx = max(n.M * n.Cout for n in self.nodes)
         # dz of the node being processed: three rotating buffers, because the weight gradient of node k runs on a second
@@ -639,11 +646,23 @@ class Trainer:
         return self._consecutive_skips >= self.max_consecutive_skips
 
     def step(self, x_u8, annotations=None, y_target=None):
-        """One training step.  annotations: list[ObjectsAnnotation] (encoded on the device) or y_target [B,P,C]."""
+        """One training step.  annotations: list[ObjectsAnnotation] (encoded on the device) or y_target [B,P,C].
+        assigner="tal" assigns from this step's predictions: annotations only, encoded between forward and loss on the
+        step's stream.  self.last_npos keeps the positives per image of the encode (device [B]; None after a y_target step)."""
+        tal = self.pb.assigner == "tal"
+        if tal and (y_target is not None or annotations is None):
+            raise ValueError('assigner "tal" assigns from the predictions of the step: step(x, annotations=...) only, '
+                             'a ready-made y_target cannot be used')
         self._poll_nonfinite()
-        if y_target is None:
-            y_target, _npos, _ = self.pb.encode_batch(annotations, return_device=True)
+        self.last_npos = None
+        if y_target is None and not tal:
+            y_target, self.last_npos, _ = self.pb.encode_batch(annotations, return_device=True)
+        if tal:  # the boxes travel to the device now: nothing but the assigner's launches sits behind the forward pass
+            uploaded = self.pb.upload_batch(annotations)
         self.forward(x_u8)
+        if tal:
+            y_target, self.last_npos, _ = self.pb.encode_uploaded(uploaded, return_device=True, pred=self.pred)
+        self.last_target = y_target
         self.loss(y_target)
         self.backward()
         self.allreduce()

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""Time of the two prior-box assigners, in ONE process: od_assign_anchors (the default rule and the yardstick) and
-od_assign_atss at topk = 9 on the same inputs -- B = 32 at 320^2 (P = 16 800) and B = 16 at 640^2 (P = 67 200), 8 and 64
-boxes per image, NC = 20 -- timed with device events, alternately, median over repetitions; and the training step at
-32 x 320^2 (bench.py's training workload: step(x, annotations) on a resident batch) under both assigners, so that the ATSS
-call is reported as a share of the default step.  Prints one JSON line.  (DESIGN.md "ATSS assignment")"""
+"""Time of the three prior-box assigners, in ONE process: od_assign_anchors (the default rule and the yardstick),
+od_assign_atss at topk = 9 and od_assign_tal at topk = 13 (on a random pred: logits N(0, 2), offsets N(0, 0.5)) on the same
+inputs -- B = 32 at 320^2 (P = 16 800) and B = 16 at 640^2 (P = 67 200), 8 and 64 boxes per image, NC = 20 -- timed with device
+events, alternately, median over repetitions; and the training step at 32 x 320^2 (bench.py's training workload:
+step(x, annotations) on a resident batch) under the three assigners: the ATSS call as a share of the default step, and the
+"tal" step, whose assignment sits between forward and loss, as a ratio of the default step.  `tal_prior_pass` gives the
+bytes od_tal_prior must read (B * P * (NC + 6) * 4) and their time at the HBM peak; the kernel's own time comes from a
+kernel trace of this script (--no-step).  Prints one JSON line.  (DESIGN.md "ATSS assignment", "Task-aligned assignment")"""
 import argparse
 import ctypes as C
 import json
@@ -25,7 +28,10 @@ def _boxes(rng, n):
     return np.clip(np.concatenate([c - wh / 2, c + wh / 2], 1), 0, 1).astype(np.float32)
 
 
-def measure_calls(size, B, G, a, dev, NC=20, topk=9):
+HBM_PEAK_TBS, HBM_COPY_TBS = 8.0, 6.29  # MI355X: specified peak, and what a float4 copy reaches
+
+
+def measure_calls(size, B, G, a, dev, NC=20, topk=9, tal_topk=13):
     from object_detector_amd import _lib, pb, priors as PR
     from object_detector_amd.net import Context
     ctx = Context.get(dev)
@@ -41,7 +47,11 @@ def measure_calls(size, B, G, a, dev, NC=20, topk=9):
     y = torch.empty((B, P, NC + 6), dtype=torch.float32, device=dev)
     asg = torch.empty((B, P), dtype=torch.int32, device=dev)
     npos = torch.empty((B,), dtype=torch.int32, device=dev)
-    nb = max(lib.od_assign_workspace_bytes(B, P, G), lib.od_assign_atss_workspace_bytes(B, P, G))
+    nb = max(lib.od_assign_workspace_bytes(B, P, G), lib.od_assign_atss_workspace_bytes(B, P, G),
+             lib.od_assign_tal_workspace_bytes(B, P, G))
+    pred = torch.from_numpy(np.concatenate([rng.normal(0, 2, (B, P, 2 + NC)), rng.normal(0, 0.5, (B, P, 4))], 2)
+                            .astype(np.float32)).to(dev)
+    metric = torch.empty((B, P), dtype=torch.float32, device=dev)
     ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -55,7 +65,13 @@ def measure_calls(size, B, G, a, dev, NC=20, topk=9):
                                       gn.data_ptr(), None, 0.0, topk, B, P, G, NC, pb.LOC_SCALE, y.data_ptr(), asg.data_ptr(),
                                       npos.data_ptr(), ws.data_ptr(), nb, st), "od_assign_atss")
 
-    fns = {"od_assign_anchors": max_iou, "od_assign_atss": atss}
+    def tal():
+        _lib.check(lib.od_assign_tal(h, pri.data_ptr(), grid_hw, len(levels), PR.NUM_PRIORS, pred.data_ptr(), gb.data_ptr(),
+                                     gc.data_ptr(), gn.data_ptr(), None, 0.0, pb.TAL_ALPHA, pb.TAL_BETA, tal_topk, B, P, G, NC,
+                                     pb.LOC_SCALE, y.data_ptr(), asg.data_ptr(), npos.data_ptr(), metric.data_ptr(),
+                                     ws.data_ptr(), nb, st), "od_assign_tal")
+
+    fns = {"od_assign_anchors": max_iou, "od_assign_atss": atss, "od_assign_tal": tal}
     times, pos = {k: [] for k in fns}, {}
     for k, fn in fns.items():
         for _ in range(a.warmup):
@@ -72,7 +88,11 @@ def measure_calls(size, B, G, a, dev, NC=20, topk=9):
             torch.cuda.synchronize()
             times[k].append(e0.elapsed_time(e1) * 1e3 / a.calls)
     us = {k: _median(v) for k, v in times.items()}
-    return {"workload": f"B {B} at {size}x{size} (P {P}), {G} boxes per image, NC {NC}, topk {topk}",
+    pred_bytes = B * P * (NC + 6) * 4
+    return {"workload": f"B {B} at {size}x{size} (P {P}), {G} boxes per image, NC {NC}, topk {topk} (atss) / {tal_topk} (tal)",
+            "tal_prior_pass": {"pred_bytes": pred_bytes, "us_at_hbm_peak": round(pred_bytes / HBM_PEAK_TBS * 1e-6, 2),
+                               "us_at_hbm_copy_rate": round(pred_bytes / HBM_COPY_TBS * 1e-6, 2)},
+            "tal_over_max_iou": round(us["od_assign_tal"] / us["od_assign_anchors"], 3),
             "us_per_call": {k: round(v, 2) for k, v in us.items()},
             "us_per_call_reps": {k: [round(t, 2) for t in v] for k, v in times.items()},
             "positives_per_image": pos,
@@ -89,7 +109,7 @@ def measure_step(size, batch, G, a, dev):
     x = torch.from_numpy(rng.integers(0, 256, (batch, size, size, 3), dtype=np.uint8)).to(dev)
     anns = [ObjectsAnnotation(None, size, size, rng.integers(0, 20, G), _boxes(rng, G)) for _ in range(batch)]
     trs = {k: Trainer(params, batch, (size, size), device=dev, lr=1e-3, momentum=0.9, loss_scale=1024.0, assigner=k)
-           for k in ("max-iou", "atss")}
+           for k in ("max-iou", "atss", "tal")}
 
     def window(tr, steps):
         torch.cuda.synchronize()
@@ -133,6 +153,7 @@ def main():
             out["320_b32_g8"]["us_per_call"]["od_assign_atss"] * 1e-3 / step["ms_per_step"]["max-iou"], 4)
         step["max_iou_call_share_of_max_iou_step"] = round(
             out["320_b32_g8"]["us_per_call"]["od_assign_anchors"] * 1e-3 / step["ms_per_step"]["max-iou"], 4)
+        step["tal_step_over_max_iou_step"] = round(step["ms_per_step"]["tal"] / step["ms_per_step"]["max-iou"], 4)
         out["train_320_b32"] = step
     print(json.dumps(out), flush=True)
 

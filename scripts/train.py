@@ -37,7 +37,8 @@ def build_parser():
     p.add_argument("--batch-size", default=32, type=int, help="per rank")
     p.add_argument("--steps", default=600, type=int)
     p.add_argument("--lr", default=None, type=float,
-                   help="peak learning rate (default 0.02 x global batch / 32: the linear scaling rule)")
+                   help="peak learning rate (default 0.02 x global batch / 32: the linear scaling rule; 0.005 x global batch / 32 "
+                        "with --assigner tal)")
     p.add_argument("--warmup", default=None, type=int,
                    help="linear warm-up steps (default 50 at a global batch of 32, 200 below it: measured -- 16 x 640^2 from "
                         "scratch diverges with 50 warm-up steps at lr 0.01-0.02 and trains with 200-300)")
@@ -61,10 +62,15 @@ def build_parser():
                    help="probability that a training image is a mosaic of four (od_augment_mosaic; off by default)")
     p.add_argument("--ignore-regions", action="store_true",
                    help="difficult / iscrowd boxes and the slivers a mosaic leaves are ignore regions instead of positives")
-    p.add_argument("--assigner", default="max-iou", choices=("max-iou", "atss"),
-                   help="the rule that gives priors to objects: fixed IoU thresholds (0.5 / 0.4) with a forced best match, or "
-                        "ATSS: the priors nearest to the object's centre on every level, IoU threshold = their mean + std")
+    p.add_argument("--assigner", default="max-iou", choices=("max-iou", "atss", "tal"),
+                   help="the rule that gives priors to objects: fixed IoU thresholds (0.5 / 0.4) with a forced best match; "
+                        "ATSS: the priors nearest to the object's centre on every level, IoU threshold = their mean + std; "
+                        "or TAL: the priors whose predicted score and predicted box agree best on the object (assigned behind "
+                        "the forward pass of every step)")
     p.add_argument("--atss-topk", default=9, type=int, metavar="K", help="--assigner atss: nearest cells per level (1..32)")
+    p.add_argument("--tal-topk", default=13, type=int, metavar="K", help="--assigner tal: positives per object (1..32)")
+    p.add_argument("--tal-alpha", default=1.0, type=float, metavar="A", help="--assigner tal: exponent of the score")
+    p.add_argument("--tal-beta", default=6.0, type=float, metavar="B", help="--assigner tal: exponent of the predicted box's IoU")
     p.add_argument("--shapes-difficult", default=0.0, type=float, help="--shapes: share of objects marked difficult")
     p.add_argument("--shapes-crowd", default=0.0, type=float, help="--shapes: share of images with a crowd region")
     p.add_argument("--prefetch", default=2, type=int, help="batches the generator thread runs ahead (0 = in the training thread)")
@@ -119,7 +125,9 @@ def _run(args):
     log = tk.log.get(__name__)
     rank, _local, world = tk.dl.dist_env()
     if args.lr is None:
-        args.lr = 0.02 * args.batch_size * world / 32.0
+        # "tal" assigns from the predictions, and its from-scratch run diverges at the rate the static assigners take; it
+        # trains at a quarter of it (DESIGN.md "Task-aligned assignment")
+        args.lr = (0.005 if args.assigner == "tal" else 0.02) * args.batch_size * world / 32.0
     if args.warmup is None:
         args.warmup = 50 if args.batch_size * world >= 32 else 200
     class_names = None
@@ -156,7 +164,7 @@ def _run(args):
     tr = Trainer(params, args.batch_size, tuple(args.input_size), device=dev, lr=args.lr, momentum=args.momentum,
                  weight_decay=args.weight_decay, comm=comm, world_size=world, lr_multipliers=mult, prior_wh=prior_wh, box_mode=args.box_loss,
                  ignore_regions=args.ignore_regions, loss_weights=(1.0, 1.0, args.box_weight), assigner=args.assigner,
-                 atss_topk=args.atss_topk,
+                 atss_topk=args.atss_topk, tal_topk=args.tal_topk, tal_alpha=args.tal_alpha, tal_beta=args.tal_beta,
                  **({} if args.ema is None else {"ema_decay": args.ema}))
     start, flow_seed = 0, args.seed + rank
     if args.resume is not None:
@@ -176,19 +184,36 @@ def _run(args):
         positives["sum"] += npos.sum()
         positives["images"] += len(anns)
         return target
-    gen =od_gen.create_generator(tuple(args.input_size), preprocess_input=None, encode_truth=encode_truth,
+    # "tal" assigns from the predictions: the generator yields the annotation lists themselves (encode_truth=None) and
+    # Trainer.step encodes behind its forward pass; the positives are then counted from tr.last_npos
+    tal = args.assigner == "tal"
+    gen =od_gen.create_generator(tuple(args.input_size), preprocess_input=None, encode_truth=None if tal else encode_truth,
                                   device=dev, on_device=True, device_cache=not args.no_device_cache, mosaic=args.mosaic,
                                   ignore_regions=args.ignore_regions)
     batches, per_epoch = gen.flow(X, y, batch_size=args.batch_size, data_augmentation=True, shuffle=True, seed=flow_seed,
                                   prefetch=args.prefetch)
     log.info(f"{n} images on rank {rank} of {world}, {per_epoch} steps per epoch, {args.steps} steps, lr {args.lr}, "
              f"multipliers {mult}")
+    pending = []  # "tal": batch sizes of issued steps whose tr.last_npos is not counted yet (at most one)
+
+    def count_last_step():
+        if pending and tr.last_npos is not None:
+            positives["sum"] += tr.last_npos.sum()
+            positives["images"] += pending.pop()
+
+    def counted(it):  # fit() asks for the next batch when the step on the last one has been issued
+        for xb, anns in it:
+            count_last_step()
+            pending.append(len(anns))
+            yield xb, anns
+    feed = counted(batches) if tal else batches
     t0 = time.perf_counter()
     schedule = cosine_schedule(args.lr, args.steps, args.warmup)
     hists, done = [], start
     while done < args.steps:  # one fit() for the whole run, or one per --save-state-every steps
         k = args.steps - done if args.save_state_every <= 0 else min(args.save_state_every, args.steps - done)
-        hists.append(tr.fit(batches, k, lr_schedule=schedule, log_every=args.log_every, log=log.info, start_step=done))
+        hists.append(tr.fit(feed, k, lr_schedule=schedule, log_every=args.log_every, log=log.info, start_step=done))
+        count_last_step()
         done += k
         if args.save_state_every > 0 and tk.dl.is_main_process():
             state = args.result_dir / "state.npz"
