@@ -119,8 +119,14 @@ int conv_describe(const od_ctx* ctx, const od_conv_desc* d, bool want_stats, od_
              "od_conv2d_fwd: tensor too large for 32-bit element offsets");
   p.HoWo = p.Ho * p.Wo;
   long long Mg = 0;
-  for (int i = 0; grouped && i < d->nseg; ++i) Mg += (long long)d->B * d->seg_H[i] * d->seg_W[i];
-  OD_REQUIRE(!grouped || Mg * d->Cout < (1LL << 31), "od_conv2d_fwd: grouped launch too large for 32-bit element offsets");
+  long long seg_x_max = 0;  // elements of the largest input map of a grouped launch (d->H / d->W are the first segment's only)
+  for (int i = 0; grouped && i < d->nseg; ++i) {
+    const long long Mi = (long long)d->B * d->seg_H[i] * d->seg_W[i];
+    Mg += Mi;
+    seg_x_max = seg_x_max > Mi * d->Cin ? seg_x_max : Mi * d->Cin;
+  }
+  OD_REQUIRE(!grouped || (Mg * d->Cout < (1LL << 31) && seg_x_max < (1LL << 31)),
+             "od_conv2d_fwd: grouped launch too large for 32-bit element offsets");
   p.M = grouped ? (int)Mg : (int)M64;
   p.nseg = grouped ? d->nseg : 0;
 
@@ -163,7 +169,9 @@ int conv_describe(const od_ctx* ctx, const od_conv_desc* d, bool want_stats, od_
   p.alpha2 = d->alpha2;
   p.K2stride = od_round_up(d->Cout, 64);
   p.w2_bytes = (unsigned)((long long)od_round_up(d->Cout2 > 0 ? d->Cout2 : 1, 256) * p.K2stride * 2);
-  p.x_bytes = (unsigned)((long long)d->B * d->H * d->W * d->Cin * 2);
+  // grouped: the extent of the LARGEST segment, so that what is decided on x_bytes (conv_choose_cfg, od_conv_8ph_select:
+  // 31-bit byte offsets) holds for every segment; the kernel takes each segment's own extent from the segment table
+  p.x_bytes = (unsigned)((grouped ? seg_x_max : (long long)d->B * d->H * d->W * d->Cin) * 2);
   p.w_bytes = (unsigned)((long long)od_round_up(d->Cout, 256) * p.Kstride * 2);
   p.obs = d->out_batch_stride ? d->out_batch_stride : (long long)p.HoWo * d->Cout;
   p.ops = d->out_pix_stride ? d->out_pix_stride : d->Cout;

@@ -204,6 +204,8 @@ extern "C" int od_topk_scores(od_ctx* ctx, const float* conf, int B, int N, int 
                               uint64_t* keys, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
   OD_REQUIRE(ctx && conf && keys && counts && workspace, "od_topk_scores: null argument");
   OD_REQUIRE(B > 0 && B <= 65535 && N > 0 && K > 0, "od_topk_scores: bad dims");
+  // the chunk walks step an int index past the end of their chunk (beg + chunk, i += 4096, i0 + 3 * 1024) before comparing it
+  OD_REQUIRE(N <= 0x7FFFFFFF - 16384, "od_topk_scores: N = %d too large for the 32-bit chunk walk", N);
   OD_REQUIRE(conf_threshold >= 0.f, "od_topk_scores: conf_threshold must be >= 0 (scores are probabilities)");
   const Layout l = ws_layout(B, N);
   if (workspace_bytes < l.total) {

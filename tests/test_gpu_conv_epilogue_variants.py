@@ -60,10 +60,12 @@ UNSPECIALISED_CASES = [(3, 10, 10, 64, 256, 3, 1, "elu", "same", NE8), (3, 10, 1
                        (3, 10, 10, 64, 200, 1, 1, None, "none", 7), (3, 10, 10, 64, 200, 3, 1, "leaky", "none", 5)]
 
 
-def expected_name(case, out_f32=False, act2=False):
-    """The kernel a case must resolve to: (regex on the full name, the (BM, BN) / MF1 bench.py reads from its head)."""
+def expected_name(case, out_f32=False, act2=False, off32=True):
+    """The kernel a case must resolve to: (regex on the full name, the (BM, BN) / MF1 bench.py reads from its head).
+    off32: whether every output offset of the launch fits 31 bits (conv_describe's p.off32); the compiled policies form
+    them in 32 bits, so a launch beyond that runs the run-time instantiation (tests/test_gpu_large_offsets.py)."""
     k, act, resm, cfg = case[5], case[7], case[8], case[9]
-    e = epi(act, resm, out_f32)
+    e = epi(act, resm, out_f32) if off32 else RT
     if cfg >= NE8:
         mf1 = 4 - (cfg - NE8)
         if act2 is not False:  # fused: 3x3 with leaky first epilogues has its instantiations, the 1x1 form runs the run-time one
