@@ -412,6 +412,39 @@ int od_loss_fwd_bwd(od_ctx* ctx, const float* pred, const float* y, float* grad,
 int od_loss_fwd_bwd_iou(od_ctx* ctx, const float* pred, const float* y, const float* priors, float* grad, float* losses,
                         int B, int P, int NC, float focal_alpha, float focal_gamma, int box_mode, float loc_scale,
                         float w_obj, float w_cls, float w_box, void* workspace, size_t workspace_bytes, void* stream);
+/* The same with a quality-aware objectness term [BUILD-DEFINED, opt-in]: quality f32 [B,P] holds q in [0,1] per prior (clamped
+ * on read, NaN = 0; read on assigned rows only; a constant in the gradient).  z = l1 - l0, p = sigmoid(z),
+ * CE = q * log(1 + e^-z) + (1 - q) * log(1 + e^z), a = focal_alpha on assigned rows:
+ *   obj_mode 0 (focal): quality is not read (may be NULL); the result is od_loss_fwd_bwd_iou's bit for bit.
+ *   obj_mode 1 (quality focal loss, Li et al. 2020; TOOD's classification loss): L = a * |q - p|^gamma * CE, focal_gamma >= 1.
+ *   obj_mode 2 (varifocal loss, Zhang et al. 2021): assigned rows with q > 0 take L = q * CE; assigned rows with q == 0 take
+ *     focal's background term, (1 - focal_alpha) included.
+ * Background rows take focal's background term in every mode, bit for bit; ignore rows add nothing; class and box terms, the
+ * normaliser max(1, #assigned), the workspace and the non-finite rule (a NaN / Inf objectness logit of a non-ignored row makes
+ * its gradient and losses[3] non-finite) are od_loss_fwd_bwd_iou's. */
+int od_loss_fwd_bwd_quality(od_ctx* ctx, const float* pred, const float* y, const float* priors, float* grad, float* losses,
+                            int B, int P, int NC, float focal_alpha, float focal_gamma, int box_mode, float loc_scale,
+                            float w_obj, float w_cls, float w_box, const float* quality, int obj_mode, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* K10b: quality targets for od_loss_fwd_bwd_quality (csrc/quality.hip; the frozen rules are its header comment, restated by
+ * tests/quality_ref.py).  q f32 [B,P]: one number in [0,1] per assigned prior (y[..., 1] > 0.5), 0 on every other row.
+ * pbox = od_decode_locs of the row's predicted offsets (no clip, corners sorted; a non-finite coordinate gives IoU 0).
+ * pred, priors 16-byte aligned; 1 <= NC <= 1024.
+ *   od_quality_iou: q = IoU(decoded target box of the row, pbox).  Works behind any assigner and on a ready-made target.
+ *   od_quality_tal: TOOD's normalised alignment metric, behind od_assign_tal (its gt_boxes [B,Gmax,4], assigned_gt [B,P] and
+ *     metric [B,P]).  u = IoU(gt box of the row's object, pbox).  A row is aligned iff metric < 0; per object lmax / umax are
+ *     the maxima of metric / u over its aligned rows; aligned rows get q = exp(metric - lmax) * umax, forced rows (metric = 0)
+ *     q = max(u, IoU(gt box, prior)).  An assigned row whose assigned_gt lies outside 0..Gmax-1 reads no box and gets q = 0;
+ *     od_assign_tal never writes one (its owners are box indices below min(gt_counts, Gmax)), so this only guards buffers
+ *     from elsewhere.  Order-independent: two calls give the same bytes.  The workspace
+ *     (od_quality_tal_workspace_bytes = 8 bytes per (image, box slot), 4-byte aligned) may arrive dirty. */
+int od_quality_iou(od_ctx* ctx, const float* pred, const float* y, const float* priors, float loc_scale, int B, int P, int NC,
+                   float* q, void* stream);
+size_t od_quality_tal_workspace_bytes(int B, int Gmax);
+int od_quality_tal(od_ctx* ctx, const float* pred, const float* y, const float* priors, float loc_scale, const float* gt_boxes,
+                   const int32_t* assigned_gt, const float* metric, int B, int P, int Gmax, int NC, float* q, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K11/K12: training-side kernels (the Keras fit() machinery behind tk.dl.od.ObjectDetector: Conv2D backward,

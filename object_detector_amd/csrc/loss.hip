@@ -1,6 +1,7 @@
 // K10: detection loss, forward + gradient w.r.t. the prediction tensor, in one elementwise pass (HBM-bound).
 // reference docs/MODEL.md:33-52:
-//   objectness : 2-class focal loss (alpha_t, gamma)                    [:33-37]
+//   objectness : 2-class focal loss (alpha_t, gamma)                    [:33-37];
+//                through od_loss_fwd_bwd_quality also quality focal / varifocal loss towards soft targets (od_loss_obj_box)
 //   class      : softmax + categorical cross-entropy on assigned priors [:39-44]
 //   box        : MSE (doc mode) or smooth-L1 (north_star mode) on the corner-form offsets, assigned priors only [:46-52];
 //                through od_loss_fwd_bwd_iou also 1 - GIoU / DIoU / CIoU of the DECODED boxes (od_iou_box below)
@@ -69,6 +70,8 @@ struct od_iou_args {
   const float* priors;  // f32 [P,4]; row r of pred belongs to prior r % P
   int P;
   float loc_scale;
+  const float* quality;  // f32 [B*P]: read by assigned rows of a QUAL instantiation only (od_loss_fwd_bwd_quality)
+  int obj_mode;          // 1 = quality focal loss, 2 = varifocal loss (QUAL instantiations)
 };
 
 constexpr float OD_IOU_EPS = 1e-9f;
@@ -137,8 +140,18 @@ __device__ __forceinline__ float od_iou_box(const float* p, const float* t, f32x
 // row (g may be p: every column is read before it is written).  Writes g[0], g[1] and g[2+NC .. 2+NC+3], sets l_obj, adds the
 // four box terms to l_box.  The one copy of this arithmetic, for od_loss_rows and od_loss_rows_wide.  IOU (box modes 2..4) is
 // a compile-time property, so that the smooth-L1 / MSE instantiations keep their code and registers; `row` = the row's
-// index in [0, B*P), `ia` the prior table: both are looked at by assigned rows of an IOU instantiation only.
-template <bool IOU>
+// index in [0, B*P), `ia` the prior table: both are looked at by assigned rows of an IOU or QUAL instantiation only.
+//
+// QUAL (od_loss_fwd_bwd_quality, obj_mode 1 | 2) is a compile-time property as well: the assigned rows' objectness target is
+// the row's quality q = clamp(quality[row], 0, 1) (NaN -> 0), a constant in the gradient.  z = l1 - l0, p = sigmoid(z),
+// sp(t) = log(1 + e^t), CE = q * sp(-z) + (1 - q) * sp(z) (both terms >= 0):
+//   1 (QFL, Li et al. 2020):      L = alpha * |q - p|^gamma * CE,  gamma >= 1;
+//                                 dL/dz = alpha * (gamma * d^(gamma-1) * sgn(p - q) * p * (1 - p) * CE + d^gamma * (p - q)), d = |p - q|
+//   2 (varifocal, Zhang et al. 2021): q > 0: L = q * CE, dL/dz = q * (p - q);  q == 0: focal's background term (1 - alpha included)
+// p, 1 - p and the two sp come from e = exp(-|z|) as in the focal term; p - q is the one difference the definition forces, taken
+// as (1 - q) - (1 - p) where p > 1/2, so that q = 1 on a saturated row gives -(1 - p) exactly.  Background rows run the focal
+// arithmetic below unchanged, in every mode.
+template <bool IOU, bool QUAL = false>
 __device__ __forceinline__ void od_loss_obj_box(const float* p, const float* t, float* g, int NC, float alpha, float gamma,
                                                 int box_mode, float w_obj, float w_box, float invn, long long row,
                                                 const od_iou_args& ia, float& l_obj, float& l_box) {
@@ -146,8 +159,39 @@ __device__ __forceinline__ void od_loss_obj_box(const float* p, const float* t, 
   const float l0 = p[0], l1 = p[1];  // read beside the targets, not behind the branch on them: one load latency, not two
   const bool pos = t1 > 0.5f;
   float g1 = 0.f;
-  if (t0 + t1 > 0.f) {
-    const float x = pos ? l0 - l1 : l1 - l0;  // l_other - l_t: p_t = 1 / (1 + exp(x))
+  bool soft = false;  // an assigned row of a QUAL instantiation that takes a quality term
+  float q = 0.f;
+  if constexpr (QUAL) {
+    if (pos) {
+      q = fminf(fmaxf(ia.quality[row], 0.f), 1.f);  // fmaxf drops a NaN
+      soft = ia.obj_mode == 1 || q > 0.f;
+    }
+  }
+  // the focal term's view of the row: an assigned row of a QUAL instantiation that is not soft (varifocal, q == 0) is background
+  const bool fpos = QUAL ? false : pos;
+  if (soft) {
+    const float x = l0 - l1;   // -z
+    const float nf = x * 0.f;  // 0, or NaN for a non-finite logit
+    const float e = expf(-fabsf(x));
+    const float inv = __builtin_amdgcn_rcpf(1.f + e);
+    const float pp = (x > 0.f ? e : 1.f) * inv;  // p
+    const float om = (x > 0.f ? 1.f : e) * inv;  // 1 - p, without the subtraction
+    const float l1p = od_log1p_unit(e);
+    const float ce = q * (fmaxf(x, 0.f) + l1p) + (1.f - q) * (fmaxf(-x, 0.f) + l1p);  // q * sp(-z) + (1 - q) * sp(z)
+    const float pmq = x > 0.f ? pp - q : (1.f - q) - om;
+    if (ia.obj_mode == 1) {
+      const float d = fabsf(pmq);
+      const float dg = gamma == 2.f ? d * d : powf(d, gamma);
+      const float dg1 = gamma == 2.f ? d : powf(d, gamma - 1.f);  // powf(0, 0) = 1, and sgn(0) = 0 beside it
+      const float sg = pmq > 0.f ? 1.f : (pmq < 0.f ? -1.f : 0.f);
+      l_obj = alpha * dg * ce + nf;
+      g1 = alpha * (gamma * dg1 * sg * (pp * om) * ce + dg * pmq) + nf;
+    } else {
+      l_obj = q * ce + nf;
+      g1 = q * pmq + nf;
+    }
+  } else if (t0 + t1 > 0.f) {
+    const float x = fpos ? l0 - l1 : l1 - l0;  // l_other - l_t: p_t = 1 / (1 + exp(x))
     const float nf = x * 0.f;                 // 0, or NaN for a non-finite logit
     const float e = expf(-fabsf(x));
     // v_rcp_f32 (1 ulp) for the two quotients: the thread's dependent chain, not the HBM traffic, is what this kernel waits
@@ -156,14 +200,14 @@ __device__ __forceinline__ void od_loss_obj_box(const float* p, const float* t, 
     const float pt = (x > 0.f ? e : 1.f) * inv;
     const float om = (x > 0.f ? 1.f : e) * inv;  // 1 - p_t, without the subtraction
     const float lpt = -(fmaxf(x, 0.f) + od_log1p_unit(e));
-    const float a = pos ? alpha : 1.f - alpha;
+    const float a = fpos ? alpha : 1.f - alpha;
     const float mod = gamma == 2.f ? om * om : powf(om, gamma);  // powf(0, 0) = 1
     // log p_t / (1 - p_t) = -(1 + om/2 + om^2/3 + ...): -1 to the last bit below 2^-24 (and 1 / om stays finite above it)
     const float ratio = om > 0x1p-24f ? lpt * __builtin_amdgcn_rcpf(om) : -1.f;
     l_obj = -a * mod * lpt + nf;
     // d loss / d log p_t = -a * mod * (1 - gamma * pt * ratio);  d log p_t / d l_t = om, d log p_t / d l_other = -om
     const float gt = -a * mod * (1.f - gamma * pt * ratio) * om + nf;
-    g1 = pos ? gt : -gt;
+    g1 = fpos ? gt : -gt;
   }
   g[0] = -g1 * w_obj * invn;
   g[1] = g1 * w_obj * invn;
@@ -245,7 +289,7 @@ __device__ __forceinline__ float od_cls_grad(const od_cls_row& r, int c, float v
   return c == r.imax ? (t == 1.f ? r.q1m1 : r.q1 - t) : expf(lq) - t;
 }
 
-template <bool IOU>
+template <bool IOU, bool QUAL>
 __global__ __launch_bounds__(256) void od_loss_rows(const float* __restrict__ pred, const float* __restrict__ y,
                                                     float* __restrict__ grad, long long R, int NC, float alpha,
                                                     float gamma, int box_mode, float w_obj, float w_cls, float w_box,
@@ -276,7 +320,7 @@ __global__ __launch_bounds__(256) void od_loss_rows(const float* __restrict__ pr
   if (tid < nrows) {
     float* p = sp + tid * C;
     const float* t = sy + tid * C;
-    od_loss_obj_box<IOU>(p, t, p, NC, alpha, gamma, box_mode, w_obj, w_box, invn, r0 + tid, ia, l_obj, l_box);
+    od_loss_obj_box<IOU, QUAL>(p, t, p, NC, alpha, gamma, box_mode, w_obj, w_box, invn, r0 + tid, ia, l_obj, l_box);
     if (t[1] > 0.5f) {
       od_cls_row cr;
       for (int c = 0; c < NC; ++c) od_cls_max(cr, c, p[2 + c]);
@@ -321,7 +365,7 @@ __device__ __forceinline__ void od_loss_stage(const float* __restrict__ src, int
   }
 }
 
-template <bool IOU>
+template <bool IOU, bool QUAL>
 __global__ __launch_bounds__(256) void od_loss_rows_wide(const float* __restrict__ pred, const float* __restrict__ y,
                                                          float* __restrict__ grad, long long R, int NC, float alpha,
                                                          float gamma, int box_mode, float w_obj, float w_cls, float w_box,
@@ -341,7 +385,7 @@ __global__ __launch_bounds__(256) void od_loss_rows_wide(const float* __restrict
   if (tid < nrows) {
     const float* t = yb + (long long)tid * C;
     pos = t[1] > 0.5f;
-    od_loss_obj_box<IOU>(pb + (long long)tid * C, t, gb + (long long)tid * C, NC, alpha, gamma, box_mode, w_obj, w_box,
+    od_loss_obj_box<IOU, QUAL>(pb + (long long)tid * C, t, gb + (long long)tid * C, NC, alpha, gamma, box_mode, w_obj, w_box,
                          invn, r0 + tid, ia, l_obj, l_box);
   }
   // ---- class: softmax cross-entropy on assigned rows; zero gradient elsewhere ----
@@ -431,19 +475,19 @@ extern "C" size_t od_loss_workspace_bytes(int B, int P) {
 
 namespace {
 
-template <bool IOU>
+template <bool IOU, bool QUAL>
 int od_loss_launch(od_ctx* ctx, const float* pred, const float* y, float* grad, float* losses, long long R, int NC,
                    float focal_alpha, float focal_gamma, int box_mode, float w_obj, float w_cls, float w_box, int* npos,
                    float* partials, od_iou_args ia, hipStream_t s) {
   const int nblocks = (int)((R + LROWS - 1) / LROWS);
   if (NC > LMAX_LDS_NC) {
-    hipLaunchKernelGGL(od_loss_rows_wide<IOU>, dim3(nblocks), dim3(256), 0, s, pred, y, grad, R, NC, focal_alpha,
+    hipLaunchKernelGGL((od_loss_rows_wide<IOU, QUAL>), dim3(nblocks), dim3(256), 0, s, pred, y, grad, R, NC, focal_alpha,
                        focal_gamma, box_mode, w_obj, w_cls, w_box, npos, partials, ia);
     OD_CHECK_LAUNCH();
   } else {
     const size_t lds = (size_t)2 * LROWS * (NC + 6) * sizeof(float);
-    if (int rc = od_ensure_lds(ctx, (const void*)&od_loss_rows<IOU>, lds)) return rc;
-    hipLaunchKernelGGL(od_loss_rows<IOU>, dim3(nblocks), dim3(256), lds, s, pred, y, grad, R, NC, focal_alpha, focal_gamma,
+    if (int rc = od_ensure_lds(ctx, (const void*)&od_loss_rows<IOU, QUAL>, lds)) return rc;
+    hipLaunchKernelGGL((od_loss_rows<IOU, QUAL>), dim3(nblocks), dim3(256), lds, s, pred, y, grad, R, NC, focal_alpha, focal_gamma,
                        box_mode, w_obj, w_cls, w_box, npos, partials, ia);
     OD_CHECK_LAUNCH();
   }
@@ -452,10 +496,11 @@ int od_loss_launch(od_ctx* ctx, const float* pred, const float* y, float* grad, 
   return OD_OK;
 }
 
-// Both entry points: `fn` names the caller in error messages.
+// All entry points: `fn` names the caller in error messages.  obj_mode 0 (focal) never looks at `quality`.
 int od_loss_run(const char* fn, od_ctx* ctx, const float* pred, const float* y, const float* priors, float* grad,
                 float* losses, int B, int P, int NC, float focal_alpha, float focal_gamma, int box_mode, float loc_scale,
-                float w_obj, float w_cls, float w_box, void* workspace, size_t workspace_bytes, void* stream) {
+                float w_obj, float w_cls, float w_box, void* workspace, size_t workspace_bytes, void* stream,
+                const float* quality = nullptr, int obj_mode = 0) {
   OD_REQUIRE(ctx && pred && y && grad && losses && workspace, "%s: null argument", fn);
   OD_REQUIRE(NC >= 1 && NC <= 1024, "%s: NC = %d outside the supported class counts 1..1024", fn, NC);
   OD_REQUIRE(B > 0 && P > 0, "%s: bad dims", fn);
@@ -478,11 +523,14 @@ int od_loss_run(const char* fn, od_ctx* ctx, const float* pred, const float* y, 
   if (cb > 2048) cb = 2048;
   hipLaunchKernelGGL(od_loss_count, dim3(cb), dim3(256), 0, s, y, R, NC + 6, npos);
   OD_CHECK_LAUNCH();
-  const od_iou_args ia = {iou ? priors : nullptr, P, loc_scale};
-  return iou ? od_loss_launch<true>(ctx, pred, y, grad, losses, R, NC, focal_alpha, focal_gamma, box_mode, w_obj, w_cls,
-                                    w_box, npos, partials, ia, s)
-             : od_loss_launch<false>(ctx, pred, y, grad, losses, R, NC, focal_alpha, focal_gamma, box_mode, w_obj, w_cls,
-                                     w_box, npos, partials, ia, s);
+  const bool qual = obj_mode != 0;
+  const od_iou_args ia = {iou ? priors : nullptr, P, loc_scale, qual ? quality : nullptr, obj_mode};
+#define OD_LOSS_LAUNCH(IOU_, QUAL_)                                                                                     \
+  od_loss_launch<IOU_, QUAL_>(ctx, pred, y, grad, losses, R, NC, focal_alpha, focal_gamma, box_mode, w_obj, w_cls, w_box, \
+                              npos, partials, ia, s)
+  if (qual) return iou ? OD_LOSS_LAUNCH(true, true) : OD_LOSS_LAUNCH(false, true);
+  return iou ? OD_LOSS_LAUNCH(true, false) : OD_LOSS_LAUNCH(false, false);
+#undef OD_LOSS_LAUNCH
 }
 
 }  // namespace
@@ -501,4 +549,18 @@ extern "C" int od_loss_fwd_bwd(od_ctx* ctx, const float* pred, const float* y, f
   OD_REQUIRE(box_mode == 0 || box_mode == 1, "od_loss_fwd_bwd: box_mode 0 = smooth-L1, 1 = MSE");
   return od_loss_run("od_loss_fwd_bwd", ctx, pred, y, nullptr, grad, losses, B, P, NC, focal_alpha, focal_gamma, box_mode, 0.f,
                      w_obj, w_cls, w_box, workspace, workspace_bytes, stream);
+}
+
+extern "C" int od_loss_fwd_bwd_quality(od_ctx* ctx, const float* pred, const float* y, const float* priors, float* grad,
+                                       float* losses, int B, int P, int NC, float focal_alpha, float focal_gamma,
+                                       int box_mode, float loc_scale, float w_obj, float w_cls, float w_box,
+                                       const float* quality, int obj_mode, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  const char* fn = "od_loss_fwd_bwd_quality";
+  OD_REQUIRE(obj_mode >= 0 && obj_mode <= 2, "%s: obj_mode 0 = focal, 1 = quality focal (qfl), 2 = varifocal (vfl)", fn);
+  OD_REQUIRE(obj_mode == 0 || quality, "%s: obj_mode %d needs the quality targets", fn, obj_mode);
+  OD_REQUIRE(obj_mode != 1 || focal_gamma >= 1.f,
+             "%s: qfl needs focal_gamma >= 1 (got %g): below 1 the gradient is unbounded at p = q", fn, (double)focal_gamma);
+  return od_loss_run(fn, ctx, pred, y, priors, grad, losses, B, P, NC, focal_alpha, focal_gamma, box_mode, loc_scale, w_obj,
+                     w_cls, w_box, workspace, workspace_bytes, stream, quality, obj_mode);
 }

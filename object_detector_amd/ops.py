@@ -155,12 +155,79 @@ def check_box_mode(box_mode, priors, num_priors):
             raise ValueError(f"priors {tuple(priors.shape)} do not match the {num_priors} rows per image of pred")
 
 
+OBJ_MODES = {"focal": 0, "qfl": 1, "vfl": 2}  # od_loss_fwd_bwd_quality's obj_mode
+QUALITY_MODES = ("iou", "tal")
+
+
+def check_objectness(objectness, quality, gamma, rows_shape):
+    """The argument rules of loss_fwd_bwd's objectness term (no device needed): a known name; a soft mode ("qfl" | "vfl")
+    needs quality of shape `rows_shape` = pred.shape[:-1]; "qfl" needs gamma >= 1 (below 1 its gradient is unbounded at
+    p = q)."""
+    if objectness not in OBJ_MODES:
+        raise ValueError(f"objectness must be one of {sorted(OBJ_MODES)}, got {objectness!r}")
+    if objectness == "focal":
+        return
+    if quality is None:
+        raise ValueError(f"objectness {objectness!r} needs quality=<f32 {list(rows_shape)} device tensor> (ops.quality_targets)")
+    if tuple(quality.shape) != tuple(rows_shape):
+        raise ValueError(f"quality {tuple(quality.shape)} does not match the rows {tuple(rows_shape)} of pred")
+    if objectness == "qfl" and not float(gamma) >= 1.0:
+        raise ValueError(f'objectness "qfl" needs gamma >= 1, got {gamma!r}')
+
+
+def check_quality_mode(mode, assigned=None, metric=None, gt_boxes=None):
+    """The argument rules of quality_targets (no device needed): a known mode, and for "tal" the three tensors of the
+    task-aligned assignment (assigned [B,P] i32, metric [B,P] f32, gt_boxes [B,Gmax,4] f32)."""
+    if mode not in QUALITY_MODES:
+        raise ValueError(f"quality mode must be one of {QUALITY_MODES}, got {mode!r}")
+    if mode == "tal":
+        missing = [n for n, v in (("assigned", assigned), ("metric", metric), ("gt_boxes", gt_boxes)) if v is None]
+        if missing:
+            raise ValueError(f'quality mode "tal" needs assigned=, metric= and gt_boxes= of the od_assign_tal call '
+                             f'(missing: {", ".join(missing)})')
+
+
+def quality_targets(pred: torch.Tensor, y: torch.Tensor, priors: torch.Tensor, loc_scale=0.1, mode="iou", assigned=None,
+                    metric=None, gt_boxes=None, out: torch.Tensor | None = None):
+    """pred, y f32 [B,P,2+NC+4], priors f32 [P,4] -> q f32 [B,P] in [0,1] on assigned rows, 0 elsewhere   (K10b)
+    mode "iou": IoU of the row's decoded target box and its decoded predicted box (od_quality_iou).
+    mode "tal": TOOD's normalised alignment metric from the outputs of the task-aligned assignment of THIS pred: `assigned`
+    i32 [B,P], `metric` f32 [B,P] (PriorBoxes.last_metric), `gt_boxes` f32 [B,Gmax,4] (od_quality_tal)."""
+    check_quality_mode(mode, assigned, metric, gt_boxes)
+    ctx = _ctx(pred)
+    assert pred.dtype == torch.float32 and y.dtype == torch.float32 and pred.is_contiguous() and y.is_contiguous()
+    assert priors.dtype == torch.float32 and priors.is_contiguous() and priors.device == pred.device
+    B, P, Cc = pred.shape
+    assert y.shape == pred.shape and tuple(priors.shape) == (P, 4)
+    q = torch.empty((B, P), dtype=torch.float32, device=pred.device) if out is None else out
+    assert q.dtype == torch.float32 and tuple(q.shape) == (B, P) and q.is_contiguous()
+    if mode == "iou":
+        _lib.check(ctx.lib.od_quality_iou(ctx.handle, pred.data_ptr(), y.data_ptr(), priors.data_ptr(), float(loc_scale), B, P,
+                                          Cc - 6, q.data_ptr(), _stream_ptr()), "od_quality_iou")
+        return q
+    assert assigned.dtype == torch.int32 and tuple(assigned.shape) == (B, P) and assigned.is_contiguous()
+    assert metric.dtype == torch.float32 and tuple(metric.shape) == (B, P) and metric.is_contiguous()
+    assert gt_boxes.dtype == torch.float32 and gt_boxes.dim() == 3 and gt_boxes.shape[0] == B and gt_boxes.shape[2] == 4 \
+        and gt_boxes.is_contiguous()
+    gmax = gt_boxes.shape[1]
+    wsb = ctx.lib.od_quality_tal_workspace_bytes(B, gmax)
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=pred.device)
+    _lib.check(ctx.lib.od_quality_tal(ctx.handle, pred.data_ptr(), y.data_ptr(), priors.data_ptr(), float(loc_scale),
+                                      gt_boxes.data_ptr(), assigned.data_ptr(), metric.data_ptr(), B, P, gmax, Cc - 6,
+                                      q.data_ptr(), ws.data_ptr(), wsb, _stream_ptr()), "od_quality_tal")
+    return q
+
+
 def loss_fwd_bwd(pred: torch.Tensor, y: torch.Tensor, num_classes=20, alpha=0.25, gamma=2.0, box_mode="smooth_l1",
-                 weights=(1.0, 1.0, 1.0), priors: torch.Tensor | None = None, loc_scale=0.1):
+                 weights=(1.0, 1.0, 1.0), priors: torch.Tensor | None = None, loc_scale=0.1, objectness="focal",
+                 quality: torch.Tensor | None = None):
     """pred, y f32 [B,P,2+NC+4] -> (losses f32 [4] = obj, cls, box, total ; grad f32 like pred)   (K10)
     box_mode "giou" | "diou" | "ciou": 1 - IoU metric of the boxes decoded from the loc columns with `priors` (f32 [P,4] on
-    pred's device) and `loc_scale`; "smooth_l1" | "mse" read neither."""
+    pred's device) and `loc_scale`; "smooth_l1" | "mse" read neither.
+    objectness "qfl" | "vfl": quality focal / varifocal loss towards `quality` (f32 [B,P], quality_targets) on the assigned
+    rows (od_loss_fwd_bwd_quality); "focal" (the default) is od_loss_fwd_bwd_iou and reads no quality."""
     check_box_mode(box_mode, priors, pred.shape[-2])
+    check_objectness(objectness, quality, gamma, pred.shape[:-1])
     ctx = _ctx(pred)
     assert pred.dtype == torch.float32 and y.dtype == torch.float32 and pred.is_contiguous() and y.is_contiguous()
     B, P, Cc = pred.shape
@@ -173,6 +240,15 @@ def loss_fwd_bwd(pred: torch.Tensor, y: torch.Tensor, num_classes=20, alpha=0.25
     losses = torch.empty((4,), dtype=torch.float32, device=pred.device)
     wsb = ctx.lib.od_loss_workspace_bytes(B, P)
     ws = torch.empty((wsb,), dtype=torch.uint8, device=pred.device)
+    if objectness != "focal":
+        assert quality.dtype == torch.float32 and quality.is_contiguous() and quality.device == pred.device
+        _lib.check(ctx.lib.od_loss_fwd_bwd_quality(ctx.handle, pred.data_ptr(), y.data_ptr(), pr_ptr, grad.data_ptr(),
+                                                   losses.data_ptr(), B, P, num_classes, float(alpha), float(gamma),
+                                                   BOX_MODES[box_mode], float(loc_scale), float(weights[0]),
+                                                   float(weights[1]), float(weights[2]), quality.data_ptr(),
+                                                   OBJ_MODES[objectness], ws.data_ptr(), wsb, _stream_ptr()),
+                   "od_loss_fwd_bwd_quality")
+        return losses, grad
     _lib.check(ctx.lib.od_loss_fwd_bwd_iou(ctx.handle, pred.data_ptr(), y.data_ptr(), pr_ptr, grad.data_ptr(),
                                            losses.data_ptr(), B, P, num_classes, float(alpha), float(gamma),
                                            BOX_MODES[box_mode], float(loc_scale), float(weights[0]), float(weights[1]),

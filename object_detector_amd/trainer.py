@@ -19,8 +19,8 @@ import torch
 
 from . import _lib, desc, weights as W
 from .net import Context, _stream_ptr
-from .ops import BOX_MODES
-from .pb import ATSS_TOPK, TAL_ALPHA, TAL_BETA, TAL_TOPK, PriorBoxes, check_assigner, check_tal
+from .ops import BOX_MODES, OBJ_MODES, QUALITY_MODES
+from .pb import ATSS_TOPK, GMAX, TAL_ALPHA, TAL_BETA, TAL_TOPK, PriorBoxes, check_assigner, check_tal
 
 BN_MOMENTUM = 0.99  # Keras default
 
@@ -62,7 +62,7 @@ class Trainer:
                  head_act=("elu", 1.0), comm=None, world_size=1, grad_payload=None, dynamic_loss_scale=True,
                  lr_multipliers=None, prior_wh=None, ignore_regions=False, ign_thr=None, loss_weights=(1.0, 1.0, 1.0),
                  ema_decay=None, ema_warmup=True, assigner="max-iou", atss_topk=ATSS_TOPK, tal_topk=TAL_TOPK,
-                 tal_alpha=TAL_ALPHA, tal_beta=TAL_BETA):
+                 tal_alpha=TAL_ALPHA, tal_beta=TAL_BETA, objectness="focal", quality="iou"):
         # ema_decay: None = no averaged model (no extra buffers, sgd() launches od_sgd_step_multi); 0 < ema_decay < 1 keeps
         # an exponential moving average of the masters (self.ema) and of the BatchNorm running statistics
         # (self.ema_run_stats), updated inside sgd() with the decay ema_decay_at(self.ema_updates, ema_decay, ema_warmup)
@@ -72,6 +72,11 @@ class Trainer:
         self.ema_warmup = bool(ema_warmup)
         check_assigner(assigner, atss_topk)  # a bad assigner fails here, before the device is touched
         check_tal(tal_topk, tal_alpha, tal_beta)
+        # objectness "qfl" | "vfl": quality focal / varifocal loss towards the quality targets of `quality` ("iou": IoU of the
+        # decoded target and predicted boxes, behind any assigner; "tal": TOOD's normalised metric, assigner="tal" only),
+        # computed between the forward pass (and the TAL encode) and the loss; "focal" keeps hard targets and launches nothing
+        check_objectness_args(objectness, quality, assigner)
+        self.objectness, self.quality = objectness, quality
         self.ctx = Context.get(device)
         self.lib = self.ctx.lib
         self.device = torch.device(device)
@@ -195,6 +200,12 @@ class Trainer:
         self.last_npos = None  # positives per image [B] (device, i32) of the last step that encoded annotations
         self.last_target = None  # the target [B,P,C] the last step's loss was taken on (device; the caller's y_target or the encode's)
         self.loss_ws = torch.empty(self.lib.od_loss_workspace_bytes(self.B, self.P), dtype=torch.uint8, device=dev)
+        # quality targets [B,P] of the last step (objectness "qfl" | "vfl"); focal keeps no buffer
+        self.last_quality = (torch.zeros((self.B, self.P), dtype=torch.float32, device=dev) if objectness != "focal"
+                             else None)
+        # od_quality_tal's two [B,Gmax] tables, for the largest Gmax an upload can have
+        self.quality_ws = (torch.empty(self.lib.od_quality_tal_workspace_bytes(self.B, GMAX), dtype=torch.uint8, device=dev)
+                           if objectness != "focal" and quality == "tal" else None)
         mx = max(n.M * n.Cout for n in self.nodes)
         # dz of the node being processed: three rotating buffers, because the weight gradient of node k runs on a second
         # stream while the main stream already computes node k-1's dz (backward())
@@ -416,9 +427,42 @@ class Trainer:
                        "od_scale_act")
         return self.pred
 
-    def loss(self, y_target):
-        """pred (from forward) + targets f32 [B,P,C] -> losses [4] on device; fills grad_pred."""
+    def quality_targets(self, y_target, tal_inputs=None):
+        """pred (from forward) + targets f32 [B,P,C] -> self.last_quality f32 [B,P] (objectness "qfl" | "vfl"), on the current
+        stream: od_quality_iou, or with quality="tal" od_quality_tal on tal_inputs = (gt_boxes f32 [B,Gmax,4], assigned_gt i32
+        [B,P]) of the od_assign_tal call that made y_target from THIS pred, and self.pb.last_metric."""
+        h, q, s = self.ctx.handle, self.last_quality, _stream_ptr()
+        if self.quality == "tal":
+            if tal_inputs is None:
+                raise ValueError('quality="tal" needs tal_inputs=(gt_boxes, assigned_gt) of the task-aligned assignment of '
+                                 'this pred; step(x, annotations=...) passes them')
+            gb, assigned = tal_inputs
+            _lib.check(self.lib.od_quality_tal(h, self.pred.data_ptr(), y_target.data_ptr(), self.pb.priors_device.data_ptr(),
+                                               self.pb.loc_scale, gb.data_ptr(), assigned.data_ptr(),
+                                               self.pb.last_metric.data_ptr(), self.B, self.P, gb.shape[1], self.num_classes,
+                                               q.data_ptr(), self.quality_ws.data_ptr(), self.quality_ws.numel(), s),
+                       "od_quality_tal")
+        else:
+            _lib.check(self.lib.od_quality_iou(h, self.pred.data_ptr(), y_target.data_ptr(), self.pb.priors_device.data_ptr(),
+                                               self.pb.loc_scale, self.B, self.P, self.num_classes, q.data_ptr(), s),
+                       "od_quality_iou")
+        return q
+
+    def loss(self, y_target, tal_inputs=None):
+        """pred (from forward) + targets f32 [B,P,C] -> losses [4] on device; fills grad_pred.  objectness "qfl" | "vfl":
+        the quality targets of this pred and y_target are computed first (quality_targets; quality="tal" needs tal_inputs)
+        and stay in self.last_quality."""
         w = self.loss_weights
+        if self.objectness != "focal":
+            self.quality_targets(y_target, tal_inputs)
+            _lib.check(self.lib.od_loss_fwd_bwd_quality(self.ctx.handle, self.pred.data_ptr(), y_target.data_ptr(),
+                                                        self.pb.priors_device.data_ptr(), self.grad_pred.data_ptr(),
+                                                        self.losses.data_ptr(), self.B, self.P, self.num_classes, 0.25, 2.0,
+                                                        BOX_MODES[self.box_mode], self.pb.loc_scale, w[0], w[1], w[2],
+                                                        self.last_quality.data_ptr(), OBJ_MODES[self.objectness],
+                                                        self.loss_ws.data_ptr(), self.loss_ws.numel(), _stream_ptr()),
+                       "od_loss_fwd_bwd_quality")
+            return self.losses
         _lib.check(self.lib.od_loss_fwd_bwd_iou(self.ctx.handle, self.pred.data_ptr(), y_target.data_ptr(),
                                                 self.pb.priors_device.data_ptr(), self.grad_pred.data_ptr(),
                                                 self.losses.data_ptr(), self.B, self.P, self.num_classes, 0.25, 2.0,
@@ -661,9 +705,10 @@ class Trainer:
             uploaded = self.pb.upload_batch(annotations)
         self.forward(x_u8)
         if tal:
-            y_target, self.last_npos, _ = self.pb.encode_uploaded(uploaded, return_device=True, pred=self.pred)
+            y_target, self.last_npos, assigned = self.pb.encode_uploaded(uploaded, return_device=True, pred=self.pred)
         self.last_target = y_target
-        self.loss(y_target)
+        # objectness "qfl" | "vfl": loss() launches the quality pass in front of the loss, on the step's stream
+        self.loss(y_target, (uploaded[2], assigned) if tal else None)
         self.backward()
         self.allreduce()
         self.sgd()
@@ -778,6 +823,18 @@ class Trainer:
             self.ema_decay = float(sd["ema_decay"])
         self._repack()
         self._sgd_key = None
+
+
+def check_objectness_args(objectness, quality, assigner):
+    """ValueError for an objectness term or a quality target the trainer cannot run (host-only: no library is loaded):
+    unknown names, and quality="tal" without assigner="tal" (its inputs are the task-aligned assignment's outputs)."""
+    if objectness not in OBJ_MODES:
+        raise ValueError(f"objectness must be one of {sorted(OBJ_MODES)}, got {objectness!r}")
+    if quality not in QUALITY_MODES:
+        raise ValueError(f"quality must be one of {QUALITY_MODES}, got {quality!r}")
+    if quality == "tal" and assigner != "tal":
+        raise ValueError(f'quality="tal" needs assigner="tal" (it normalises the metric of that assignment), got '
+                         f'assigner={assigner!r}')
 
 
 def make_buckets(layers, n_flat, min_elems):

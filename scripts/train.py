@@ -71,6 +71,12 @@ def build_parser():
     p.add_argument("--tal-topk", default=13, type=int, metavar="K", help="--assigner tal: positives per object (1..32)")
     p.add_argument("--tal-alpha", default=1.0, type=float, metavar="A", help="--assigner tal: exponent of the score")
     p.add_argument("--tal-beta", default=6.0, type=float, metavar="B", help="--assigner tal: exponent of the predicted box's IoU")
+    p.add_argument("--objectness", default="focal", choices=("focal", "qfl", "vfl"),
+                   help="objectness term: focal loss on hard targets, or quality focal / varifocal loss towards the quality "
+                        "targets of --quality (od_loss_fwd_bwd_quality)")
+    p.add_argument("--quality", default="iou", choices=("iou", "tal"),
+                   help="--objectness qfl | vfl: the target of an assigned prior: IoU of its predicted box with its object, or "
+                        "TOOD's normalised alignment metric (needs --assigner tal)")
     p.add_argument("--shapes-difficult", default=0.0, type=float, help="--shapes: share of objects marked difficult")
     p.add_argument("--shapes-crowd", default=0.0, type=float, help="--shapes: share of images with a crowd region")
     p.add_argument("--prefetch", default=2, type=int, help="batches the generator thread runs ahead (0 = in the training thread)")
@@ -165,6 +171,7 @@ def _run(args):
                  weight_decay=args.weight_decay, comm=comm, world_size=world, lr_multipliers=mult, prior_wh=prior_wh, box_mode=args.box_loss,
                  ignore_regions=args.ignore_regions, loss_weights=(1.0, 1.0, args.box_weight), assigner=args.assigner,
                  atss_topk=args.atss_topk, tal_topk=args.tal_topk, tal_alpha=args.tal_alpha, tal_beta=args.tal_beta,
+                 objectness=args.objectness, quality=args.quality,
                  **({} if args.ema is None else {"ema_decay": args.ema}))
     start, flow_seed = 0, args.seed + rank
     if args.resume is not None:
