@@ -49,6 +49,81 @@ def ema_omd(n: int, decay: float, warmup: bool = True) -> np.float32:
     return np.float32(1.0 - ema_decay_at(n, decay, warmup))
 
 
+LAG = 2  # the non-finite flag of step j is applied at the start of step j + LAG, on every rank, whatever the timing
+LOSS_SCALE_MIN, LOSS_SCALE_MAX = 1.0, 65536.0
+
+
+class LossScaleControl:
+    """The host rule of the dynamic loss scale and its fixed-lag queue (no GPU, no library): a pure function of the flags.
+
+    apply(flag): any non-zero flag is a skipped step -- skipped_steps and consecutive_skips go up, good_steps back to 0 and
+    the scale is halved (floor LOSS_SCALE_MIN); a zero flag ends the run of skips, and the `interval`-th clean flag in a row
+    doubles the scale (cap LOSS_SCALE_MAX) and starts the count again.  dynamic=False moves the counters and not the scale.
+
+    pending: the flags of the steps not applied yet, oldest first.  A step calls begin_step() first and push()es its own
+    flag last, so begin_step() of step i finds the flags of steps .. i-1 and applies those of steps .. i-lag: one per step
+    in a run, none before `lag` steps have been pushed.  drain() applies everything pending, in order (end of a run, tests).
+    An entry is whatever `read` turns into an int -- the trainer's are (event, pinned host flag) pairs whose copy it waits
+    for; both calls return the entries they consumed."""
+
+    def __init__(self, loss_scale, interval=2000, dynamic=True, lag=LAG, read=int):
+        self.loss_scale, self.interval, self.dynamic = float(loss_scale), interval, bool(dynamic)
+        self.lag, self.read = int(lag), read
+        self.skipped_steps = self.good_steps = self.consecutive_skips = 0
+        self.pending = []
+
+    def apply(self, flag):
+        if int(flag) != 0:
+            self.skipped_steps += 1
+            self.consecutive_skips += 1
+            self.good_steps = 0
+            if self.dynamic:
+                self.loss_scale = max(LOSS_SCALE_MIN, self.loss_scale * 0.5)
+        else:
+            self.consecutive_skips = 0
+            self.good_steps += 1
+            if self.dynamic and self.good_steps >= self.interval:
+                self.loss_scale, self.good_steps = min(self.loss_scale * 2.0, LOSS_SCALE_MAX), 0
+
+    def push(self, entry):
+        self.pending.append(entry)
+
+    def _consume(self, keep):
+        done = []
+        while len(self.pending) > keep:
+            done.append(self.pending.pop(0))
+            self.apply(self.read(done[-1]))
+        return done
+
+    def begin_step(self):
+        return self._consume(self.lag - 1)
+
+    def drain(self):
+        return self._consume(0)
+
+    def pending_flags(self):
+        """The values of the pending flags, oldest first; applies none."""
+        return [int(self.read(e)) for e in self.pending]
+
+    def values(self):
+        return self.loss_scale, self.skipped_steps, self.good_steps, self.consecutive_skips
+
+
+def _flag_value(entry):
+    """LossScaleControl.read of the trainer: an (event, pinned host flag) pair is waited for (its copy was queued at least
+    one whole step ago when a step asks, so the wait does not stall), anything else is the value itself."""
+    if isinstance(entry, tuple):
+        ev, host = entry
+        ev.synchronize()
+        return int(host[0])
+    return int(entry)
+
+
+def _ctl_attr(name):
+    """Trainer attribute that lives in its LossScaleControl (read and set under the trainer's own name)."""
+    return property(lambda self: getattr(self._ctl, name), lambda self, v: setattr(self._ctl, name, v))
+
+
 class _Node:
     __slots__ = ("name", "x", "out", "res", "res_mode", "H", "W", "Cin", "Cout", "k", "stride", "act", "bn", "z",
                  "mean", "rstd", "scale", "shift", "first", "pred_off", "pred_rows", "need_dx",
@@ -57,6 +132,11 @@ class _Node:
 
 
 class Trainer:
+    # the loss-scale control's values (LossScaleControl), under the names the trainer has always had
+    loss_scale, skipped_steps = _ctl_attr("loss_scale"), _ctl_attr("skipped_steps")
+    _good_steps, _consecutive_skips = _ctl_attr("good_steps"), _ctl_attr("consecutive_skips")
+    dynamic_loss_scale, loss_scale_growth_interval = _ctl_attr("dynamic"), _ctl_attr("interval")
+
     def __init__(self, params, batch_size, input_size=(320, 320), device="cuda:0", lr=1e-3, momentum=0.9,
                  weight_decay=0.0, loss_scale=1024.0, box_mode="smooth_l1", backbone_act=("leaky", 0.1),
                  head_act=("elu", 1.0), comm=None, world_size=1, grad_payload=None, dynamic_loss_scale=True,
@@ -85,7 +165,14 @@ class Trainer:
         self.num_classes, self.neck_ch, self.tower = W.infer_arch(params)
         self.C = self.num_classes + 6
         self.lr, self.momentum, self.weight_decay = float(lr), float(momentum), float(weight_decay)
-        self.loss_scale, self.box_mode = float(loss_scale), box_mode
+        # loss-scale guard: a non-finite value in the flat gradient buffer (one f16 overflow in a loss-scaled dz is enough)
+        # makes the device skip the update; the host applies the flag exactly LAG steps later (_poll_nonfinite) and halves
+        # the scale.  self._flag_queue IS the control's pending list: (event, pinned host flag) of the steps whose flag is
+        # not applied yet, or plain ints (load_state_dict)
+        self._ctl = LossScaleControl(loss_scale, 2000, dynamic_loss_scale, read=_flag_value)
+        self._flag_queue, self._flag_pool = self._ctl.pending, []
+        self.max_consecutive_skips = 50  # fit() gives up after this many skipped steps in a row (see diverged())
+        self.box_mode = box_mode
         # box_mode "giou" | "diou" | "ciou": the box loss is taken on the boxes decoded with self.pb's priors and loc_scale;
         # loss_weights = (objectness, class, box) multiply the three components
         if box_mode not in BOX_MODES:
@@ -102,12 +189,6 @@ class Trainer:
         self.grad_payload = grad_payload or os.environ.get("OD_TRAIN_GRAD_PAYLOAD", "f32")
         if self.grad_payload not in ("f32", "bf16"):
             raise ValueError(f"grad_payload must be 'f32' or 'bf16', got {self.grad_payload!r}")
-        # loss-scale guard: a non-finite value in the flat gradient buffer (one f16 overflow in a loss-scaled dz is enough)
-        # makes the device skip the update; the host learns about it one step later and halves the scale
-        self.dynamic_loss_scale = bool(dynamic_loss_scale)
-        self.skipped_steps = 0
-        self._good_steps = 0
-        self.loss_scale_growth_interval = 2000
         # prior_wh: the [3, 8, 2] table of prior sizes in grid-cell units (priors.fit: KMeans over the training boxes,
         # docs/MODEL.md:29-31); None = the frozen default table
         # ignore_regions / ign_thr: handed to the PriorBoxes (pb.py): annotations' `difficults` become ignore regions in
@@ -232,9 +313,6 @@ class Trainer:
         self.payload_buf = (torch.empty(self.n_flat, dtype=torch.bfloat16, device=dev) if self.grad_payload == "bf16"
                             else None)
         self.nonfinite = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._flag_queue, self._flag_pool = [], []  # (event, pinned host flag) of steps whose flag copy is still in flight
-        self._consecutive_skips = 0
-        self.max_consecutive_skips = 50  # fit() gives up after this many skipped steps in a row (see diverged())
         self._buckets = self._make_buckets(int(self.bucket_mb * (1 << 20) / 4)) if self.cstream is not None else []
         self._next_bucket = 0
         self.bn_ws = torch.empty(max(n.bn_wsb + 2 * n.Cout * 4 for n in self.nodes), dtype=torch.uint8, device=dev)
@@ -634,8 +712,8 @@ class Trainer:
                        "od_sgd_step_multi")
         else:
             # the decay follows the number of sgd() calls made so far, skipped steps INCLUDED: the host learns of a skip
-            # one or two steps late (_poll_nonfinite), and a schedule that waited for it would differ between a run and
-            # its replay, and between ranks that poll at different moments.  The device skips the update itself.
+            # LAG steps late (_poll_nonfinite), so a schedule that counted applied updates would lag the device by as
+            # much.  The device skips the update itself.
             omd = float(ema_omd(self.ema_updates, self.ema_decay, self.ema_warmup))
             _lib.check(self.lib.od_sgd_step_multi_ema(self.ctx.handle, self.params.data_ptr(), self.mom.data_ptr(),
                                                       self.grads.data_ptr(), self.ema.data_ptr(), self._sgd_table.data_ptr(),
@@ -656,32 +734,22 @@ class Trainer:
         host.copy_(self.nonfinite, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
-        self._flag_queue.append((ev, host))
+        self._ctl.push((ev, host))
 
     def _poll_nonfinite(self, wait=False):
-        """Consume the flags of earlier steps whose device->host copy HAS completed (event.query(): the host never waits
-        for the previous step here, so encode_batch and the first launches of this step overlap its tail; the loss scale
-        reacts one or two steps late).  A skipped step halves the loss scale; a long clean run doubles it again.
-        wait=True drains the queue (end of fit(), tests)."""
-        while self._flag_queue:
-            ev, host = self._flag_queue[0]
-            if wait:
-                ev.synchronize()
-            elif not ev.query():
-                break
-            self._flag_queue.pop(0)
-            bad = int(host[0]) != 0
-            self._flag_pool.append(host)
-            self._consecutive_skips = self._consecutive_skips + 1 if bad else 0
-            if bad:
-                self.skipped_steps += 1
-                self._good_steps = 0
-                if self.dynamic_loss_scale:
-                    self.loss_scale = max(1.0, self.loss_scale * 0.5)
-            else:
-                self._good_steps += 1
-                if self.dynamic_loss_scale and self._good_steps >= self.loss_scale_growth_interval:
-                    self.loss_scale, self._good_steps = min(self.loss_scale * 2.0, 65536.0), 0
+        """Start of a step: apply the flag of the step LAG steps back (LossScaleControl.begin_step) and no newer one,
+        waiting for its device->host copy.  That copy was queued behind a step that ended a whole step ago, so the wait
+        does not stall and the host still runs two steps ahead: encode_batch and the first launches of this step overlap
+        the previous step's tail.  When a flag is applied therefore depends on the step count alone -- not on timing, not
+        on the rank.  A skipped step halves the loss scale; a long clean run doubles it again.
+        wait=True applies everything pending, in order (the end of a run, tests)."""
+        for entry in (self._ctl.drain() if wait else self._ctl.begin_step()):
+            if isinstance(entry, tuple):
+                self._flag_pool.append(entry[1])
+
+    def pending_flags(self):
+        """The flags of the steps the control has not applied yet, oldest first (waits for their copies, applies none)."""
+        return self._ctl.pending_flags()
 
     def diverged(self):
         """True when the last `max_consecutive_skips` steps were ALL skipped although the loss scale has already been halved
@@ -719,8 +787,10 @@ class Trainer:
         list of annotations) -- what od_gen.Generator(on_device=True).flow(...) yields (the reference's unseen `fit`:
         generator -> encode_truth -> losses, check_assign.py:21-22).  lr_schedule(step) -> learning rate.  Returns the
         per-step losses [steps, 4] (objectness, class, box, total) as a numpy array; losses stay on the device until the
-        end, so the loop never synchronises.  start_step: a continued run (load_state_dict) -- the schedule is asked for
-        start_step + i, and the history covers the `steps` steps run here."""
+        end, and the loop waits for nothing but the flag copy of the step LAG steps back (_poll_nonfinite), so the host
+        runs two steps ahead.  start_step: a continued run (load_state_dict) -- the schedule is asked for start_step + i,
+        and the history covers the `steps` steps run here.  The flags of the last LAG steps stay pending when fit()
+        returns: a run in several fit() calls is the run in one, and _poll_nonfinite(wait=True) ends a run."""
         hist = torch.zeros((steps, 4), dtype=torch.float32, device=self.device)
         for i, (xb, yb) in zip(range(steps), batches):
             if lr_schedule is not None:
@@ -739,7 +809,6 @@ class Trainer:
                 l = hist[i].cpu().numpy()
                 log(f"step {start_step + i + 1}/{start_step + steps} lr {self.lr:.4g} loss {l[3]:.4f} (obj {l[0]:.4f} cls {l[1]:.4f} box {l[2]:.4f}) "
                     f"loss_scale {self.loss_scale:g} skipped {self.skipped_steps}")
-        self._poll_nonfinite(wait=True)
         return hist.cpu().numpy()
 
     def export_params(self, ema=False):
@@ -783,21 +852,25 @@ class Trainer:
     def state_dict(self):
         """Everything a continued run needs, as host numpy arrays and scalars (weights.save_state writes it): masters,
         momentum, BatchNorm running statistics, the averaged model when there is one, the loss-scale control's counters
-        and the layout record that load_state_dict checks.  Waits for the flags of the steps in flight first."""
-        self._poll_nonfinite(wait=True)
+        and the layout record that load_state_dict checks.  An observer: it applies no pending flag, it waits for their
+        values and stores them as "pending_flags" (int32, oldest first, at most LAG entries in a run of step() calls), so
+        that a run goes on as if it had not been called and a resumed run applies them at the same steps."""
         sd = {"params": self.params.cpu().numpy(), "mom": self.mom.cpu().numpy(), "run_stats": self.run_stats.cpu().numpy()}
         if self.ema_decay is not None:
             sd["ema"], sd["ema_run_stats"] = self.ema.cpu().numpy(), self.ema_run_stats.cpu().numpy()
         sd["loss_scale"] = float(self.loss_scale)
         for k in self._STATE_SCALARS[1:]:
             sd[k] = int(getattr(self, k))
+        sd["pending_flags"] = np.array(self.pending_flags(), np.int32)
         sd["ema_decay"] = self.ema_decay  # None = no averaged model (weights.save_state leaves a None out of the file)
         sd.update(self._layout())
         return sd
 
     def load_state_dict(self, sd):
         """Continue from a state_dict() of a trainer with the same layout and the same EMA switch (ValueError otherwise):
-        uploads every buffer, sets the counters, re-packs the f16 weights, and has the next sgd() rebuild its table."""
+        uploads every buffer, sets the counters, puts the state's pending flags in place of this trainer's own (a state
+        without "pending_flags" is of the older format: none pending), re-packs the f16 weights, and has the next sgd()
+        rebuild its table."""
         mine = self._layout()
         for k, v in mine.items():
             if k not in sd or not np.array_equal(np.asarray(sd[k]), v):
@@ -813,7 +886,9 @@ class Trainer:
             a = np.ascontiguousarray(sd[k], np.float32)
             if a.shape != tuple(t.shape):
                 raise ValueError(f"load_state_dict: {k} has shape {a.shape}, expected {tuple(t.shape)}")
+        pending = [int(v) for v in np.asarray(sd["pending_flags"]).reshape(-1)] if "pending_flags" in sd else []
         self._poll_nonfinite(wait=True)  # flags of this trainer's own earlier steps must not touch the loaded counters
+        self._flag_queue[:] = pending
         for k, t in bufs:
             t.copy_(torch.from_numpy(np.ascontiguousarray(sd[k], np.float32)))
         self.loss_scale = float(sd["loss_scale"])

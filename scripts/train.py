@@ -228,6 +228,7 @@ def _run(args):
             W.save_state(tmp, dict(tr.state_dict(), step=done))
             tmp.replace(state)  # a run killed while writing leaves the previous state file whole
             log.info(f"state of step {done} written to {state}")
+    tr._poll_nonfinite(wait=True)  # the run is over: apply the flags of its last steps (fit() and state_dict() leave them pending)
     hist = np.concatenate(hists)
     ran = args.steps - start
     torch.cuda.synchronize()

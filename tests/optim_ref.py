@@ -100,3 +100,33 @@ def lr_mult_ref(name):
     if name.startswith("h."):
         return 1.0 / 3.0
     return 1.0
+
+
+def loss_scale_ref(flags, lag, scale0, interval, dynamic=True, steps=None):
+    """The host loss-scale control as a function of the non-finite flags alone.  -> for every step i in range(steps)
+    (default len(flags)) the (loss_scale, skipped_steps, good_steps, consecutive_skips) that step i STARTS with: the flags
+    of steps 0 .. i - lag have been applied, in order, and no other.  Each entry is computed from scratch, without a queue.
+
+    The rule: a non-zero flag (any value) counts one skipped step and one more consecutive skip, forgets the clean steps
+    counted so far and halves the scale, never below 1; a zero flag ends the consecutive skips and counts one clean step,
+    and when `interval` of them have come in a row the scale doubles, never above 65536, and the count starts again.
+    dynamic=False: the scale stays, skipped_steps and consecutive_skips move as before, and good_steps counts the clean
+    flags since the last bad one without starting again (nothing doubles).  steps > len(flags): the run goes on with no new flags, so entry
+    len(flags) + lag - 1 has every flag applied (what a drain at the end of the run leaves)."""
+    flags = [int(f) for f in flags]
+    out = []
+    for i in range(len(flags) if steps is None else steps):
+        scale, skipped, good, consecutive = float(scale0), 0, 0, 0
+        for f in flags[:max(0, i - lag + 1)]:
+            if f != 0:
+                skipped, consecutive, good = skipped + 1, consecutive + 1, 0
+                if dynamic and scale > 1.0:
+                    scale = max(scale / 2.0, 1.0)
+            else:
+                consecutive, good = 0, good + 1
+                if dynamic and good == interval:
+                    good = 0
+                    if scale < 65536.0:
+                        scale = min(scale * 2.0, 65536.0)
+        out.append((scale, skipped, good, consecutive))
+    return out

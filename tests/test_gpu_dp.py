@@ -135,3 +135,51 @@ def test_train_script_two_ranks_learns_and_ranks_agree(cuda, tmp_path):
     first, last = float(hist[:3].mean()), float(hist[-20:].mean())
     print(f"2-rank train.py: loss {first:.3f} -> {last:.3f}")
     assert last * 1.8 <= first, (first, last)  # (120 short steps at 160^2: measured 8.76 -> 4.12)
+
+
+def test_two_ranks_with_different_timing_keep_one_loss_scale_schedule(cuda, tmp_path):
+    """tests/dp_schedule_worker.py: 8 steps on two ranks whose hosts run as differently as they can -- rank 0 waits for the
+    device after every step and alone calls state_dict() after step 3, rank 1 holds every sgd() back with a spin kernel
+    four single-process steps long -- with an Inf in rank 1's loss gradient at steps 2 and 5.  Both ranks apply each flag two
+    steps behind its step: one history of control values, the reference's, and bit-identical params and momentum.  (A rank
+    that halved its scale one step before the other would scale its dz and unscale the summed gradient by another factor than
+    its peer, and nothing brings the weights together again.)"""
+    sys.path.insert(0, str(ROOT / "tests"))
+    import dp_worker as D
+    import loss_scale_sched as L
+    import optim_ref as R
+    from object_detector_amd import weights as W
+    from object_detector_amd.trainer import Trainer
+    x, anns = D.make_batch(D.GLOBAL_B, D.S)
+    tr = Trainer(W.random_init(2), 2, (D.S, D.S), device=cuda, lr=D.LR, momentum=0.9, loss_scale=D.LS)
+    y = tr.pb.encode_batch(anns[:2], return_device=True)[0]
+    step_ms = L.measure_step_ms(tr, torch.from_numpy(x[:2]).to(cuda), y)
+    del tr, y
+    torch.cuda.empty_cache()
+    print(f"single-process step {step_ms:.2f} ms, rank 1 spins {L.SPIN_STEPS * step_ms:.1f} ms in front of sgd()")
+    _launch(2, [str(tmp_path), f"{L.SPIN_STEPS * step_ms:.3f}"], script=ROOT / "tests" / "dp_schedule_worker.py")
+    r0 = np.load(tmp_path / "schedule_rank0.npz")
+    r1 = np.load(tmp_path / "schedule_rank1.npz")
+    want = R.loss_scale_ref(L.FLAGS, L.LAG, D.LS, L.INTERVAL, steps=8 + L.LAG)
+    h0, h1 = ([tuple(row) for row in r["history"].tolist()] for r in (r0, r1))
+    print("rank 0", h0, "\nrank 1", h1, "\nref   ", want[:8])
+    assert int(r1["spin_ticks"]) > 0 and int(r0["spin_ticks"]) == 0
+    assert r0["flags"].tolist() == r1["flags"].tolist() == L.FLAGS, "rank 1's Inf did not reach both ranks' flags"
+    # every statement is looked at before the test fails, so that one failure shows what went apart and what followed from it
+    wrong = []
+    if h0 != want[:8]:
+        wrong.append(f"rank 0 (eager, state_dict() after step 3) leaves the reference at step {[a == b for a, b in zip(h0, want)].index(False)}")
+    if h1 != want[:8]:
+        wrong.append(f"rank 1 (lazy) leaves the reference at step {[a == b for a, b in zip(h1, want)].index(False)}")
+    for k in ("params", "mom"):
+        differ = int((r0[k].view(np.uint32) != r1[k].view(np.uint32)).sum())
+        if differ:
+            wrong.append(f"{k}: {differ} of {r0[k].size} elements differ between the ranks")
+    if not np.isfinite(r0["params"]).all():
+        wrong.append("rank 0's params are not finite")
+    for rank, r in enumerate((r0, r1)):
+        if int(r["pending"]) != L.LAG:
+            wrong.append(f"rank {rank} ends the run with {int(r['pending'])} flags pending, not {L.LAG}")
+        if tuple(r["final"].tolist()) != want[8 + L.LAG - 1] or int(r["final"][1]) != 2:
+            wrong.append(f"rank {rank} after the final drain: {tuple(r['final'].tolist())}, reference {want[8 + L.LAG - 1]}")
+    assert not wrong, "\n".join(wrong)

@@ -273,6 +273,7 @@ def test_giou_training_lowers_the_box_loss(cuda):
         while True:
             yield xt, y
     hist = tr.fit(batches(), 30)
+    tr._poll_nonfinite(wait=True)
     assert np.isfinite(hist).all() and tr.skipped_steps == 0, f"{tr.skipped_steps} skipped steps"
     first, last = hist[:5, 2].mean(), hist[-5:, 2].mean()
     print(f"giou box loss: first 5 steps {first:.4f}, last 5 steps {last:.4f}, drop {first - last:.4f}")

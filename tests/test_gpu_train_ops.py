@@ -159,6 +159,7 @@ def test_generator_feeds_trainer_without_leaving_the_device(cuda):
         assert isinstance(yb, torch.Tensor) and yb.is_cuda and tuple(yb.shape) == (B, tr.P, 26)
         assert np.array_equal(xb.cpu().numpy(), xh) and np.array_equal(yb.cpu().numpy(), yh)
         losses.append(float(tr.step(xb, y_target=yb)[3]))
+    tr._poll_nonfinite(wait=True)
     assert all(np.isfinite(losses)) and tr.skipped_steps == 0
     with pytest.raises(ValueError):
         od_gen.create_generator((S, S), on_device=True)

@@ -189,7 +189,9 @@ def test_state_round_trip_continues_bit_for_bit(cuda, trained, tmp_path):
     tr, _xt, _anns = trained
     tr.loss_scale, tr._good_steps, tr.skipped_steps, tr._consecutive_skips = 128.0, 17, 3, 2
     sd = tr.state_dict()
-    assert not tr._flag_queue
+    # state_dict() observes: the flags the control has not applied yet travel in the state, none is applied
+    assert sd["pending_flags"].dtype == np.int32 and sd["pending_flags"].tolist() == tr.pending_flags()
+    assert len(tr._flag_queue) == len(sd["pending_flags"])
     assert set(sd) >= {"params", "mom", "run_stats", "ema", "ema_run_stats", "loss_scale", "_good_steps", "skipped_steps",
                        "_consecutive_skips", "ema_updates", "ema_decay", "layout.names", "layout.kinds", "layout.offsets",
                        "layout.counts"}
@@ -202,6 +204,7 @@ def test_state_round_trip_continues_bit_for_bit(cuda, trained, tmp_path):
     other._sgd_key = "stale"
     other.load_state_dict(W.load_state(tmp_path / "state.npz"))
     assert other._sgd_key is None
+    assert other.pending_flags() == tr.pending_flags() and len(other._flag_queue) == len(tr._flag_queue)
     for k in ("params", "mom", "run_stats", "ema", "ema_run_stats"):
         _same(getattr(other, k), getattr(tr, k), k)
     for k in ("loss_scale", "_good_steps", "skipped_steps", "_consecutive_skips", "ema_updates", "ema_decay"):
