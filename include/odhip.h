@@ -565,6 +565,74 @@ int od_ema_update(od_ctx* ctx, float* ema, const float* x, long long n, float on
 /* flag[0] (DEVICE int32) = 1 when any of g[0..n) is Inf / NaN, else 0.  Run it on the flat gradient buffer AFTER the
  * all-reduce: a non-finite value on one rank reaches every rank through the sum, so all ranks skip the same step. */
 int od_grad_nonfinite(od_ctx* ctx, const float* g, long long n, int32_t* flag, void* stream);
+
+/* ---- Optimizers beyond plain momentum SGD, and gradient clipping by global norm.  Three launches per step, no host
+ * synchronisation: od_grad_stats -> od_optim_prepare -> od_optim_step_multi.  All f32 arithmetic below is a sequence of
+ * single, separately rounded operations in the order written (the sum of squares alone is f64), so a numpy restatement
+ * reproduces every result bit for bit, and every rank of a data-parallel run computes the same bits from the same
+ * all-reduced gradient buffer. */
+#define OD_OPT_SGD 0      /* w -= lr*(m = momentum*m + g*inv + wd*w): od_sgd_step_multi's rule */
+#define OD_OPT_NESTEROV 1 /* grad = g*inv + wd*w; m = momentum*m + grad; w -= lr*(grad + momentum*m) */
+#define OD_OPT_ADAMW 2    /* decoupled weight decay; bias correction from od_optim_state */
+/* DEVICE-resident state of the optimizer, 32 bytes; the host initialises it to step = 0, b1pow = b2pow = 1 (the other
+ * fields are written by od_optim_prepare before anything reads them). */
+typedef struct od_optim_state {
+  int32_t step;        /* updates applied so far (skipped steps do not count) */
+  float b1pow;         /* beta1 ** step as a running product of f32 multiplications */
+  float b2pow;         /* beta2 ** step likewise */
+  float grad_norm;     /* the step's true gradient norm: unscaled, before clipping; Inf / NaN on a flagged step */
+  float clip_coef;     /* min(1, max_grad_norm / (grad_norm + 1e-6)), 1 without clipping; may be NaN on a flagged step */
+  float inv_scale_eff; /* inv_loss_scale * clip_coef: what every update rule multiplies g by */
+  float bc1;           /* 1 - b1pow */
+  float bc2;           /* 1 - b2pow */
+} od_optim_state;
+/* HOST struct of the hyper-parameters the three launches share */
+typedef struct od_optim_cfg {
+  int32_t kind;              /* OD_OPT_* */
+  float momentum;            /* SGD kinds: momentum; AdamW: beta1.  In [0, 1) */
+  float beta2;               /* AdamW, in [0, 1) */
+  float eps;                 /* AdamW, > 0 */
+  float inv_loss_scale;      /* as od_sgd_step_multi's */
+  float max_grad_norm;       /* <= 0: no clipping */
+  float ema_one_minus_decay; /* read when od_optim_step_multi is given `ema`; in [0, 1] */
+  int32_t pad_;
+} od_optim_cfg;
+/* od_grad_stats: od_grad_nonfinite (same `flag` contract: cleared, then set to 1 when any of g[0..n) is Inf / NaN) and, in
+ * the same pass, the sum of squares of g: `workspace` (DEVICE, 8-byte aligned, od_grad_stats_workspace_bytes(n) bytes)
+ * receives one f64 partial per workgroup.  Every element is widened to f64, squared (exact) and added in f64; which
+ * elements a lane adds in which order, the in-workgroup reduction and the number of partials are fixed functions of n
+ * alone, and no float atomic is used: the same bits on every run and every rank.  g must be 16-byte aligned. */
+size_t od_grad_stats_workspace_bytes(long long n);
+int od_grad_stats(od_ctx* ctx, const float* g, long long n, int32_t* flag, void* workspace, void* stream);
+/* od_optim_prepare: one small launch behind od_grad_stats(g, n, flag, workspace) that turns the partials into the step's
+ * scalars in *state (DEVICE):
+ *   s = sum of the partials in ascending index order (f64);  norm_raw = sqrtf((float)s)
+ *   grad_norm = norm_raw * inv_loss_scale
+ *   clip_coef = max_grad_norm > 0 ? fminf(1.0f, max_grad_norm / (grad_norm + 1e-6f)) : 1.0f   (clip_grad_norm_'s formula)
+ *   inv_scale_eff = inv_loss_scale * clip_coef
+ *   if (*flag == 0) { step += 1; b1pow = b1pow * momentum; b2pow = b2pow * beta2; bc1 = 1.0f - b1pow; bc2 = 1.0f - b2pow; }
+ * A flagged step leaves step, b1pow, b2pow, bc1 and bc2 untouched; its grad_norm, clip_coef and inv_scale_eff may be
+ * Inf / NaN (od_optim_step_multi skips that step, so nothing consumes them).  The bias correction is a running product,
+ * not powf: numpy reproduces it, and the device -- not the host -- knows which steps were skipped. */
+int od_optim_prepare(od_ctx* ctx, const od_optim_cfg* cfg, const void* workspace, long long n, const int32_t* flag,
+                     od_optim_state* state, void* stream);
+/* od_optim_step_multi: one launch over the segment table of od_sgd_step_multi (per-segment lr and weight_decay as there).
+ * Every kind multiplies g by state->inv_scale_eff.  Per element:
+ *   OD_OPT_SGD       sgd_update: with clip_coef == 1 the bits of od_sgd_step_multi
+ *   OD_OPT_NESTEROV  grad = g*inv + wd*w; mv = momentum*m + grad; m = mv; u = grad + momentum*mv; w = w - lr*u
+ *   OD_OPT_ADAMW     gh = g*inv; m = beta1*m + (1.0f-beta1)*gh; v = beta2*v + (1.0f-beta2)*(gh*gh);
+ *                    mh = m/bc1; vh = v/bc2; den = sqrtf(vh) + eps; u = mh/den; w = w - lr*(u + wd*w)
+ * v: the second-moment buffer, required for OD_OPT_ADAMW, NULL otherwise.  ema: NULL, or the averaged model, updated
+ * behind the weight update per element exactly as od_sgd_step_multi_ema does (cfg->ema_one_minus_decay); it must not be
+ * w, m, v or g.  *skip_if_nonzero != 0 (DEVICE, may be NULL) leaves w, m, v and ema untouched; elements of no segment are
+ * never written.  Any offset is accepted: a segment whose buffers share the 16-byte phase moves as 16-byte accesses,
+ * any other one element by element, with the same bits.  OD_ERR_INVALID, and nothing written, for an unknown kind, nseg
+ * outside 1..65535, v against the kind, an aliasing ema, ema_one_minus_decay outside [0, 1], momentum / beta2 outside
+ * [0, 1) or eps <= 0 (AdamW). */
+int od_optim_step_multi(od_ctx* ctx, const od_optim_cfg* cfg, float* w, float* m, float* v, const float* g, float* ema,
+                        const od_sgd_seg* segs, int nseg, const od_optim_state* state, const int32_t* skip_if_nonzero,
+                        void* stream);
+
 /* dst[0..n) = src[0..n) when *flag (DEVICE int32) != 0, untouched otherwise.  The trainer keeps a copy of the BatchNorm
  * running statistics taken before forward and restores it with this call when od_grad_nonfinite flagged the step: the
  * skipped step's forward has already folded its (possibly overflowed) batch statistics into them. */

@@ -79,6 +79,23 @@ class SgdSeg(C.Structure):
     _fields_ = [("offset", C.c_int64), ("count", C.c_int64), ("lr", C.c_float), ("weight_decay", C.c_float)]
 
 
+OD_OPT_SGD, OD_OPT_NESTEROV, OD_OPT_ADAMW = 0, 1, 2
+OPTIMIZERS = {"sgd": OD_OPT_SGD, "nesterov": OD_OPT_NESTEROV, "adamw": OD_OPT_ADAMW}
+
+
+class OptimState(C.Structure):
+    C_NAME = "od_optim_state"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
+    _fields_ = [("step", C.c_int32), ("b1pow", C.c_float), ("b2pow", C.c_float), ("grad_norm", C.c_float),
+                ("clip_coef", C.c_float), ("inv_scale_eff", C.c_float), ("bc1", C.c_float), ("bc2", C.c_float)]
+
+
+class OptimCfg(C.Structure):
+    C_NAME = "od_optim_cfg"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
+    _fields_ = [("kind", C.c_int32), ("momentum", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("inv_loss_scale", C.c_float), ("max_grad_norm", C.c_float), ("ema_one_minus_decay", C.c_float),
+                ("pad_", C.c_int32)]
+
+
 class WgradRed(C.Structure):
     C_NAME = "od_wgrad_red"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
     _fields_ = [("dw_offset", C.c_int64), ("count", C.c_int64), ("slabs", C.c_void_p), ("nslabs", C.c_int32),
@@ -136,7 +153,7 @@ class SoftNmsCfg(C.Structure):
                 ("sigma", C.c_float), ("min_conf", C.c_float)]
 
 
-STRUCTS = (SoftNmsCfg, TileDesc, TtaView, ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
+STRUCTS = (SoftNmsCfg, TileDesc, TtaView, ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, OptimState, OptimCfg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
 
 
 class OdError(RuntimeError):
@@ -259,6 +276,12 @@ _PROTOS = {
                                         C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "od_ema_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_float, C.c_void_p, C.c_void_p]),
     "od_grad_nonfinite": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "od_grad_stats_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "od_grad_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "od_optim_prepare": (C.c_int, [C.c_void_p, C.POINTER(OptimCfg), C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "od_optim_step_multi": (C.c_int, [C.c_void_p, C.POINTER(OptimCfg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "od_copy_if_nonzero": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "od_cast_f32_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "od_cast_bf16_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),

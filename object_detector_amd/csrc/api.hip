@@ -97,6 +97,14 @@ const std::vector<StructInfo>& od_struct_table() {
         OD_F(od_wgrad_red, pad_)}},
       {"od_sgd_seg", sizeof(od_sgd_seg),
        {OD_F(od_sgd_seg, offset), OD_F(od_sgd_seg, count), OD_F(od_sgd_seg, lr), OD_F(od_sgd_seg, weight_decay)}},
+      {"od_optim_state", sizeof(od_optim_state),
+       {OD_F(od_optim_state, step), OD_F(od_optim_state, b1pow), OD_F(od_optim_state, b2pow),
+        OD_F(od_optim_state, grad_norm), OD_F(od_optim_state, clip_coef), OD_F(od_optim_state, inv_scale_eff),
+        OD_F(od_optim_state, bc1), OD_F(od_optim_state, bc2)}},
+      {"od_optim_cfg", sizeof(od_optim_cfg),
+       {OD_F(od_optim_cfg, kind), OD_F(od_optim_cfg, momentum), OD_F(od_optim_cfg, beta2), OD_F(od_optim_cfg, eps),
+        OD_F(od_optim_cfg, inv_loss_scale), OD_F(od_optim_cfg, max_grad_norm), OD_F(od_optim_cfg, ema_one_minus_decay),
+        OD_F(od_optim_cfg, pad_)}},
       {"od_pack_layer", sizeof(od_pack_layer),
        {OD_F(od_pack_layer, w_offset), OD_F(od_pack_layer, w_fwd), OD_F(od_pack_layer, w_bwd), OD_F(od_pack_layer, Cout),
         OD_F(od_pack_layer, Cin), OD_F(od_pack_layer, ksize), OD_F(od_pack_layer, pad_)}},

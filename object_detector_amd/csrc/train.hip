@@ -540,6 +540,187 @@ __global__ __launch_bounds__(256) void od_ema_k(float* __restrict__ ema, const f
   }
 }
 
+// ---- od_optim_step_multi: the update rules beyond od_sgd_multi[_ema]_k, one kernel per (kind, with / without average) ----
+// What the host resolves once per launch: the constants every element's update reads (1 - beta computed in f32 on the host:
+// one rounded subtraction, as the header writes it)
+struct optim_hp {
+  float momentum;  // beta1 for AdamW
+  float beta2, omb1, omb2, eps;
+  float omd;  // the average's 1 - decay
+};
+
+// One element's update, each line one rounded f32 operation or two as the header splits them (-ffp-contract=off).  `v` is
+// touched by AdamW alone.
+template <int KIND>
+__device__ __forceinline__ void optim_update(float& w, float& m, float& v, float g, float lr, float wd, const optim_hp& hp,
+                                             float inv, float bc1, float bc2) {
+  if (KIND == OD_OPT_SGD) {
+    sgd_update(w, m, g, lr, hp.momentum, wd, inv);
+  } else if (KIND == OD_OPT_NESTEROV) {
+    const float grad = g * inv + wd * w;
+    const float mv = hp.momentum * m + grad;
+    m = mv;
+    const float u = grad + hp.momentum * mv;
+    w = w - lr * u;
+  } else {
+    const float gh = g * inv;
+    m = hp.momentum * m + hp.omb1 * gh;
+    v = hp.beta2 * v + hp.omb2 * (gh * gh);
+    const float mh = m / bc1;
+    const float vh = v / bc2;
+    const float den = sqrtf(vh) + hp.eps;
+    const float u = mh / den;
+    w = w - lr * (u + wd * w);
+  }
+}
+
+// The segment walk of od_sgd_multi_ema_k (head < 4 / 16-byte body / tail < 4 where every buffer of the segment sits at the
+// same distance from a 16-byte boundary, element by element otherwise) around optim_update<KIND>, then ema_update when EMA.
+// v is NULL unless KIND == OD_OPT_ADAMW, ema is NULL unless EMA: neither is then formed into an address that is read.
+template <int KIND, bool EMA>
+__global__ __launch_bounds__(256) void od_optim_multi_k(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
+                                                        const float* __restrict__ g, float* __restrict__ ema,
+                                                        const od_sgd_seg* __restrict__ segs, optim_hp hp,
+                                                        const od_optim_state* __restrict__ state,
+                                                        const int32_t* __restrict__ skip) {
+  constexpr bool ADAM = KIND == OD_OPT_ADAMW;
+  if (skip && *skip) return;  // a skipped step leaves weights, both moments and the average alone
+  const float inv = state->inv_scale_eff, bc1 = state->bc1, bc2 = state->bc2;
+  const od_sgd_seg sg = segs[blockIdx.y];
+  float* ws = w + sg.offset;
+  float* ms = m + sg.offset;
+  float* vs = ADAM ? v + sg.offset : nullptr;
+  const float* gs = g + sg.offset;
+  float* es = EMA ? ema + sg.offset : nullptr;
+  const long long first = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+  auto one = [&](long long i) {
+    float dummy = 0.f;
+    optim_update<KIND>(ws[i], ms[i], ADAM ? vs[i] : dummy, gs[i], sg.lr, sg.weight_decay, hp, inv, bc1, bc2);
+    if (EMA) ema_update(es[i], ws[i], hp.omd);
+  };
+  const unsigned a = (unsigned)((uintptr_t)ws & 15);
+  if (((uintptr_t)ms & 15) != a || ((uintptr_t)gs & 15) != a || (ADAM && ((uintptr_t)vs & 15) != a) ||
+      (EMA && ((uintptr_t)es & 15) != a)) {
+    for (long long i = first; i < sg.count; i += stride) one(i);
+    return;
+  }
+  const long long head = head_to_16(ws, sg.count);
+  const long long nvec = (sg.count - head) >> 2;
+  const long long tail0 = head + 4 * nvec;  // first element behind the aligned body
+  f32x4* w4 = (f32x4*)(ws + head);
+  f32x4* m4 = (f32x4*)(ms + head);
+  f32x4* v4 = ADAM ? (f32x4*)(vs + head) : nullptr;
+  const f32x4* g4 = (const f32x4*)(gs + head);
+  f32x4* e4 = EMA ? (f32x4*)(es + head) : nullptr;
+  for (long long i = first; i < nvec; i += stride) {
+    f32x4 wv = w4[i], mv = m4[i], vv = {0.f, 0.f, 0.f, 0.f}, ev = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 gv = g4[i];
+    if (ADAM) vv = v4[i];
+    if (EMA) ev = e4[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float wk = wv[k], mk = mv[k], vk = vv[k], ek = ev[k];
+      optim_update<KIND>(wk, mk, vk, gv[k], sg.lr, sg.weight_decay, hp, inv, bc1, bc2);
+      if (EMA) ema_update(ek, wk, hp.omd);
+      wv[k] = wk, mv[k] = mk, vv[k] = vk, ev[k] = ek;
+    }
+    w4[i] = wv;
+    m4[i] = mv;
+    if (ADAM) v4[i] = vv;
+    if (EMA) e4[i] = ev;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 8) {  // lanes 0..3: the head, lanes 4..7: the tail
+    const long long i = threadIdx.x < 4 ? (long long)threadIdx.x : tail0 + (threadIdx.x - 4);
+    if (threadIdx.x < 4 ? i < head : i < sg.count) one(i);
+  }
+}
+
+// ---- od_grad_stats / od_optim_prepare ----------------------------------------------------------------------------------
+// Workgroups of od_grad_stats_k: a function of n alone.  At most 1024 (4 per CU: enough 16-byte loads in flight to stream
+// from HBM) so that od_optim_prepare_k's ordered sum of the partials stays a few microseconds.
+#define OD_STATS_MAX_GROUPS 1024
+static unsigned grad_stats_groups(long long n) {
+  const long long b = (n / 4 + 1023) / 1024;  // one tile of 1024 vectors per workgroup before the grid starts to stride
+  return (unsigned)(b > OD_STATS_MAX_GROUPS ? OD_STATS_MAX_GROUPS : (b < 1 ? 1 : b));
+}
+
+__device__ __forceinline__ bool nonfinite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// od_grad_nonfinite_k plus the sum of squares.  Lane order: each lane adds its vectors tile by tile (below), the four
+// elements of a vector in index order, then (workgroup 0, lanes 0..2) its tail element; the 256 lane sums are folded in
+// LDS by halving (lane t += lane t + s for s = 128 .. 1).  All of it in f64, nothing atomic but the integer flag.
+__global__ __launch_bounds__(256) void od_grad_stats_k(const float* __restrict__ g, long long n4, long long n,
+                                                       int32_t* __restrict__ flag, double* __restrict__ partials) {
+  __shared__ double red[256];
+  bool bad = false;
+  double acc = 0.0;
+  const f32x4* g4 = (const f32x4*)g;
+  auto add = [&](const f32x4 v) {
+    bad = bad || nonfinite_bits(v.x) || nonfinite_bits(v.y) || nonfinite_bits(v.z) || nonfinite_bits(v.w);
+    const double x = (double)v.x, y = (double)v.y, z = (double)v.z, q = (double)v.w;
+    acc = acc + x * x;
+    acc = acc + y * y;
+    acc = acc + z * z;
+    acc = acc + q * q;
+  };
+  // a workgroup walks tiles of 1024 consecutive vectors (16 KiB) in grid-stride order; a lane takes vectors t, t + 256,
+  // t + 512, t + 768 of the tile: four loads in flight, added in that order
+  for (long long base = (long long)blockIdx.x * 1024 + threadIdx.x; base < n4; base += (long long)gridDim.x * 1024) {
+    if (base + 768 < n4) {
+      const f32x4 a = g4[base], b = g4[base + 256], c = g4[base + 512], d = g4[base + 768];
+      add(a), add(b), add(c), add(d);
+    } else {
+      for (long long i = base; i < n4 && i < base + 1024; i += 256) add(g4[i]);
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n - 4 * n4)) {
+    const float t = g[4 * n4 + threadIdx.x];
+    bad = bad || nonfinite_bits(t);
+    acc = acc + (double)t * (double)t;
+  }
+  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
+// One workgroup: the partials travel to LDS side by side, lane 0 adds them in ascending order and writes the scalars
+__global__ __launch_bounds__(256) void od_optim_prepare_k(const double* __restrict__ partials, int npart, float momentum,
+                                                          float beta2, float inv_loss_scale, float max_grad_norm,
+                                                          const int32_t* __restrict__ flag, od_optim_state* __restrict__ st) {
+  __shared__ double p[OD_STATS_MAX_GROUPS];
+  double r[OD_STATS_MAX_GROUPS / 256];  // all of a lane's loads in flight before the first is waited for
+#pragma unroll
+  for (int k = 0; k < OD_STATS_MAX_GROUPS / 256; ++k) {
+    const int i = 256 * k + (int)threadIdx.x;
+    r[k] = i < npart ? partials[i] : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < OD_STATS_MAX_GROUPS / 256; ++k) p[256 * k + threadIdx.x] = r[k];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double s = 0.0;
+  for (int i = 0; i < npart; ++i) s = s + p[i];
+  const float norm_raw = sqrtf((float)s);
+  const float grad_norm = norm_raw * inv_loss_scale;
+  const float clip_coef = max_grad_norm > 0.f ? fminf(1.0f, max_grad_norm / (grad_norm + 1e-6f)) : 1.0f;
+  st->grad_norm = grad_norm;
+  st->clip_coef = clip_coef;
+  st->inv_scale_eff = inv_loss_scale * clip_coef;
+  if (*flag == 0) {
+    const float b1pow = st->b1pow * momentum, b2pow = st->b2pow * beta2;
+    st->step = st->step + 1;
+    st->b1pow = b1pow;
+    st->b2pow = b2pow;
+    st->bc1 = 1.0f - b1pow;
+    st->bc2 = 1.0f - b2pow;
+  }
+}
+
 // f16 re-pack of conv weights: master f32 [Cout][k*k*Cin] (k index = tap*Cin + cin) -> forward f16 [Cout_pad][Kpad] and, for
 // the backward-data conv, f16 [Cin_pad][Kpad_t] with wt[ci][(k*k-1-tap)*Cout + co] = w[co][tap*Cin + ci] (taps flipped,
 // channels swapped).  One 64 (Cout) x 64 (Cin) tile of one tap per trip: coalesced f32 reads, forward rows written straight
@@ -831,6 +1012,73 @@ extern "C" int od_grad_nonfinite(od_ctx* ctx, const float* g, long long n, int32
   hipLaunchKernelGGL(od_flag_clear_k, dim3(1), dim3(1), 0, (hipStream_t)stream, flag);
   OD_CHECK_LAUNCH();
   hipLaunchKernelGGL(od_grad_nonfinite_k, dim3(grid_for(n / 4 / 4 + 1)), dim3(256), 0, (hipStream_t)stream, g, n / 4, n, flag);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
+extern "C" size_t od_grad_stats_workspace_bytes(long long n) {
+  return n > 0 ? (size_t)grad_stats_groups(n) * sizeof(double) : 0;
+}
+
+extern "C" int od_grad_stats(od_ctx* ctx, const float* g, long long n, int32_t* flag, void* workspace, void* stream) {
+  OD_REQUIRE(ctx && g && flag && workspace && n > 0, "od_grad_stats: bad argument");
+  OD_REQUIRE(((uintptr_t)g & 15) == 0, "od_grad_stats: g must be 16-byte aligned");
+  OD_REQUIRE(((uintptr_t)workspace & 7) == 0, "od_grad_stats: workspace must be 8-byte aligned");
+  hipLaunchKernelGGL(od_flag_clear_k, dim3(1), dim3(1), 0, (hipStream_t)stream, flag);
+  OD_CHECK_LAUNCH();
+  hipLaunchKernelGGL(od_grad_stats_k, dim3(grad_stats_groups(n)), dim3(256), 0, (hipStream_t)stream, g, n / 4, n, flag,
+                     (double*)workspace);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
+// beta in [0, 1) (false for NaN)
+static bool unit_half_open(float b) { return b >= 0.f && b < 1.f; }
+
+extern "C" int od_optim_prepare(od_ctx* ctx, const od_optim_cfg* cfg, const void* workspace, long long n,
+                                const int32_t* flag, od_optim_state* state, void* stream) {
+  OD_REQUIRE(ctx && cfg && workspace && flag && state && n > 0, "od_optim_prepare: bad argument");
+  OD_REQUIRE(((uintptr_t)workspace & 7) == 0, "od_optim_prepare: workspace must be 8-byte aligned");
+  OD_REQUIRE(cfg->kind == OD_OPT_SGD || cfg->kind == OD_OPT_NESTEROV || cfg->kind == OD_OPT_ADAMW,
+             "od_optim_prepare: unknown optimizer kind %d", cfg->kind);
+  OD_REQUIRE(unit_half_open(cfg->momentum) && (cfg->kind != OD_OPT_ADAMW || unit_half_open(cfg->beta2)),
+             "od_optim_prepare: momentum / beta must be in [0, 1)");
+  hipLaunchKernelGGL(od_optim_prepare_k, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace,
+                     (int)grad_stats_groups(n), cfg->momentum, cfg->beta2, cfg->inv_loss_scale, cfg->max_grad_norm, flag,
+                     state);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
+template <int KIND>
+static void launch_optim(bool with_ema, dim3 grid, hipStream_t s, float* w, float* m, float* v, const float* g, float* ema,
+                         const od_sgd_seg* segs, const optim_hp& hp, const od_optim_state* state, const int32_t* skip) {
+  if (with_ema) hipLaunchKernelGGL((od_optim_multi_k<KIND, true>), grid, dim3(256), 0, s, w, m, v, g, ema, segs, hp, state, skip);
+  else hipLaunchKernelGGL((od_optim_multi_k<KIND, false>), grid, dim3(256), 0, s, w, m, v, g, ema, segs, hp, state, skip);
+}
+
+extern "C" int od_optim_step_multi(od_ctx* ctx, const od_optim_cfg* cfg, float* w, float* m, float* v, const float* g,
+                                   float* ema, const od_sgd_seg* segs, int nseg, const od_optim_state* state,
+                                   const int32_t* skip_if_nonzero, void* stream) {
+  OD_REQUIRE(ctx && cfg && w && m && g && segs && state, "od_optim_step_multi: bad argument");
+  OD_REQUIRE(nseg > 0 && nseg <= 65535, "od_optim_step_multi: nseg must be in 1..65535");
+  OD_REQUIRE(cfg->kind == OD_OPT_SGD || cfg->kind == OD_OPT_NESTEROV || cfg->kind == OD_OPT_ADAMW,
+             "od_optim_step_multi: unknown optimizer kind %d", cfg->kind);
+  const bool adam = cfg->kind == OD_OPT_ADAMW;
+  OD_REQUIRE(adam == (v != nullptr), "od_optim_step_multi: v is the second moment of OD_OPT_ADAMW: required there, NULL otherwise");
+  OD_REQUIRE(unit_half_open(cfg->momentum), "od_optim_step_multi: momentum (beta1) must be in [0, 1)");
+  OD_REQUIRE(!adam || (unit_half_open(cfg->beta2) && cfg->eps > 0.f), "od_optim_step_multi: beta2 must be in [0, 1) and eps > 0");
+  if (ema) {
+    OD_REQUIRE(cfg->ema_one_minus_decay >= 0.f && cfg->ema_one_minus_decay <= 1.f,  // (false for NaN)
+               "od_optim_step_multi: ema_one_minus_decay must be in [0, 1]");
+    OD_REQUIRE(ema != w && ema != m && ema != g && ema != v, "od_optim_step_multi: ema must be a buffer of its own");
+  }
+  const optim_hp hp = {cfg->momentum, cfg->beta2, 1.0f - cfg->momentum, 1.0f - cfg->beta2, cfg->eps, cfg->ema_one_minus_decay};
+  const dim3 grid(256, nseg);
+  const hipStream_t s = (hipStream_t)stream;
+  if (cfg->kind == OD_OPT_SGD) launch_optim<OD_OPT_SGD>(ema != nullptr, grid, s, w, m, v, g, ema, segs, hp, state, skip_if_nonzero);
+  else if (cfg->kind == OD_OPT_NESTEROV) launch_optim<OD_OPT_NESTEROV>(ema != nullptr, grid, s, w, m, v, g, ema, segs, hp, state, skip_if_nonzero);
+  else launch_optim<OD_OPT_ADAMW>(ema != nullptr, grid, s, w, m, v, g, ema, segs, hp, state, skip_if_nonzero);
   OD_CHECK_LAUNCH();
   return OD_OK;
 }

@@ -12,6 +12,7 @@ only gradients are exchanged.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -142,7 +143,8 @@ class Trainer:
                  head_act=("elu", 1.0), comm=None, world_size=1, grad_payload=None, dynamic_loss_scale=True,
                  lr_multipliers=None, prior_wh=None, ignore_regions=False, ign_thr=None, loss_weights=(1.0, 1.0, 1.0),
                  ema_decay=None, ema_warmup=True, assigner="max-iou", atss_topk=ATSS_TOPK, tal_topk=TAL_TOPK,
-                 tal_alpha=TAL_ALPHA, tal_beta=TAL_BETA, objectness="focal", quality="iou"):
+                 tal_alpha=TAL_ALPHA, tal_beta=TAL_BETA, objectness="focal", quality="iou", optimizer="sgd",
+                 betas=(0.9, 0.999), adam_eps=1e-8, clip_grad_norm=None):
         # ema_decay: None = no averaged model (no extra buffers, sgd() launches od_sgd_step_multi); 0 < ema_decay < 1 keeps
         # an exponential moving average of the masters (self.ema) and of the BatchNorm running statistics
         # (self.ema_run_stats), updated inside sgd() with the decay ema_decay_at(self.ema_updates, ema_decay, ema_warmup)
@@ -157,6 +159,12 @@ class Trainer:
         # computed between the forward pass (and the TAL encode) and the loss; "focal" keeps hard targets and launches nothing
         check_objectness_args(objectness, quality, assigner)
         self.objectness, self.quality = objectness, quality
+        # optimizer "sgd" | "nesterov" | "adamw" (momentum is the SGD kinds', betas / adam_eps are AdamW's); clip_grad_norm:
+        # None, or the global gradient norm above which a step is scaled down (torch's clip_grad_norm_).  The defaults run
+        # od_grad_nonfinite -> od_sgd_step_multi[_ema]; anything else od_grad_stats -> od_optim_prepare -> od_optim_step_multi
+        self.optimizer, self.betas, self.adam_eps, self.clip_grad_norm = check_optimizer_args(optimizer, betas, adam_eps,
+                                                                                             clip_grad_norm)
+        self._optim_path = self.optimizer != "sgd" or self.clip_grad_norm is not None
         self.ctx = Context.get(device)
         self.lib = self.ctx.lib
         self.device = torch.device(device)
@@ -241,6 +249,18 @@ class Trainer:
         self.ema = self.params.clone() if self.ema_decay is not None else None
         self.ema_run_stats = self.run_stats.clone() if self.ema_decay is not None else None
         self.ema_updates = 0
+        # the new optimizer path's buffers (none on the default path): AdamW's second moment, the device od_optim_state
+        # (int32 step, then seven f32: _lib.OptimState), the per-workgroup f64 partials of od_grad_stats
+        self.mom2 = torch.zeros_like(self.params) if self.optimizer == "adamw" else None
+        self.optim_state = self.last_grad_norm = self._stats_ws = None
+        if self._optim_path:
+            st0 = _lib.OptimState()
+            st0.b1pow = st0.b2pow = 1.0
+            self.optim_state = torch.frombuffer(bytearray(bytes(st0)), dtype=torch.int32).to(dev)
+            # the step's true gradient norm (unscaled, before clipping) as a device f32 view: read it when it is wanted
+            self.last_grad_norm = self.optim_state.view(torch.float32)[3:4]
+            self._stats_ws = torch.empty(self.lib.od_grad_stats_workspace_bytes(self.n_flat) // 8, dtype=torch.float64,
+                                         device=dev)
         # per-channel stand-ins (scale / shift / bias / sink) cover every layer's Cout, read in whole 256-channel pads: the
         # prediction conv of a many-class head has Cout = 8 * (NC + 6), beyond the backbone's widths from NC = 251
         maxpad = max(2048, max(desc.pad_to(s[2], 256) for s in self.specs.values()))
@@ -693,8 +713,12 @@ class Trainer:
         weight decay in a device table), one multi-layer re-pack launch."""
         inv = dp_effective_scale(self.loss_scale, self.world)  # grads are averaged over ranks
         # after the all-reduce, so every rank sees the same flag: Inf / NaN anywhere -> this step's update is skipped
-        _lib.check(self.lib.od_grad_nonfinite(self.ctx.handle, self.grads.data_ptr(), self.n_flat, self.nonfinite.data_ptr(),
-                                              _stream_ptr()), "od_grad_nonfinite")
+        if self._optim_path:  # the same scan, with the sum of squares the global norm is taken from
+            _lib.check(self.lib.od_grad_stats(self.ctx.handle, self.grads.data_ptr(), self.n_flat, self.nonfinite.data_ptr(),
+                                              self._stats_ws.data_ptr(), _stream_ptr()), "od_grad_stats")
+        else:
+            _lib.check(self.lib.od_grad_nonfinite(self.ctx.handle, self.grads.data_ptr(), self.n_flat,
+                                                  self.nonfinite.data_ptr(), _stream_ptr()), "od_grad_nonfinite")
         key = (self.lr, self.weight_decay, tuple(sorted(self.lr_multipliers.items())))
         if self._sgd_key != key:
             segs = []
@@ -705,7 +729,25 @@ class Trainer:
                 sg.weight_decay = self.weight_decay if kind == "w" else 0.0
                 segs.append(sg)
             self._sgd_table, self._sgd_n, self._sgd_key = self._device_table(segs), len(segs), key
-        if self.ema_decay is None:
+        omd = None if self.ema_decay is None else float(ema_omd(self.ema_updates, self.ema_decay, self.ema_warmup))
+        if self._optim_path:
+            # norm, clipping coefficient and bias correction are computed on the device (od_optim_prepare) from the
+            # identical all-reduced buffer in a fixed order: every rank gets the same bits, and the host waits for nothing
+            cfg = _lib.OptimCfg()
+            cfg.kind = _lib.OPTIMIZERS[self.optimizer]
+            cfg.momentum = self.betas[0] if self.optimizer == "adamw" else self.momentum
+            cfg.beta2, cfg.eps, cfg.inv_loss_scale = self.betas[1], self.adam_eps, inv
+            cfg.max_grad_norm = 0.0 if self.clip_grad_norm is None else self.clip_grad_norm
+            cfg.ema_one_minus_decay = 0.0 if omd is None else omd
+            _lib.check(self.lib.od_optim_prepare(self.ctx.handle, C.byref(cfg), self._stats_ws.data_ptr(), self.n_flat,
+                                                 self.nonfinite.data_ptr(), self.optim_state.data_ptr(), _stream_ptr()),
+                       "od_optim_prepare")
+            _lib.check(self.lib.od_optim_step_multi(self.ctx.handle, C.byref(cfg), self.params.data_ptr(), self.mom.data_ptr(),
+                                                    None if self.mom2 is None else self.mom2.data_ptr(),
+                                                    self.grads.data_ptr(), None if self.ema is None else self.ema.data_ptr(),
+                                                    self._sgd_table.data_ptr(), self._sgd_n, self.optim_state.data_ptr(),
+                                                    self.nonfinite.data_ptr(), _stream_ptr()), "od_optim_step_multi")
+        elif self.ema_decay is None:
             _lib.check(self.lib.od_sgd_step_multi(self.ctx.handle, self.params.data_ptr(), self.mom.data_ptr(),
                                                   self.grads.data_ptr(), self._sgd_table.data_ptr(), self._sgd_n,
                                                   self.momentum, inv, self.nonfinite.data_ptr(), _stream_ptr()),
@@ -714,7 +756,6 @@ class Trainer:
             # the decay follows the number of sgd() calls made so far, skipped steps INCLUDED: the host learns of a skip
             # LAG steps late (_poll_nonfinite), so a schedule that counted applied updates would lag the device by as
             # much.  The device skips the update itself.
-            omd = float(ema_omd(self.ema_updates, self.ema_decay, self.ema_warmup))
             _lib.check(self.lib.od_sgd_step_multi_ema(self.ctx.handle, self.params.data_ptr(), self.mom.data_ptr(),
                                                       self.grads.data_ptr(), self.ema.data_ptr(), self._sgd_table.data_ptr(),
                                                       self._sgd_n, self.momentum, inv, omd, self.nonfinite.data_ptr(),
@@ -808,7 +849,8 @@ class Trainer:
             if log_every and (start_step + i + 1) % log_every == 0:
                 l = hist[i].cpu().numpy()
                 log(f"step {start_step + i + 1}/{start_step + steps} lr {self.lr:.4g} loss {l[3]:.4f} (obj {l[0]:.4f} cls {l[1]:.4f} box {l[2]:.4f}) "
-                    f"loss_scale {self.loss_scale:g} skipped {self.skipped_steps}")
+                    f"loss_scale {self.loss_scale:g} skipped {self.skipped_steps}"
+                    + (f" grad_norm {float(self.last_grad_norm.item()):.4g}" if self._optim_path else ""))
         return hist.cpu().numpy()
 
     def export_params(self, ema=False):
@@ -863,6 +905,12 @@ class Trainer:
             sd[k] = int(getattr(self, k))
         sd["pending_flags"] = np.array(self.pending_flags(), np.int32)
         sd["ema_decay"] = self.ema_decay  # None = no averaged model (weights.save_state leaves a None out of the file)
+        sd["optimizer"] = self.optimizer
+        if self.mom2 is not None:
+            sd["mom2"] = self.mom2.cpu().numpy()
+        if self._optim_path:  # what od_optim_prepare carries from step to step; the other fields are rewritten every step
+            st = _lib.OptimState.from_buffer_copy(self.optim_state.cpu().numpy().tobytes())
+            sd["optim_state"] = np.array((st.step, st.b1pow, st.b2pow), OPTIM_STATE_DTYPE)  # a 0-d record: an .npz holds it
         sd.update(self._layout())
         return sd
 
@@ -879,10 +927,17 @@ class Trainer:
         if has_ema != (self.ema_decay is not None):
             raise ValueError("load_state_dict: the state " + ("has" if has_ema else "has no") + " averaged model, the trainer "
                              + ("has none (ema_decay=None)" if has_ema else "keeps one"))
+        theirs = str(np.asarray(sd["optimizer"]).item()) if "optimizer" in sd else "sgd"  # an older state is an SGD one
+        if theirs != self.optimizer:
+            raise ValueError(f"load_state_dict: the state is of optimizer {theirs!r}, this trainer runs {self.optimizer!r}")
         bufs = [("params", self.params), ("mom", self.mom), ("run_stats", self.run_stats)]
+        if self.mom2 is not None:
+            bufs += [("mom2", self.mom2)]
         if has_ema:
             bufs += [("ema", self.ema), ("ema_run_stats", self.ema_run_stats)]
         for k, t in bufs:
+            if k not in sd:
+                raise ValueError(f"load_state_dict: the state has no {k}")
             a = np.ascontiguousarray(sd[k], np.float32)
             if a.shape != tuple(t.shape):
                 raise ValueError(f"load_state_dict: {k} has shape {a.shape}, expected {tuple(t.shape)}")
@@ -896,8 +951,39 @@ class Trainer:
             setattr(self, k, int(sd[k]))
         if has_ema:
             self.ema_decay = float(sd["ema_decay"])
+        if self._optim_path:  # a state without the record (an SGD run without clipping) starts the count afresh
+            ost = np.asarray(sd["optim_state"] if "optim_state" in sd else np.array((0, 1.0, 1.0), OPTIM_STATE_DTYPE))
+            st = _lib.OptimState()
+            st.step, st.b1pow, st.b2pow = int(ost["step"]), float(ost["b1pow"]), float(ost["b2pow"])
+            st.bc1, st.bc2 = float(np.float32(1) - np.float32(st.b1pow)), float(np.float32(1) - np.float32(st.b2pow))
+            self.optim_state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
         self._repack()
         self._sgd_key = None
+
+
+# "optim_state" of a state_dict: what od_optim_prepare carries from step to step
+OPTIM_STATE_DTYPE = np.dtype([("step", np.int32), ("b1pow", np.float32), ("b2pow", np.float32)])
+
+
+def check_optimizer_args(optimizer, betas, adam_eps, clip_grad_norm):
+    """ValueError for an optimizer setting the trainer cannot run (host-only: no library is loaded).
+    -> (optimizer, (beta1, beta2), adam_eps, clip_grad_norm or None) as floats."""
+    if optimizer not in _lib.OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {sorted(_lib.OPTIMIZERS)}, got {optimizer!r}")
+    try:
+        b1, b2 = (float(b) for b in betas)
+    except (TypeError, ValueError):
+        raise ValueError(f"betas must be (beta1, beta2), got {betas!r}") from None
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"betas must lie in [0, 1), got {betas!r}")
+    eps = float(adam_eps)
+    if not (math.isfinite(eps) and eps > 0.0):
+        raise ValueError(f"adam_eps must be positive and finite, got {adam_eps!r}")
+    if clip_grad_norm is not None:
+        clip_grad_norm = float(clip_grad_norm)
+        if not (math.isfinite(clip_grad_norm) and clip_grad_norm > 0.0):
+            raise ValueError(f"clip_grad_norm must be None or positive and finite, got {clip_grad_norm!r}")
+    return optimizer, (b1, b2), eps, clip_grad_norm
 
 
 def check_objectness_args(objectness, quality, assigner):

@@ -88,7 +88,8 @@ def load(path):
 
 
 def save_state(path, sd):
-    """Trainer.state_dict() (flat f32 buffers, scalars, the int32 array of pending loss-scale flags, the layout record) ->
+    """Trainer.state_dict() (flat f32 buffers, scalars, the int32 array of pending loss-scale flags, the layout record, the
+    optimizer's name, AdamW's "mom2" and the "optim_state" record of the device-side step count and beta products) ->
     ONE .npz at exactly `path`.  A value of None (ema_decay of a trainer without an averaged model) is left out."""
     with open(pathlib.Path(path), "wb") as f:  # a file object: np.savez appends ".npz" to a bare name without it
         np.savez(f, **{k: np.asarray(v) for k, v in sd.items() if v is not None})

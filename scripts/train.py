@@ -83,6 +83,15 @@ def build_parser():
     p.add_argument("--ema", default=None, type=float, metavar="D",
                    help="keep an exponential moving average of the weights with decay D (0 < D < 1, warmed up from 0.1) and "
                         "write it to <out stem>_ema.npz beside the usual file")
+    p.add_argument("--optimizer", default="sgd", choices=("sgd", "nesterov", "adamw"),
+                   help="update rule: momentum SGD, Nesterov momentum (both with --momentum), or AdamW with decoupled "
+                        "--weight-decay (--beta1 / --beta2 / --adam-eps; default --lr 0.001 at batch 32)")
+    p.add_argument("--beta1", default=0.9, type=float, help="--optimizer adamw: decay of the first moment, in [0, 1)")
+    p.add_argument("--beta2", default=0.999, type=float, help="--optimizer adamw: decay of the second moment, in [0, 1)")
+    p.add_argument("--adam-eps", default=1e-8, type=float, help="--optimizer adamw: added to the root of the second moment")
+    p.add_argument("--clip-norm", default=None, type=float, metavar="X",
+                   help="scale a step's gradients down so that their global norm is at most X (computed on the device, "
+                        "the same on every rank); the log lines then show the unclipped norm")
     p.add_argument("--save-state-every", default=0, type=int, metavar="N",
                    help="every N steps rank 0 writes <result-dir>/state.npz (masters, momentum, BatchNorm statistics, the "
                         "average, loss scale, step) for --resume")
@@ -133,7 +142,10 @@ def _run(args):
     if args.lr is None:
         # "tal" assigns from the predictions, and its from-scratch run diverges at the rate the static assigners take; it
         # trains at a quarter of it (DESIGN.md "Task-aligned assignment")
-        args.lr = (0.005 if args.assigner == "tal" else 0.02) * args.batch_size * world / 32.0
+        # AdamW's step is the gradient's sign at first, not its size: 1e-3 at batch 32 (DESIGN.md "Optimizers and gradient
+        # clipping")
+        base = 0.001 if args.optimizer == "adamw" else (0.005 if args.assigner == "tal" else 0.02)
+        args.lr = base * args.batch_size * world / 32.0
     if args.warmup is None:
         args.warmup = 50 if args.batch_size * world >= 32 else 200
     class_names = None
@@ -171,12 +183,16 @@ def _run(args):
                  weight_decay=args.weight_decay, comm=comm, world_size=world, lr_multipliers=mult, prior_wh=prior_wh, box_mode=args.box_loss,
                  ignore_regions=args.ignore_regions, loss_weights=(1.0, 1.0, args.box_weight), assigner=args.assigner,
                  atss_topk=args.atss_topk, tal_topk=args.tal_topk, tal_alpha=args.tal_alpha, tal_beta=args.tal_beta,
-                 objectness=args.objectness, quality=args.quality,
+                 objectness=args.objectness, quality=args.quality, optimizer=args.optimizer,
+                 betas=(args.beta1, args.beta2), adam_eps=args.adam_eps, clip_grad_norm=args.clip_norm,
                  **({} if args.ema is None else {"ema_decay": args.ema}))
     start, flow_seed = 0, args.seed + rank
     if args.resume is not None:
         sd = W.load_state(args.resume)
-        tr.load_state_dict(sd)
+        try:
+            tr.load_state_dict(sd)
+        except ValueError as e:  # another architecture, another EMA switch, another optimizer: the trainer's own message
+            raise SystemExit(f"--resume {args.resume}: {e}") from None
         start = int(sd["step"])
         if start >= args.steps:
             raise SystemExit(f"{args.resume} is at step {start}: nothing left of --steps {args.steps}")
