@@ -700,6 +700,37 @@ typedef struct od_mosaic_params {
 int od_mosaic_params_bytes(void);
 int od_augment_mosaic(od_ctx* ctx, const uint8_t* src, const void* params, uint8_t* out, int B, int H, int W,
                       void* stream);
+/* K14b: affine warp + colour matrix + MixUp.  One od_warp_params per output image: n_frames (1 or 2) mosaic frames
+ * (frame[f]: tiles and split as in od_augment_mosaic, its own n_erase must be 0; a single image is the degenerate mosaic),
+ * each seen through the INVERSE affine matrix a[f] and the colour matrix k[f]; fill_rgb where a frame does not reach; the
+ * MixUp weights; one erase list for the final image.  Per output pixel (x, y), all f32 without contraction, in this order:
+ *  1. px = (float)x + 0.5f, py = (float)y + 0.5f
+ *  2. frame f: fx = (a0*px + a1*py) + a2, fy = (a3*px + a4*py) + a5 -- frame coordinates in OUTPUT-PIXEL units (not
+ *     normalised), so the identity matrix {1,0,0, 0,1,0} is exact
+ *  3. fx < 0 || fx >= W || fy < 0 || fy >= H: the frame's colour is fill_rgb; no colour matrix is applied to it
+ *  4. else right = fx >= split_x, low = fy >= split_y choose the tile (X0, Y0, Wt, Ht) as od_augment_mosaic does;
+ *     u = (fx - X0) / Wt, v = (fy - Y0) / Ht; c = the tile's od_augment_batch colour at (u, v), already rounded and clamped;
+ *     t[ch] = ((k[ch][0]*c0 + k[ch][1]*c1) + k[ch][2]*c2) + k[ch][3], rounded half up, clamped to [0, 255]
+ *  5. n_frames == 2: t = A*mix_a + B*mix_b of the two frames' finished colours, rounded half up, clamped
+ *  6. the erase list on normalised output coordinates, then the 3-byte store, as in od_augment_mosaic.
+ * With one frame, a = identity and k = identity (offset column 0) the output is od_augment_mosaic's for frame[0] and the
+ * erase list, byte for byte.  src / src_offset as in od_augment_batch.  Split range, n_frames and the tiles' n_erase are
+ * the caller's to keep valid. */
+typedef struct od_warp_params {
+  int32_t n_frames;
+  float mix_a, mix_b;
+  uint8_t fill_rgb[4];
+  float a[2][6];
+  float k[2][3][4];
+  od_mosaic_params frame[2];
+  int32_t n_erase;
+  int32_t pad_;
+  float erase[3][4];
+  uint8_t erase_rgb[3][4];
+} od_warp_params;
+int od_warp_params_bytes(void);
+int od_augment_warp(od_ctx* ctx, const uint8_t* src, const void* params, uint8_t* out, int B, int H, int W,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * K15: image decode + resize into the network input for ObjectDetector(image_decode="device") (reference

@@ -55,6 +55,14 @@ class MosaicParams(C.Structure):
                 ("pad_", C.c_int32), ("erase", (C.c_float * 4) * 3), ("erase_rgb", (C.c_uint8 * 4) * 3)]
 
 
+class WarpParams(C.Structure):
+    C_NAME = "od_warp_params"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
+    _fields_ = [("n_frames", C.c_int32), ("mix_a", C.c_float), ("mix_b", C.c_float), ("fill_rgb", C.c_uint8 * 4),
+                ("a", (C.c_float * 6) * 2), ("k", ((C.c_float * 4) * 3) * 2), ("frame", MosaicParams * 2),
+                ("n_erase", C.c_int32), ("pad_", C.c_int32), ("erase", (C.c_float * 4) * 3),
+                ("erase_rgb", (C.c_uint8 * 4) * 3)]
+
+
 class BneckDesc(C.Structure):
     C_NAME = "od_bneck_desc"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
     _fields_ = [
@@ -153,7 +161,7 @@ class SoftNmsCfg(C.Structure):
                 ("sigma", C.c_float), ("min_conf", C.c_float)]
 
 
-STRUCTS = (SoftNmsCfg, TileDesc, TtaView, ConvDesc, AugParams, MosaicParams, BneckDesc, StemDesc, SgdSeg, OptimState, OptimCfg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
+STRUCTS = (SoftNmsCfg, TileDesc, TtaView, ConvDesc, AugParams, MosaicParams, WarpParams, BneckDesc, StemDesc, SgdSeg, OptimState, OptimCfg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
 
 
 class OdError(RuntimeError):
@@ -311,6 +319,9 @@ _PROTOS = {
                                 C.c_void_p]),
     "od_aug_params_bytes": (C.c_int, []),
     "od_mosaic_params_bytes": (C.c_int, []),
+    "od_warp_params_bytes": (C.c_int, []),
+    "od_augment_warp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                  C.c_void_p]),
     "od_augment_mosaic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p]),
     "od_augment_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,

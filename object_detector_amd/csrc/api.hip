@@ -124,6 +124,11 @@ const std::vector<StructInfo>& od_struct_table() {
        {OD_F(od_mosaic_params, split_x), OD_F(od_mosaic_params, split_y), OD_F(od_mosaic_params, tile),
         OD_F(od_mosaic_params, n_erase), OD_F(od_mosaic_params, pad_), OD_F(od_mosaic_params, erase),
         OD_F(od_mosaic_params, erase_rgb)}},
+      {"od_warp_params", sizeof(od_warp_params),
+       {OD_F(od_warp_params, n_frames), OD_F(od_warp_params, mix_a), OD_F(od_warp_params, mix_b),
+        OD_F(od_warp_params, fill_rgb), OD_F(od_warp_params, a), OD_F(od_warp_params, k), OD_F(od_warp_params, frame),
+        OD_F(od_warp_params, n_erase), OD_F(od_warp_params, pad_), OD_F(od_warp_params, erase),
+        OD_F(od_warp_params, erase_rgb)}},
       {"od_img_desc", sizeof(od_img_desc),
        {OD_F(od_img_desc, kind), OD_F(od_img_desc, width), OD_F(od_img_desc, height), OD_F(od_img_desc, out_w),
         OD_F(od_img_desc, out_h), OD_F(od_img_desc, ncomp), OD_F(od_img_desc, samp_h), OD_F(od_img_desc, samp_v),

@@ -106,10 +106,79 @@ __global__ __launch_bounds__(256) void od_augment_mosaic_k(const uint8_t* __rest
   aug_erase_store(m.n_erase, m.erase, m.erase_rgb, x, y, H, W, c, out + (((long long)b * H + y) * W + x) * 3);
 }
 
+// round half up, clamp to a byte's range (aug_sample's last step)
+__device__ __forceinline__ float aug_round_u8(float t) { return fminf(fmaxf(floorf(t + 0.5f), 0.f), 255.f); }
+
+// K14b: affine warp + colour matrix + MixUp of one or two mosaic frames.  Per output pixel (x, y), all f32, in this order:
+//  1. px = (float)x + 0.5f, py = (float)y + 0.5f
+//  2. frame f: fx = (a0*px + a1*py) + a2, fy = (a3*px + a4*py) + a5   (frame coordinates in OUTPUT-PIXEL units, so the
+//     identity matrix gives fx = px, fy = py exactly)
+//  3. fx < 0 || fx >= W || fy < 0 || fy >= H: the frame's colour is fill_rgb (no colour matrix)
+//  4. else right = fx >= split_x, low = fy >= split_y pick the tile (X0, Y0, Wt, Ht) as od_augment_mosaic_k does;
+//     u = (fx - X0) / Wt, v = (fy - Y0) / Ht; c = aug_sample(tile, u, v) (whole numbers in [0, 255]);
+//     t[ch] = ((k[ch][0]*c0 + k[ch][1]*c1) + k[ch][2]*c2) + k[ch][3], round half up, clamp to [0, 255]
+//  5. two frames: t = A*mix_a + B*mix_b of the two finished colours, round half up, clamp
+//  6. the erase list on normalised output coordinates and the 3-byte store (aug_erase_store)
+// One frame's colour at (px, py).  The tile is wave-uniform except where a wavefront crosses a split line -- under
+// rotation most waves near one do -- so the mosaic kernel's scheme is kept: take the first unserved lane's tile through a
+// wave-uniform index (scalar loads of that tile's parameters), serve the lanes that want it, at most four rounds.  Lanes
+// outside the frame take the fill colour and never enter the loop.
+__device__ __forceinline__ void warp_frame(const uint8_t* __restrict__ src, const od_warp_params& w, int f, float px,
+                                           float py, int H, int W, float c[3]) {
+  const float* a = w.a[f];
+  const od_mosaic_params& m = w.frame[f];
+  const float fx = (a[0] * px + a[1] * py) + a[2];
+  const float fy = (a[3] * px + a[4] * py) + a[5];
+  const bool outside = fx < 0.f || fx >= (float)W || fy < 0.f || fy >= (float)H;
+  const int sx = m.split_x, sy = m.split_y;
+  const int right = fx >= (float)sx, low = fy >= (float)sy;
+  const int t = low * 2 + right;  // TL, TR, BL, BR
+  const int X0 = right ? sx : 0, Wt = right ? W - sx : sx;
+  const int Y0 = low ? sy : 0, Ht = low ? H - sy : sy;
+  const float u = (fx - (float)X0) / (float)Wt, v = (fy - (float)Y0) / (float)Ht;
+  c[0] = (float)w.fill_rgb[0];
+  c[1] = (float)w.fill_rgb[1];
+  c[2] = (float)w.fill_rgb[2];
+  for (bool done = outside; !done;) {
+    const int tu = __builtin_amdgcn_readfirstlane(t);
+    if (t == tu) {
+      float s[3];
+      aug_sample(src, m.tile[tu], u, v, s);
+      const float(*k)[4] = w.k[f];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch)
+        c[ch] = aug_round_u8(((k[ch][0] * s[0] + k[ch][1] * s[1]) + k[ch][2] * s[2]) + k[ch][3]);
+      done = true;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void od_augment_warp_k(const uint8_t* __restrict__ src,
+                                                         const od_warp_params* __restrict__ prm,
+                                                         uint8_t* __restrict__ out, int H, int W) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= H * W) return;
+  const int y = i / W, x = i - y * W;
+  const od_warp_params& w = prm[b];
+  const float px = (float)x + 0.5f, py = (float)y + 0.5f;
+  float c[3];
+  warp_frame(src, w, 0, px, py, H, W, c);
+  if (w.n_frames == 2) {  // wave-uniform: one image per blockIdx.y
+    float d[3];
+    warp_frame(src, w, 1, px, py, H, W, d);
+    const float ma = w.mix_a, mb = w.mix_b;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) c[ch] = aug_round_u8(c[ch] * ma + d[ch] * mb);
+  }
+  aug_erase_store(w.n_erase, w.erase, w.erase_rgb, x, y, H, W, c, out + (((long long)b * H + y) * W + x) * 3);
+}
+
 }  // namespace
 
 extern "C" int od_aug_params_bytes(void) { return (int)sizeof(od_aug_params); }
 extern "C" int od_mosaic_params_bytes(void) { return (int)sizeof(od_mosaic_params); }
+extern "C" int od_warp_params_bytes(void) { return (int)sizeof(od_warp_params); }
 
 extern "C" int od_augment_batch(od_ctx* ctx, const uint8_t* src, const void* params, uint8_t* out, int B, int H, int W,
                                 void* stream) {
@@ -125,6 +194,15 @@ extern "C" int od_augment_mosaic(od_ctx* ctx, const uint8_t* src, const void* pa
   OD_REQUIRE(ctx && src && params && out && B > 0 && B <= 65535 && H > 0 && W > 0, "od_augment_mosaic: bad argument");
   hipLaunchKernelGGL(od_augment_mosaic_k, dim3(od_ceil_div(H * W, 256), B), dim3(256), 0, (hipStream_t)stream, src,
                      (const od_mosaic_params*)params, out, H, W);
+  OD_CHECK_LAUNCH();
+  return OD_OK;
+}
+
+extern "C" int od_augment_warp(od_ctx* ctx, const uint8_t* src, const void* params, uint8_t* out, int B, int H, int W,
+                               void* stream) {
+  OD_REQUIRE(ctx && src && params && out && B > 0 && B <= 65535 && H > 0 && W > 0, "od_augment_warp: bad argument");
+  hipLaunchKernelGGL(od_augment_warp_k, dim3(od_ceil_div(H * W, 256), B), dim3(256), 0, (hipStream_t)stream, src,
+                     (const od_warp_params*)params, out, H, W);
   OD_CHECK_LAUNCH();
   return OD_OK;
 }

@@ -57,8 +57,9 @@ def print_scores(precisions, recalls, fscores, supports, class_names=None, print
     print_fn(f"{'avg':>{w}s}  {avg(precisions):9.3f} {avg(recalls):8.3f} {avg(fscores):9.3f} {int(np.sum(supports)):8d}")
 
 
-def plot_objects(base_image, classes, confs, bboxes, class_names=None):
-    """Draw boxes (normalised corner form) on an image (path or array) -> uint8 array."""
+def plot_objects(base_image, classes, confs, bboxes, class_names=None, color=None):
+    """Draw boxes (normalised corner form) on an image (path or array) -> uint8 array.  color: one (r, g, b) for every box
+    instead of a colour per class."""
     from PIL import Image, ImageDraw
     if isinstance(base_image, (str, os.PathLike)):
         img = Image.open(base_image).convert("RGB")
@@ -70,7 +71,7 @@ def plot_objects(base_image, classes, confs, bboxes, class_names=None):
         x1, y1, x2, y2 = (float(v) for v in bboxes[i])
         x1, x2, y1, y2 = min(x1, x2), max(x1, x2), min(y1, y2), max(y1, y2)  # an untrained net can decode inverted boxes
         c = int(classes[i]) if classes is not None else 0
-        col = tuple(int(v) for v in (np.array([37, 97, 173]) * (c + 1)) % 200 + 55)
+        col = tuple(int(v) for v in (np.array([37, 97, 173]) * (c + 1)) % 200 + 55) if color is None else tuple(color)
         d.rectangle([x1 * Wd, y1 * H, x2 * Wd, y2 * H], outline=col, width=2)
         label = class_names[c] if class_names is not None else str(c)
         if confs is not None:

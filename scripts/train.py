@@ -60,6 +60,14 @@ def build_parser():
                    help="decode and upload every image every epoch instead of keeping the decoded dataset in HBM")
     p.add_argument("--mosaic", default=0.0, type=float, metavar="P",
                    help="probability that a training image is a mosaic of four (od_augment_mosaic; off by default)")
+    p.add_argument("--affine", default=None, type=float, nargs=4, metavar=("DEG", "TRANSLATE", "SCALE", "SHEAR"),
+                   help="random affine warp of every training frame (od_augment_warp): rotation and shear in degrees, "
+                        "translation as a share of the frame, zoom in 1 +- SCALE; off by default")
+    p.add_argument("--hsv", default=None, type=float, nargs=3, metavar=("H", "S", "V"),
+                   help="hue (turns) / saturation / value jitter half-widths, e.g. 0.015 0.7 0.4; off by default")
+    p.add_argument("--mixup", default=0.0, type=float, metavar="P",
+                   help="probability that a training image is a MixUp of two frames; off by default")
+    p.add_argument("--mixup-beta", default=8.0, type=float, metavar="B", help="--mixup: the ratio is Beta(B, B)")
     p.add_argument("--ignore-regions", action="store_true",
                    help="difficult / iscrowd boxes and the slivers a mosaic leaves are ignore regions instead of positives")
     p.add_argument("--assigner", default="max-iou", choices=("max-iou", "atss", "tal"),
@@ -212,7 +220,11 @@ def _run(args):
     tal = args.assigner == "tal"
     gen =od_gen.create_generator(tuple(args.input_size), preprocess_input=None, encode_truth=None if tal else encode_truth,
                                   device=dev, on_device=True, device_cache=not args.no_device_cache, mosaic=args.mosaic,
-                                  ignore_regions=args.ignore_regions)
+                                  ignore_regions=args.ignore_regions,
+                                  affine=None if args.affine is None else dict(zip(("degrees", "translate", "scale", "shear"),
+                                                                                   args.affine)),
+                                  hsv=None if args.hsv is None else tuple(args.hsv), mixup=args.mixup,
+                                  mixup_beta=args.mixup_beta)
     batches, per_epoch = gen.flow(X, y, batch_size=args.batch_size, data_augmentation=True, shuffle=True, seed=flow_seed,
                                   prefetch=args.prefetch)
     log.info(f"{n} images on rank {rank} of {world}, {per_epoch} steps per epoch, {args.steps} steps, lr {args.lr}, "
@@ -249,7 +261,7 @@ def _run(args):
     ran = args.steps - start
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    if args.mosaic > 0:
+    if args.mosaic > 0 or gen.warp:
         log.info(f"mosaic: {json.dumps(gen.stats)}")
     batches.close()  # ends the generator's prefetch thread (a thread still issuing GPU work at interpreter exit aborts)
     k = max(1, min(20, ran // 10))
