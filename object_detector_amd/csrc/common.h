@@ -58,6 +58,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int od_ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int od_round_up(int a, int b) { return od_ceil_div(a, b) * b; }
+// workgroups of 256 threads for a grid-stride loop over nvec items: one item per thread up to 4096 workgroups
+static inline unsigned od_grid_for(long long nvec) {
+  const long long b = (nvec + 255) / 256;
+  return (unsigned)(b > 256 * 16 ? 256 * 16 : (b < 1 ? 1 : b));
+}
 
 // ---- launch records.  The forward entry points of the conv families and od_wide_add PREPARE an op (validate it, select
 //      the kernel, fill its parameter struct, raise its LDS limit) into launch records, then issue them.  A forward plan

@@ -1,6 +1,6 @@
-// K11 (elementwise part) + K12: training-side kernels around the MFMA convolutions.  All HBM-bound; NHWC f16
+// K11 (elementwise part) + K12 (re-pack part): training-side kernels around the MFMA convolutions.  All HBM-bound; NHWC f16
 // activations / gradients, f32 statistics and parameters.  Reductions are deterministic (per-workgroup partials summed
-// in a fixed order), so a training step is bit-reproducible on one GPU.
+// in a fixed order), so a training step is bit-reproducible on one GPU.  The weight update lives in optim.hip.
 //
 //   od_bn_stats        per-channel mean / rstd of z = conv(x) over (B,H,W) (BatchNorm in training mode), folded into the
 //                      (scale, shift) pair of the fused form  y = act(scale*z + shift) (+ residual)
@@ -8,15 +8,11 @@
 //   od_bn_bwd          da = dy * act'(.) ; dgamma = sum(da*xhat), dbeta = sum(da) ; dz = gamma*rstd*(da - dbeta/N - xhat*dgamma/N)
 //   od_down2_sum_add   gradient of the nearest 2x upsample in the FPN top-down add
 //   od_add_f16, od_pred_grad_to_level, od_cast_f32_bf16 / od_cast_bf16_f32   small elementwise passes
-//   od_sgd_step[_multi]      SGD + momentum + weight decay on f32 masters: one flat segment, or one launch over a device
-//                      table of segments (each with its own learning rate: the trainer folds the per-layer multipliers of
-//                      docs/MODEL.md:84-90 into it); od_grad_nonfinite / od_copy_if_nonzero guard a step that overflowed
-//   od_sgd_step_multi_ema    the same launch with an exponential moving average of the masters updated in the same pass;
-//                      od_ema_update is the average alone over a flat buffer (the BatchNorm running statistics)
-//   od_pack_weights[_multi]  f32 masters -> the f16 forward and backward-data packs of the convolutions
+//   od_pack_weights[_multi]  f32 masters -> the f16 forward and backward-data packs of the convolutions: one layer, or one
+//                      launch over a device table of layers
 //
-// reference: the Keras BatchNormalization / activation / optimizer machinery behind the (unseen) `fit` of
-// tk.dl.od.ObjectDetector; specified here by docs/MODEL.md:19-21,84-90.
+// reference: the Keras BatchNormalization / activation machinery behind the (unseen) `fit` of tk.dl.od.ObjectDetector;
+// specified here by docs/MODEL.md:19-21.
 #include "common.h"
 
 namespace {
@@ -414,313 +410,6 @@ __global__ __launch_bounds__(256) void od_add_f16_k(f16* __restrict__ a, const f
   }
 }
 
-// w -= lr * (m = momentum * m + g * inv_scale + wd * w)
-__device__ __forceinline__ void sgd_update(float& w, float& m, float g, float lr, float momentum, float wd, float inv_scale) {
-  const float grad = g * inv_scale + wd * w;
-  const float mv = momentum * m + grad;
-  m = mv;
-  w -= lr * mv;
-}
-
-__global__ __launch_bounds__(256) void od_sgd_k(float* __restrict__ w, float* __restrict__ m, const float* __restrict__ g,
-                                                long long n, float lr, float momentum, float wd, float inv_scale) {
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-    sgd_update(w[i], m[i], g[i], lr, momentum, wd, inv_scale);
-}
-
-// multi-tensor form: blockIdx.y = segment of the device table, blockIdx.x strides over its elements
-__global__ __launch_bounds__(256) void od_sgd_multi_k(float* __restrict__ w, float* __restrict__ m, const float* __restrict__ g,
-                                                      const od_sgd_seg* __restrict__ segs, float momentum, float inv_scale,
-                                                      const int32_t* __restrict__ skip) {
-  if (skip && *skip) return;  // a non-finite gradient was found (od_grad_nonfinite): leave weights and momentum untouched
-  const od_sgd_seg sg = segs[blockIdx.y];
-  float* ws = w + sg.offset;
-  float* ms = m + sg.offset;
-  const float* gs = g + sg.offset;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < sg.count; i += (long long)gridDim.x * 256)
-    sgd_update(ws[i], ms[i], gs[i], sg.lr, momentum, sg.weight_decay, inv_scale);
-}
-
-// e += omd * (x - e): three separately rounded f32 operations (this TU is built with -ffp-contract=off), so that e stays
-// bitwise where x == e -- decay * e + omd * x would not
-__device__ __forceinline__ void ema_update(float& e, float x, float omd) {
-  const float d = x - e;
-  const float p = omd * d;
-  e = e + p;
-}
-
-// Elements in front of the first 16-byte boundary of a run of `count` floats at `p` (0..3, at most count)
-__device__ __forceinline__ long long head_to_16(const float* p, long long count) {
-  const long long h = (4 - (long long)(((uintptr_t)p >> 2) & 3)) & 3;
-  return h < count ? h : count;
-}
-
-// od_sgd_multi_k plus the weight average in the same pass: 4 loads and 3 stores of 4 B per parameter where a separate EMA
-// launch would read w a third time.  Where the segment starts at the same offset from a 16-byte boundary in all four
-// buffers (the trainer's always do: offsets are multiples of 4 floats in 16-byte-aligned buffers) its aligned body moves
-// as 16-byte accesses and only the head (< 4 elements) and the tail (< 4) go one by one; any other segment goes one by
-// one as a whole.  Per element both paths run sgd_update then ema_update, so the bits do not depend on the path.
-__global__ __launch_bounds__(256) void od_sgd_multi_ema_k(float* __restrict__ w, float* __restrict__ m,
-                                                          const float* __restrict__ g, float* __restrict__ ema,
-                                                          const od_sgd_seg* __restrict__ segs, float momentum,
-                                                          float inv_scale, float omd, const int32_t* __restrict__ skip) {
-  if (skip && *skip) return;  // a skipped step leaves the average alone as well
-  const od_sgd_seg sg = segs[blockIdx.y];
-  float* ws = w + sg.offset;
-  float* ms = m + sg.offset;
-  const float* gs = g + sg.offset;
-  float* es = ema + sg.offset;
-  const long long first = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
-  const unsigned a = (unsigned)((uintptr_t)ws & 15);
-  if (((uintptr_t)ms & 15) != a || ((uintptr_t)gs & 15) != a || ((uintptr_t)es & 15) != a) {
-    for (long long i = first; i < sg.count; i += stride) {
-      sgd_update(ws[i], ms[i], gs[i], sg.lr, momentum, sg.weight_decay, inv_scale);
-      ema_update(es[i], ws[i], omd);
-    }
-    return;
-  }
-  const long long head = head_to_16(ws, sg.count);
-  const long long nvec = (sg.count - head) >> 2;
-  const long long tail0 = head + 4 * nvec;  // first element behind the aligned body
-  f32x4* w4 = (f32x4*)(ws + head);
-  f32x4* m4 = (f32x4*)(ms + head);
-  const f32x4* g4 = (const f32x4*)(gs + head);
-  f32x4* e4 = (f32x4*)(es + head);
-  for (long long i = first; i < nvec; i += stride) {
-    f32x4 wv = w4[i], mv = m4[i], ev = e4[i];
-    const f32x4 gv = g4[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float wk = wv[k], mk = mv[k], ek = ev[k];
-      sgd_update(wk, mk, gv[k], sg.lr, momentum, sg.weight_decay, inv_scale);
-      ema_update(ek, wk, omd);
-      wv[k] = wk, mv[k] = mk, ev[k] = ek;
-    }
-    w4[i] = wv;
-    m4[i] = mv;
-    e4[i] = ev;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < 8) {  // lanes 0..3: the head, lanes 4..7: the tail
-    const long long i = threadIdx.x < 4 ? (long long)threadIdx.x : tail0 + (threadIdx.x - 4);
-    if (threadIdx.x < 4 ? i < head : i < sg.count) {
-      sgd_update(ws[i], ms[i], gs[i], sg.lr, momentum, sg.weight_decay, inv_scale);
-      ema_update(es[i], ws[i], omd);
-    }
-  }
-}
-
-// ema[i] += omd * (x[i] - ema[i]) over a flat buffer, unless *skip != 0; same head / 16-byte body / tail split
-__global__ __launch_bounds__(256) void od_ema_k(float* __restrict__ ema, const float* __restrict__ x, long long n, float omd,
-                                                const int32_t* __restrict__ skip) {
-  if (skip && *skip) return;
-  const long long first = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
-  if ((((uintptr_t)ema ^ (uintptr_t)x) & 15) != 0) {
-    for (long long i = first; i < n; i += stride) ema_update(ema[i], x[i], omd);
-    return;
-  }
-  const long long head = head_to_16(ema, n);
-  const long long nvec = (n - head) >> 2;
-  const long long tail0 = head + 4 * nvec;
-  f32x4* e4 = (f32x4*)(ema + head);
-  const f32x4* x4 = (const f32x4*)(x + head);
-  for (long long i = first; i < nvec; i += stride) {
-    f32x4 ev = e4[i];
-    const f32x4 xv = x4[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float ek = ev[k];
-      ema_update(ek, xv[k], omd);
-      ev[k] = ek;
-    }
-    e4[i] = ev;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < 8) {
-    const long long i = threadIdx.x < 4 ? (long long)threadIdx.x : tail0 + (threadIdx.x - 4);
-    if (threadIdx.x < 4 ? i < head : i < n) ema_update(ema[i], x[i], omd);
-  }
-}
-
-// ---- od_optim_step_multi: the update rules beyond od_sgd_multi[_ema]_k, one kernel per (kind, with / without average) ----
-// What the host resolves once per launch: the constants every element's update reads (1 - beta computed in f32 on the host:
-// one rounded subtraction, as the header writes it)
-struct optim_hp {
-  float momentum;  // beta1 for AdamW
-  float beta2, omb1, omb2, eps;
-  float omd;  // the average's 1 - decay
-};
-
-// One element's update, each line one rounded f32 operation or two as the header splits them (-ffp-contract=off).  `v` is
-// touched by AdamW alone.
-template <int KIND>
-__device__ __forceinline__ void optim_update(float& w, float& m, float& v, float g, float lr, float wd, const optim_hp& hp,
-                                             float inv, float bc1, float bc2) {
-  if (KIND == OD_OPT_SGD) {
-    sgd_update(w, m, g, lr, hp.momentum, wd, inv);
-  } else if (KIND == OD_OPT_NESTEROV) {
-    const float grad = g * inv + wd * w;
-    const float mv = hp.momentum * m + grad;
-    m = mv;
-    const float u = grad + hp.momentum * mv;
-    w = w - lr * u;
-  } else {
-    const float gh = g * inv;
-    m = hp.momentum * m + hp.omb1 * gh;
-    v = hp.beta2 * v + hp.omb2 * (gh * gh);
-    const float mh = m / bc1;
-    const float vh = v / bc2;
-    const float den = sqrtf(vh) + hp.eps;
-    const float u = mh / den;
-    w = w - lr * (u + wd * w);
-  }
-}
-
-// The segment walk of od_sgd_multi_ema_k (head < 4 / 16-byte body / tail < 4 where every buffer of the segment sits at the
-// same distance from a 16-byte boundary, element by element otherwise) around optim_update<KIND>, then ema_update when EMA.
-// v is NULL unless KIND == OD_OPT_ADAMW, ema is NULL unless EMA: neither is then formed into an address that is read.
-template <int KIND, bool EMA>
-__global__ __launch_bounds__(256) void od_optim_multi_k(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
-                                                        const float* __restrict__ g, float* __restrict__ ema,
-                                                        const od_sgd_seg* __restrict__ segs, optim_hp hp,
-                                                        const od_optim_state* __restrict__ state,
-                                                        const int32_t* __restrict__ skip) {
-  constexpr bool ADAM = KIND == OD_OPT_ADAMW;
-  if (skip && *skip) return;  // a skipped step leaves weights, both moments and the average alone
-  const float inv = state->inv_scale_eff, bc1 = state->bc1, bc2 = state->bc2;
-  const od_sgd_seg sg = segs[blockIdx.y];
-  float* ws = w + sg.offset;
-  float* ms = m + sg.offset;
-  float* vs = ADAM ? v + sg.offset : nullptr;
-  const float* gs = g + sg.offset;
-  float* es = EMA ? ema + sg.offset : nullptr;
-  const long long first = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
-  auto one = [&](long long i) {
-    float dummy = 0.f;
-    optim_update<KIND>(ws[i], ms[i], ADAM ? vs[i] : dummy, gs[i], sg.lr, sg.weight_decay, hp, inv, bc1, bc2);
-    if (EMA) ema_update(es[i], ws[i], hp.omd);
-  };
-  const unsigned a = (unsigned)((uintptr_t)ws & 15);
-  if (((uintptr_t)ms & 15) != a || ((uintptr_t)gs & 15) != a || (ADAM && ((uintptr_t)vs & 15) != a) ||
-      (EMA && ((uintptr_t)es & 15) != a)) {
-    for (long long i = first; i < sg.count; i += stride) one(i);
-    return;
-  }
-  const long long head = head_to_16(ws, sg.count);
-  const long long nvec = (sg.count - head) >> 2;
-  const long long tail0 = head + 4 * nvec;  // first element behind the aligned body
-  f32x4* w4 = (f32x4*)(ws + head);
-  f32x4* m4 = (f32x4*)(ms + head);
-  f32x4* v4 = ADAM ? (f32x4*)(vs + head) : nullptr;
-  const f32x4* g4 = (const f32x4*)(gs + head);
-  f32x4* e4 = EMA ? (f32x4*)(es + head) : nullptr;
-  for (long long i = first; i < nvec; i += stride) {
-    f32x4 wv = w4[i], mv = m4[i], vv = {0.f, 0.f, 0.f, 0.f}, ev = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 gv = g4[i];
-    if (ADAM) vv = v4[i];
-    if (EMA) ev = e4[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float wk = wv[k], mk = mv[k], vk = vv[k], ek = ev[k];
-      optim_update<KIND>(wk, mk, vk, gv[k], sg.lr, sg.weight_decay, hp, inv, bc1, bc2);
-      if (EMA) ema_update(ek, wk, hp.omd);
-      wv[k] = wk, mv[k] = mk, vv[k] = vk, ev[k] = ek;
-    }
-    w4[i] = wv;
-    m4[i] = mv;
-    if (ADAM) v4[i] = vv;
-    if (EMA) e4[i] = ev;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < 8) {  // lanes 0..3: the head, lanes 4..7: the tail
-    const long long i = threadIdx.x < 4 ? (long long)threadIdx.x : tail0 + (threadIdx.x - 4);
-    if (threadIdx.x < 4 ? i < head : i < sg.count) one(i);
-  }
-}
-
-// ---- od_grad_stats / od_optim_prepare ----------------------------------------------------------------------------------
-// Workgroups of od_grad_stats_k: a function of n alone.  At most 1024 (4 per CU: enough 16-byte loads in flight to stream
-// from HBM) so that od_optim_prepare_k's ordered sum of the partials stays a few microseconds.
-#define OD_STATS_MAX_GROUPS 1024
-static unsigned grad_stats_groups(long long n) {
-  const long long b = (n / 4 + 1023) / 1024;  // one tile of 1024 vectors per workgroup before the grid starts to stride
-  return (unsigned)(b > OD_STATS_MAX_GROUPS ? OD_STATS_MAX_GROUPS : (b < 1 ? 1 : b));
-}
-
-__device__ __forceinline__ bool nonfinite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
-// od_grad_nonfinite_k plus the sum of squares.  Lane order: each lane adds its vectors tile by tile (below), the four
-// elements of a vector in index order, then (workgroup 0, lanes 0..2) its tail element; the 256 lane sums are folded in
-// LDS by halving (lane t += lane t + s for s = 128 .. 1).  All of it in f64, nothing atomic but the integer flag.
-__global__ __launch_bounds__(256) void od_grad_stats_k(const float* __restrict__ g, long long n4, long long n,
-                                                       int32_t* __restrict__ flag, double* __restrict__ partials) {
-  __shared__ double red[256];
-  bool bad = false;
-  double acc = 0.0;
-  const f32x4* g4 = (const f32x4*)g;
-  auto add = [&](const f32x4 v) {
-    bad = bad || nonfinite_bits(v.x) || nonfinite_bits(v.y) || nonfinite_bits(v.z) || nonfinite_bits(v.w);
-    const double x = (double)v.x, y = (double)v.y, z = (double)v.z, q = (double)v.w;
-    acc = acc + x * x;
-    acc = acc + y * y;
-    acc = acc + z * z;
-    acc = acc + q * q;
-  };
-  // a workgroup walks tiles of 1024 consecutive vectors (16 KiB) in grid-stride order; a lane takes vectors t, t + 256,
-  // t + 512, t + 768 of the tile: four loads in flight, added in that order
-  for (long long base = (long long)blockIdx.x * 1024 + threadIdx.x; base < n4; base += (long long)gridDim.x * 1024) {
-    if (base + 768 < n4) {
-      const f32x4 a = g4[base], b = g4[base + 256], c = g4[base + 512], d = g4[base + 768];
-      add(a), add(b), add(c), add(d);
-    } else {
-      for (long long i = base; i < n4 && i < base + 1024; i += 256) add(g4[i]);
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - 4 * n4)) {
-    const float t = g[4 * n4 + threadIdx.x];
-    bad = bad || nonfinite_bits(t);
-    acc = acc + (double)t * (double)t;
-  }
-  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
-}
-
-// One workgroup: the partials travel to LDS side by side, lane 0 adds them in ascending order and writes the scalars
-__global__ __launch_bounds__(256) void od_optim_prepare_k(const double* __restrict__ partials, int npart, float momentum,
-                                                          float beta2, float inv_loss_scale, float max_grad_norm,
-                                                          const int32_t* __restrict__ flag, od_optim_state* __restrict__ st) {
-  __shared__ double p[OD_STATS_MAX_GROUPS];
-  double r[OD_STATS_MAX_GROUPS / 256];  // all of a lane's loads in flight before the first is waited for
-#pragma unroll
-  for (int k = 0; k < OD_STATS_MAX_GROUPS / 256; ++k) {
-    const int i = 256 * k + (int)threadIdx.x;
-    r[k] = i < npart ? partials[i] : 0.0;
-  }
-#pragma unroll
-  for (int k = 0; k < OD_STATS_MAX_GROUPS / 256; ++k) p[256 * k + threadIdx.x] = r[k];
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double s = 0.0;
-  for (int i = 0; i < npart; ++i) s = s + p[i];
-  const float norm_raw = sqrtf((float)s);
-  const float grad_norm = norm_raw * inv_loss_scale;
-  const float clip_coef = max_grad_norm > 0.f ? fminf(1.0f, max_grad_norm / (grad_norm + 1e-6f)) : 1.0f;
-  st->grad_norm = grad_norm;
-  st->clip_coef = clip_coef;
-  st->inv_scale_eff = inv_loss_scale * clip_coef;
-  if (*flag == 0) {
-    const float b1pow = st->b1pow * momentum, b2pow = st->b2pow * beta2;
-    st->step = st->step + 1;
-    st->b1pow = b1pow;
-    st->b2pow = b2pow;
-    st->bc1 = 1.0f - b1pow;
-    st->bc2 = 1.0f - b2pow;
-  }
-}
-
 // f16 re-pack of conv weights: master f32 [Cout][k*k*Cin] (k index = tap*Cin + cin) -> forward f16 [Cout_pad][Kpad] and, for
 // the backward-data conv, f16 [Cin_pad][Kpad_t] with wt[ci][(k*k-1-tap)*Cout + co] = w[co][tap*Cin + ci] (taps flipped,
 // channels swapped).  One 64 (Cout) x 64 (Cin) tile of one tap per trip: coalesced f32 reads, forward rows written straight
@@ -809,11 +498,6 @@ __global__ __launch_bounds__(256) void od_pred_grad_level_k(const float* __restr
     asm volatile("" : "+v"(v));
     dz[i] = (f16)v;
   }
-}
-
-unsigned grid_for(long long nvec) {
-  long long b = (nvec + 255) / 256;
-  return (unsigned)(b > 256 * 16 ? 256 * 16 : (b < 1 ? 1 : b));
 }
 
 }  // namespace
@@ -934,7 +618,7 @@ extern "C" int od_down2_sum_add(od_ctx* ctx, const void* d, void* dup, int B, in
                                 void* stream) {
   OD_REQUIRE(ctx && d && dup && B > 0 && Hh > 0 && Wh > 0 && C > 0 && C % 8 == 0, "od_down2_sum_add: bad argument");
   const long long nvec = (long long)B * Hh * Wh * (C / 8);
-  hipLaunchKernelGGL(od_down2_sum_add_k, dim3(grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const f16*)d, (f16*)dup,
+  hipLaunchKernelGGL(od_down2_sum_add_k, dim3(od_grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const f16*)d, (f16*)dup,
                      nvec, Hh, Wh, C / 8, accumulate);
   OD_CHECK_LAUNCH();
   return OD_OK;
@@ -942,158 +626,7 @@ extern "C" int od_down2_sum_add(od_ctx* ctx, const void* d, void* dup, int B, in
 
 extern "C" int od_add_f16(od_ctx* ctx, void* a, const void* b, long long n, void* stream) {
   OD_REQUIRE(ctx && a && b && n > 0 && n % 8 == 0, "od_add_f16: n must be a positive multiple of 8");
-  hipLaunchKernelGGL(od_add_f16_k, dim3(grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (f16*)a, (const f16*)b, n / 8);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
-}
-
-extern "C" int od_sgd_step(od_ctx* ctx, float* w, float* m, const float* g, long long n, float lr, float momentum,
-                           float weight_decay, float inv_loss_scale, void* stream) {
-  OD_REQUIRE(ctx && w && m && g && n > 0, "od_sgd_step: bad argument");
-  hipLaunchKernelGGL(od_sgd_k, dim3(grid_for((n + 7) / 8)), dim3(256), 0, (hipStream_t)stream, w, m, g, n, lr, momentum,
-                     weight_decay, inv_loss_scale);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
-}
-
-extern "C" int od_sgd_step_multi(od_ctx* ctx, float* w, float* m, const float* g, const od_sgd_seg* segs, int nseg,
-                                 float momentum, float inv_loss_scale, const int32_t* skip_if_nonzero, void* stream) {
-  OD_REQUIRE(ctx && w && m && g && segs && nseg > 0 && nseg <= 65535, "od_sgd_step_multi: bad argument");
-  hipLaunchKernelGGL(od_sgd_multi_k, dim3(256, nseg), dim3(256), 0, (hipStream_t)stream, w, m, g, segs, momentum,
-                     inv_loss_scale, skip_if_nonzero);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
-}
-
-extern "C" int od_sgd_step_multi_ema(od_ctx* ctx, float* w, float* m, const float* g, float* ema, const od_sgd_seg* segs,
-                                     int nseg, float momentum, float inv_loss_scale, float ema_one_minus_decay,
-                                     const int32_t* skip_if_nonzero, void* stream) {
-  OD_REQUIRE(ctx && w && m && g && ema && segs && nseg > 0 && nseg <= 65535, "od_sgd_step_multi_ema: bad argument");
-  OD_REQUIRE(ema_one_minus_decay >= 0.f && ema_one_minus_decay <= 1.f,  // (false for NaN)
-             "od_sgd_step_multi_ema: ema_one_minus_decay must be in [0, 1]");
-  OD_REQUIRE(ema != w && ema != m && ema != g, "od_sgd_step_multi_ema: ema must be a buffer of its own");
-  hipLaunchKernelGGL(od_sgd_multi_ema_k, dim3(256, nseg), dim3(256), 0, (hipStream_t)stream, w, m, g, ema, segs, momentum,
-                     inv_loss_scale, ema_one_minus_decay, skip_if_nonzero);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
-}
-
-extern "C" int od_ema_update(od_ctx* ctx, float* ema, const float* x, long long n, float one_minus_decay,
-                             const int32_t* skip_if_nonzero, void* stream) {
-  OD_REQUIRE(ctx && ema && x && n > 0, "od_ema_update: bad argument");
-  OD_REQUIRE(one_minus_decay >= 0.f && one_minus_decay <= 1.f, "od_ema_update: one_minus_decay must be in [0, 1]");
-  OD_REQUIRE(ema != x, "od_ema_update: ema must be a buffer of its own");
-  hipLaunchKernelGGL(od_ema_k, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, ema, x, n, one_minus_decay,
-                     skip_if_nonzero);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
-}
-
-// flag[0] = 1 when any of g[0..n) is Inf or NaN, else 0 (flag is cleared by the first launch, set by the second)
-__global__ void od_flag_clear_k(int32_t* flag) { *flag = 0; }
-__global__ __launch_bounds__(256) void od_grad_nonfinite_k(const float* __restrict__ g, long long n4, long long n,
-                                                           int32_t* __restrict__ flag) {
-  bool bad = false;
-  const f32x4* g4 = (const f32x4*)g;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    const f32x4 v = g4[i];
-    // exponent field all ones <=> Inf or NaN
-    bad = bad || (__float_as_uint(v.x) & 0x7f800000u) == 0x7f800000u || (__float_as_uint(v.y) & 0x7f800000u) == 0x7f800000u ||
-          (__float_as_uint(v.z) & 0x7f800000u) == 0x7f800000u || (__float_as_uint(v.w) & 0x7f800000u) == 0x7f800000u;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (int)(n - 4 * n4))
-    bad = bad || (__float_as_uint(g[4 * n4 + threadIdx.x]) & 0x7f800000u) == 0x7f800000u;
-  if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-}
-
-extern "C" int od_grad_nonfinite(od_ctx* ctx, const float* g, long long n, int32_t* flag, void* stream) {
-  OD_REQUIRE(ctx && g && flag && n > 0, "od_grad_nonfinite: bad argument");
-  OD_REQUIRE(((uintptr_t)g & 15) == 0, "od_grad_nonfinite: g must be 16-byte aligned");
-  hipLaunchKernelGGL(od_flag_clear_k, dim3(1), dim3(1), 0, (hipStream_t)stream, flag);
-  OD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(od_grad_nonfinite_k, dim3(grid_for(n / 4 / 4 + 1)), dim3(256), 0, (hipStream_t)stream, g, n / 4, n, flag);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
-}
-
-extern "C" size_t od_grad_stats_workspace_bytes(long long n) {
-  return n > 0 ? (size_t)grad_stats_groups(n) * sizeof(double) : 0;
-}
-
-extern "C" int od_grad_stats(od_ctx* ctx, const float* g, long long n, int32_t* flag, void* workspace, void* stream) {
-  OD_REQUIRE(ctx && g && flag && workspace && n > 0, "od_grad_stats: bad argument");
-  OD_REQUIRE(((uintptr_t)g & 15) == 0, "od_grad_stats: g must be 16-byte aligned");
-  OD_REQUIRE(((uintptr_t)workspace & 7) == 0, "od_grad_stats: workspace must be 8-byte aligned");
-  hipLaunchKernelGGL(od_flag_clear_k, dim3(1), dim3(1), 0, (hipStream_t)stream, flag);
-  OD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(od_grad_stats_k, dim3(grad_stats_groups(n)), dim3(256), 0, (hipStream_t)stream, g, n / 4, n, flag,
-                     (double*)workspace);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
-}
-
-// beta in [0, 1) (false for NaN)
-static bool unit_half_open(float b) { return b >= 0.f && b < 1.f; }
-
-extern "C" int od_optim_prepare(od_ctx* ctx, const od_optim_cfg* cfg, const void* workspace, long long n,
-                                const int32_t* flag, od_optim_state* state, void* stream) {
-  OD_REQUIRE(ctx && cfg && workspace && flag && state && n > 0, "od_optim_prepare: bad argument");
-  OD_REQUIRE(((uintptr_t)workspace & 7) == 0, "od_optim_prepare: workspace must be 8-byte aligned");
-  OD_REQUIRE(cfg->kind == OD_OPT_SGD || cfg->kind == OD_OPT_NESTEROV || cfg->kind == OD_OPT_ADAMW,
-             "od_optim_prepare: unknown optimizer kind %d", cfg->kind);
-  OD_REQUIRE(unit_half_open(cfg->momentum) && (cfg->kind != OD_OPT_ADAMW || unit_half_open(cfg->beta2)),
-             "od_optim_prepare: momentum / beta must be in [0, 1)");
-  hipLaunchKernelGGL(od_optim_prepare_k, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace,
-                     (int)grad_stats_groups(n), cfg->momentum, cfg->beta2, cfg->inv_loss_scale, cfg->max_grad_norm, flag,
-                     state);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
-}
-
-template <int KIND>
-static void launch_optim(bool with_ema, dim3 grid, hipStream_t s, float* w, float* m, float* v, const float* g, float* ema,
-                         const od_sgd_seg* segs, const optim_hp& hp, const od_optim_state* state, const int32_t* skip) {
-  if (with_ema) hipLaunchKernelGGL((od_optim_multi_k<KIND, true>), grid, dim3(256), 0, s, w, m, v, g, ema, segs, hp, state, skip);
-  else hipLaunchKernelGGL((od_optim_multi_k<KIND, false>), grid, dim3(256), 0, s, w, m, v, g, ema, segs, hp, state, skip);
-}
-
-extern "C" int od_optim_step_multi(od_ctx* ctx, const od_optim_cfg* cfg, float* w, float* m, float* v, const float* g,
-                                   float* ema, const od_sgd_seg* segs, int nseg, const od_optim_state* state,
-                                   const int32_t* skip_if_nonzero, void* stream) {
-  OD_REQUIRE(ctx && cfg && w && m && g && segs && state, "od_optim_step_multi: bad argument");
-  OD_REQUIRE(nseg > 0 && nseg <= 65535, "od_optim_step_multi: nseg must be in 1..65535");
-  OD_REQUIRE(cfg->kind == OD_OPT_SGD || cfg->kind == OD_OPT_NESTEROV || cfg->kind == OD_OPT_ADAMW,
-             "od_optim_step_multi: unknown optimizer kind %d", cfg->kind);
-  const bool adam = cfg->kind == OD_OPT_ADAMW;
-  OD_REQUIRE(adam == (v != nullptr), "od_optim_step_multi: v is the second moment of OD_OPT_ADAMW: required there, NULL otherwise");
-  OD_REQUIRE(unit_half_open(cfg->momentum), "od_optim_step_multi: momentum (beta1) must be in [0, 1)");
-  OD_REQUIRE(!adam || (unit_half_open(cfg->beta2) && cfg->eps > 0.f), "od_optim_step_multi: beta2 must be in [0, 1) and eps > 0");
-  if (ema) {
-    OD_REQUIRE(cfg->ema_one_minus_decay >= 0.f && cfg->ema_one_minus_decay <= 1.f,  // (false for NaN)
-               "od_optim_step_multi: ema_one_minus_decay must be in [0, 1]");
-    OD_REQUIRE(ema != w && ema != m && ema != g && ema != v, "od_optim_step_multi: ema must be a buffer of its own");
-  }
-  const optim_hp hp = {cfg->momentum, cfg->beta2, 1.0f - cfg->momentum, 1.0f - cfg->beta2, cfg->eps, cfg->ema_one_minus_decay};
-  const dim3 grid(256, nseg);
-  const hipStream_t s = (hipStream_t)stream;
-  if (cfg->kind == OD_OPT_SGD) launch_optim<OD_OPT_SGD>(ema != nullptr, grid, s, w, m, v, g, ema, segs, hp, state, skip_if_nonzero);
-  else if (cfg->kind == OD_OPT_NESTEROV) launch_optim<OD_OPT_NESTEROV>(ema != nullptr, grid, s, w, m, v, g, ema, segs, hp, state, skip_if_nonzero);
-  else launch_optim<OD_OPT_ADAMW>(ema != nullptr, grid, s, w, m, v, g, ema, segs, hp, state, skip_if_nonzero);
-  OD_CHECK_LAUNCH();
-  return OD_OK;
-}
-
-// dst[0..n) = src[0..n) when *flag != 0 (no-op otherwise): the trainer restores the BatchNorm running statistics of a
-// step whose update was skipped (the forward pass that overflowed has already folded its batch statistics into them)
-__global__ __launch_bounds__(256) void od_copy_if_k(float* __restrict__ dst, const float* __restrict__ src, long long n,
-                                                    const int32_t* __restrict__ flag) {
-  if (*flag == 0) return;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dst[i] = src[i];
-}
-
-extern "C" int od_copy_if_nonzero(od_ctx* ctx, float* dst, const float* src, long long n, const int32_t* flag, void* stream) {
-  OD_REQUIRE(ctx && dst && src && flag && n > 0, "od_copy_if_nonzero: bad argument");
-  hipLaunchKernelGGL(od_copy_if_k, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, dst, src, n, flag);
+  hipLaunchKernelGGL(od_add_f16_k, dim3(od_grid_for(n / 8)), dim3(256), 0, (hipStream_t)stream, (f16*)a, (const f16*)b, n / 8);
   OD_CHECK_LAUNCH();
   return OD_OK;
 }
@@ -1116,14 +649,14 @@ __global__ __launch_bounds__(256) void od_bf16_to_f32_k(const uint16_t* __restri
 
 extern "C" int od_cast_f32_bf16(od_ctx* ctx, const float* src, void* dst, long long n, void* stream) {
   OD_REQUIRE(ctx && src && dst && n > 0, "od_cast_f32_bf16: bad argument");
-  hipLaunchKernelGGL(od_f32_to_bf16_k, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, src, (uint16_t*)dst, n);
+  hipLaunchKernelGGL(od_f32_to_bf16_k, dim3(od_grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, src, (uint16_t*)dst, n);
   OD_CHECK_LAUNCH();
   return OD_OK;
 }
 
 extern "C" int od_cast_bf16_f32(od_ctx* ctx, const void* src, float* dst, long long n, void* stream) {
   OD_REQUIRE(ctx && src && dst && n > 0, "od_cast_bf16_f32: bad argument");
-  hipLaunchKernelGGL(od_bf16_to_f32_k, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, dst,
+  hipLaunchKernelGGL(od_bf16_to_f32_k, dim3(od_grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, dst,
                      n);
   OD_CHECK_LAUNCH();
   return OD_OK;
@@ -1154,7 +687,7 @@ extern "C" int od_pred_grad_to_level(od_ctx* ctx, const float* grad_pred, void* 
   OD_REQUIRE(ctx && grad_pred && dz && B > 0 && P > 0 && C > 0 && rows > 0 && row_off >= 0 && row_off + rows <= P,
              "od_pred_grad_to_level: bad argument");
   const long long n = (long long)rows * C;
-  hipLaunchKernelGGL(od_pred_grad_level_k, dim3(grid_for(((long long)B * n + 7) / 8)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(od_pred_grad_level_k, dim3(od_grid_for(((long long)B * n + 7) / 8)), dim3(256), 0, (hipStream_t)stream,
                      grad_pred, (f16*)dz, B, (long long)P * C, (long long)row_off * C, n, loss_scale);
   OD_CHECK_LAUNCH();
   return OD_OK;

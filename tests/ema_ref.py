@@ -1,7 +1,7 @@
-"""Restated reference of the weight average (od_sgd_step_multi_ema / od_ema_update of csrc/train.hip and
+"""Restated reference of the weight average (od_sgd_step_multi_ema / od_ema_update of csrc/optim.hip and
 trainer.ema_decay_at), in numpy, without a GPU.
 
-The update is three separately rounded f32 operations, d = w - e; p = omd * d; e = e + p (train.hip is built with
+The update is three separately rounded f32 operations, d = w - e; p = omd * d; e = e + p (optim.hip is built with
 -ffp-contract=off), which numpy float32 arithmetic reproduces one rounding per operation: the GPU tests compare uint32 views
 with no tolerance.  This form, not decay * e + omd * w, is the contract: it leaves e bitwise unchanged where w == e.
 With the inputs of optim_ref.values (|x| in [1e-6, 1e3]) no intermediate is subnormal for the omd values the tests use.

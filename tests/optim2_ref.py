@@ -1,8 +1,8 @@
-"""Restated reference of the optimizer path beyond plain momentum SGD (csrc/train.hip), in numpy, without a GPU:
+"""Restated reference of the optimizer path beyond plain momentum SGD (csrc/optim.hip), in numpy, without a GPU:
 
   od_grad_stats -> od_optim_prepare -> od_optim_step_multi (OD_OPT_SGD | OD_OPT_NESTEROV | OD_OPT_ADAMW)
 
-As in optim_ref.py: train.hip is built with -ffp-contract=off, every f32 expression of these kernels is a sequence of
+As in optim_ref.py: optim.hip is built with -ffp-contract=off, every f32 expression of these kernels is a sequence of
 correctly rounded IEEE operations (division and square root included), and numpy float32 arithmetic is the same sequence,
 so the GPU tests compare `uint32` views with no tolerance.  The one f64 quantity is the sum of squares; the GPU tests that
 compare it bit for bit use inputs whose sum is exact in f64 in any order.

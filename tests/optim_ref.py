@@ -1,8 +1,9 @@
-"""Restated reference of the weight-update path (csrc/train.hip), in numpy, without a GPU:
+"""Restated reference of the weight-update path (csrc/optim.hip; the re-pack and the casts: csrc/train.hip), in numpy,
+without a GPU:
 
   od_grad_nonfinite -> od_sgd_step[_multi] -> od_copy_if_nonzero -> od_pack_weights[_multi] -> host loss-scale control
 
-train.hip is compiled with -ffp-contract=off, so every f32 expression of these kernels is a sequence of correctly rounded
+Both files are compiled with -ffp-contract=off, so every f32 expression of these kernels is a sequence of correctly rounded
 IEEE operations.  numpy `float32` arithmetic is the same sequence, one rounding per operation, so the GPU tests compare
 results as integer views (`uint32` / `uint16`) with no tolerance; signed zeros count.
 
@@ -28,7 +29,7 @@ def values(rng, n, lo=-6.0, hi=3.0):
 
 
 def sgd_ref(w, m, g, lr, momentum, wd, inv):
-    """`sgd_update` of csrc/train.hip: grad = g*inv + wd*w; mv = momentum*m + grad; m = mv; w = w - lr*mv, each operation
+    """`sgd_update` of csrc/optim.hip: grad = g*inv + wd*w; mv = momentum*m + grad; m = mv; w = w - lr*mv, each operation
     rounded once to f32.  Arrays and scalars are np.float32 (the scalars as ctypes c_float rounds them).  -> new (w, m)."""
     for a in (w, m, g):
         assert a.dtype == F32

@@ -1,6 +1,6 @@
 """GPU: od_grad_stats, od_optim_prepare and od_optim_step_multi against tests/optim2_ref.py, bit for bit, through the C ABI.
 
-As test_gpu_optimizer_exact.py: train.hip is built with -ffp-contract=off, every f32 expression is a sequence of correctly
+As test_gpu_optimizer_exact.py: optim.hip is built with -ffp-contract=off, every f32 expression is a sequence of correctly
 rounded operations (division and square root included) that numpy float32 reproduces, so results are compared as uint32
 views with no tolerance.  Update inputs have magnitudes 10 ** uniform(-4, 2) with lr <= 0.1, so that no intermediate is
 subnormal: the smallest is (1 - beta2) * gh**2 >= 1e-3 * (1e-4 * inv)**2 with inv = 1/8, about 1.6e-13.  The one f64 sum

@@ -4,7 +4,7 @@ through the C ABI:
   od_sgd_step, od_sgd_step_multi, od_grad_nonfinite, od_copy_if_nonzero, od_cast_f32_bf16 / od_cast_bf16_f32, od_add_f16,
   od_down2_sum_add, od_pack_weights, od_pack_weights_multi
 
-train.hip is built with -ffp-contract=off, so every f32 expression is a sequence of correctly rounded operations that
+optim.hip and train.hip are built with -ffp-contract=off, so every f32 expression is a sequence of correctly rounded operations that
 numpy float32 reproduces: results are compared as uint32 / uint16 views (signed zeros count), with no tolerance anywhere.
 Input magnitudes are 10 ** uniform(-6, 3) with a random sign and lr <= 0.1, so that no input, intermediate or result of the
 f32 arithmetic is subnormal.  Every output lies inside a larger buffer whose guards on both sides are compared too.
@@ -102,6 +102,28 @@ def test_sgd_step_exact(cuda, momentum, wd):
             gd_.check(_u32(g), f"g n={n} step {step}")
 
 
+@pytest.mark.parametrize("skew", [(0, 0, 0), (1, 1, 1), (3, 3, 3), (0, 1, 0), (2, 2, 1)], ids=str)
+def test_sgd_step_phases(cuda, skew):
+    """(w, m, g) each `skew` floats behind a 16-byte boundary.  A shared phase gives a head of 0, 3 or 1 elements, a 16-byte
+    body that may be empty (n < 4 + head) and a tail of 0 .. 3; two buffers out of phase send the whole run one by one.  Two
+    consecutive calls, same bits on every path, guards on both sides of all three buffers untouched."""
+    lib, h = _api(cuda)
+    rng = np.random.default_rng(23)
+    inv = 1.0 / 128.0
+    for n in (1, 2, 3, 4, 5, 7, 8, 9, 255, 257, 2051):
+        w, m = R.values(rng, n, -3, 1), R.values(rng, n, -4, 0)
+        wd_, md_ = Guarded(cuda, n, 4, P32, w, skew=skew[0]), Guarded(cuda, n, 4, P32, m, skew=skew[1])
+        assert wd_.ptr % 16 == 4 * skew[0] and md_.ptr % 16 == 4 * skew[1]
+        for step, lr in enumerate((0.1, 0.03)):
+            g = R.values(rng, n)
+            gd_ = Guarded(cuda, n, 4, P32, g, skew=skew[2])
+            assert lib.od_sgd_step(h, wd_.ptr, md_.ptr, gd_.ptr, n, lr, 0.9, 1e-4, inv, _s()) == 0
+            w, m = R.sgd_ref(w, m, g, lr, 0.9, 1e-4, inv)
+            wd_.check(_u32(w), f"w n={n} skew {skew} step {step}")
+            md_.check(_u32(m), f"m n={n} skew {skew} step {step}")
+            gd_.check(_u32(g), f"g n={n} skew {skew} step {step}")
+
+
 # ---- od_sgd_step_multi -------------------------------------------------------------------------------------------------
 SEG_COUNTS = (1, 3, 255, 256, 257, 4100, 65536, 65541, 2 * 65536 + 5)  # 256 x 256 threads per segment: 1, 2 and 3 sweeps
 SEG_LR = (0.1, 0.05, 0.0, 0.02, 0.013, 0.07, 0.001, 0.09, 0.033)
@@ -179,6 +201,35 @@ def test_sgd_multi_exact_two_calls(cuda, seg_case):
     # the lr = 0 segment kept its weights and still took the momentum; the decay = 0 one is not the decayed one
     o, n = c["offs"][2], SEG_COUNTS[2]
     assert np.array_equal(c["w"][1][o:o + n], c["w0"][o:o + n]) and not np.array_equal(c["m"][1][o:o + n], c["m0"][o:o + n])
+
+
+def _skewed(cuda, a, skew):
+    """The host buffer on the device behind `skew` extra floats: the base pointer is 4 * skew bytes off a 16-byte boundary."""
+    t = torch.empty(a.size + skew, dtype=torch.float32, device=cuda)
+    assert t.data_ptr() % 16 == 0
+    t = t[skew:]
+    t.copy_(torch.from_numpy(a.copy()))
+    assert t.data_ptr() % 16 == 4 * skew
+    return t
+
+
+@pytest.mark.parametrize("skew", [(1, 1, 1), (0, 0, 1), (1, 0, 1)], ids=str)
+def test_sgd_multi_misaligned_bases(cuda, seg_case, skew):
+    """The nine segments with the base pointers of (w, m, g) advanced by `skew` floats.  All by one: every segment shares a
+    phase that is not the boundary, so it has a scalar head, a 16-byte body and a scalar tail, and the seams are where an
+    element would be lost or done twice.  One buffer against the others: no common phase, every segment goes one by one.
+    Same bits; gaps, guards and the gradients bit-identical afterwards."""
+    lib, h = _api(cuda)
+    c = seg_case
+    tbl = _seg_table(cuda, c["offs"], SEG_COUNTS, SEG_LR, SEG_WD)
+    w, m = _skewed(cuda, c["w0"], skew[0]), _skewed(cuda, c["m0"], skew[1])
+    for step in range(2):
+        g = _skewed(cuda, c["g"][step], skew[2])
+        assert lib.od_sgd_step_multi(h, w.data_ptr(), m.data_ptr(), g.data_ptr(), tbl.data_ptr(), len(SEG_COUNTS), 0.9,
+                                     c["inv"], None, _s()) == 0
+        _same(_u32(w.cpu().numpy()), _u32(c["w"][step]), f"skew {skew} w after call {step}")
+        _same(_u32(m.cpu().numpy()), _u32(c["m"][step]), f"skew {skew} m after call {step}")
+        _same(_u32(g.cpu().numpy()), _u32(c["g"][step]), f"skew {skew} g after call {step}")
 
 
 @pytest.mark.parametrize("flag", [None, 0, 1, -1, 0x100], ids=str)
@@ -267,6 +318,42 @@ def test_grad_nonfinite_small_sizes(cuda):
         g.buf[g.lo + n:] = _i32(0x7fc00000)
         assert _nonfinite(lib, h, cuda, g.ptr, n) == (0, 0), n
         for pos in (range(n) if n <= 5 else (0, 3, 4, 511, 999, 1000, 1001, 1002)):
+            keep = int(g.buf[g.lo + pos].item())
+            g.buf[g.lo + pos] = _i32(BAD_BITS[k % 5])
+            assert _nonfinite(lib, h, cuda, g.ptr, n) == (0, 1), (n, pos, hex(BAD_BITS[k % 5]))
+            g.buf[g.lo + pos] = keep
+            k += 1
+        assert _nonfinite(lib, h, cuda, g.ptr, n) == (0, 0), n
+
+
+def _tile_edge_positions(n):
+    """Element 0, the first and last element of each 256-vector quarter of the last 1024-vector tile (ragged: a quarter may
+    be short or absent), and every tail element behind the last whole vector."""
+    n4 = n // 4
+    pos = {0}
+    t0 = (n4 - 1) // 1024 * 1024
+    for q in range(4):
+        a, b = t0 + 256 * q, min(t0 + 256 * (q + 1), n4)
+        if a < b:
+            pos |= {4 * a, 4 * b - 1}
+    return sorted(pos | set(range(4 * n4, n)))
+
+
+def test_grad_nonfinite_tile_edges(cuda):
+    """Sizes around a scan tile of 1024 vectors (4096 floats), where a lane's four loads are in flight only if its fourth
+    vector (base + 768) exists: 768 and 769 vectors, one vector short of a tile, exactly one, one tile and three quarters, two
+    tiles and one vector; tails of 0, 1 and 3.  One bad value at a time at every edge; clean in between."""
+    lib, h = _api(cuda)
+    rng = np.random.default_rng(5)
+    assert _tile_edge_positions(7175) == [0, 4096, 5119, 5120, 6143, 6144, 7167, 7168, 7171, 7172, 7173, 7174]
+    k = 0
+    for n in (3075, 3076, 3077, 4095, 4096, 4097, 7168, 7175, 8197):
+        g = Guarded(cuda, n, 4, P32, R.values(rng, n))
+        # the guards next to the buffer are non-finite: reading one element too many raises a false flag
+        g.buf[:g.lo] = _i32(0x7fc00000)
+        g.buf[g.lo + n:] = _i32(0x7fc00000)
+        assert _nonfinite(lib, h, cuda, g.ptr, n) == (0, 0), n
+        for pos in _tile_edge_positions(n):
             keep = int(g.buf[g.lo + pos].item())
             g.buf[g.lo + pos] = _i32(BAD_BITS[k % 5])
             assert _nonfinite(lib, h, cuda, g.ptr, n) == (0, 1), (n, pos, hex(BAD_BITS[k % 5]))
