@@ -642,6 +642,36 @@ int od_cast_f32_bf16(od_ctx* ctx, const float* src, void* dst, long long n, void
 int od_cast_bf16_f32(od_ctx* ctx, const void* src, float* dst, long long n, void* stream);
 int od_pack_weights_multi(od_ctx* ctx, const float* w, const od_pack_layer* layers, int nlayers, void* stream);
 
+/* ---- Trainer -> detector weight refresh: one launch rewrites the inference tensors of a live network (f16 pack, folded
+ * f32 scale and bias per layer) from the trainer's flat f32 buffers.  `layers` is a DEVICE array, one entry per pack. */
+typedef struct od_refresh_layer {
+  int64_t w_offset;     /* master weights f32 [Cout][k*k*Cin] in params_flat */
+  int64_t gamma_offset; /* has_bn: gamma[Cout] in params_flat */
+  int64_t beta_offset;  /* has_bn: beta[Cout] in params_flat; otherwise the layer's bias[Cout] */
+  int64_t mean_offset;  /* has_bn: running mean[Cout] in run_stats_flat */
+  int64_t var_offset;   /* has_bn: running variance[Cout] in run_stats_flat */
+  void* w_dst;          /* f16 [Cout_pad][Kpad], written whole */
+  void* scale_dst;      /* f32 [Cout_pad], written whole; NULL (with bias_dst) = this entry writes the pack alone */
+  void* bias_dst;       /* f32 [Cout_pad] */
+  int32_t Cout, Cin, ksize;
+  int32_t Cout_pad, Kpad; /* od_conv_weight_dims(Cout, cin_repeat * Cin, ksize); the image layer: Cout, 32 */
+  int32_t cin_repeat;     /* 1, or 2: the pack of the weights repeated along the input channels ([w | w], the operand of
+                           * a layer that reads an f16 (hi, lo) pair) */
+  int32_t first;          /* the image layer: scale is additionally divided by 255.0f */
+  int32_t has_bn;
+} od_refresh_layer;
+/* Per entry, for EVERY element of the three destination tensors (padding is written as zero, never assumed):
+ *   w_dst[co][tap*cin_repeat*Cin + r*Cin + ci] = (f16)w[co][tap*Cin + ci]     (round to nearest even, overflow to Inf,
+ *                                                                             f16 subnormals kept)
+ *   has_bn:  scale = gamma / sqrtf(var + eps);  bias = beta - mean * scale    (od_bn_fold's expression: one correctly
+ *            first: scale = scale / 255.0f                                     rounded f32 operation each, no contraction)
+ *   else:    scale = 1;  bias = bias
+ * Offsets are in elements and may have any 4-byte alignment (rows that are 16-byte aligned move as 16-byte loads); the
+ * destination pointers must be 16-byte aligned (the launch cannot see them: the table is on the device).  Returns
+ * OD_ERR_INVALID for a null ctx / params_flat / run_stats_flat / layers or nlayers outside 1..65535. */
+int od_net_refresh(od_ctx* ctx, const float* params_flat, const float* run_stats_flat, const od_refresh_layer* layers,
+                   int nlayers, float eps, void* stream);
+
 /* first layer's weight gradient: dw f32 [32][27] += dz^T . shifted(x_u8) * in_scale (no dX: the input is the image).
  * Streaming kernel (W a multiple of 32: the uint8 window is read in place, one 32 x 32 f32 partial slab per workgroup);
  * other widths run the MFMA weight-gradient kernel over an f16 x 8-channel copy of the image kept in `workspace`.  Either way

@@ -116,6 +116,14 @@ class PackLayer(C.Structure):
                 ("Cout", C.c_int32), ("Cin", C.c_int32), ("ksize", C.c_int32), ("pad_", C.c_int32)]
 
 
+class RefreshLayer(C.Structure):
+    C_NAME = "od_refresh_layer"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
+    _fields_ = [("w_offset", C.c_int64), ("gamma_offset", C.c_int64), ("beta_offset", C.c_int64),
+                ("mean_offset", C.c_int64), ("var_offset", C.c_int64),
+                ("w_dst", C.c_void_p), ("scale_dst", C.c_void_p), ("bias_dst", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("Cout", "Cin", "ksize", "Cout_pad", "Kpad", "cin_repeat", "first", "has_bn")]
+
+
 class WideDesc(C.Structure):
     C_NAME = "od_wide_desc"  # the struct of include/odhip.h this mirrors (layout checked by tests/test_host_logic.py)
     _fields_ = [("y", C.c_void_p), ("res", C.c_void_p), ("out32", C.c_void_p), ("out16", C.c_void_p),
@@ -161,7 +169,7 @@ class SoftNmsCfg(C.Structure):
                 ("sigma", C.c_float), ("min_conf", C.c_float)]
 
 
-STRUCTS = (SoftNmsCfg, TileDesc, TtaView, ConvDesc, AugParams, MosaicParams, WarpParams, BneckDesc, StemDesc, SgdSeg, OptimState, OptimCfg, WgradRed, PackLayer, WideDesc, PlanOp, ImgDesc)
+STRUCTS = (SoftNmsCfg, TileDesc, TtaView, ConvDesc, AugParams, MosaicParams, WarpParams, BneckDesc, StemDesc, SgdSeg, OptimState, OptimCfg, WgradRed, PackLayer, RefreshLayer, WideDesc, PlanOp, ImgDesc)
 
 
 class OdError(RuntimeError):
@@ -296,6 +304,7 @@ _PROTOS = {
     "od_pack_weights_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "od_pack_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                   C.c_void_p]),
+    "od_net_refresh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "od_conv_first_bwd_weight_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "od_conv_first_bwd_weight": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),

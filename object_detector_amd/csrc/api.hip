@@ -108,6 +108,13 @@ const std::vector<StructInfo>& od_struct_table() {
       {"od_pack_layer", sizeof(od_pack_layer),
        {OD_F(od_pack_layer, w_offset), OD_F(od_pack_layer, w_fwd), OD_F(od_pack_layer, w_bwd), OD_F(od_pack_layer, Cout),
         OD_F(od_pack_layer, Cin), OD_F(od_pack_layer, ksize), OD_F(od_pack_layer, pad_)}},
+      {"od_refresh_layer", sizeof(od_refresh_layer),
+       {OD_F(od_refresh_layer, w_offset), OD_F(od_refresh_layer, gamma_offset), OD_F(od_refresh_layer, beta_offset),
+        OD_F(od_refresh_layer, mean_offset), OD_F(od_refresh_layer, var_offset), OD_F(od_refresh_layer, w_dst),
+        OD_F(od_refresh_layer, scale_dst), OD_F(od_refresh_layer, bias_dst), OD_F(od_refresh_layer, Cout),
+        OD_F(od_refresh_layer, Cin), OD_F(od_refresh_layer, ksize), OD_F(od_refresh_layer, Cout_pad),
+        OD_F(od_refresh_layer, Kpad), OD_F(od_refresh_layer, cin_repeat), OD_F(od_refresh_layer, first),
+        OD_F(od_refresh_layer, has_bn)}},
       {"od_aug_params", sizeof(od_aug_params),
        {OD_F(od_aug_params, src_offset), OD_F(od_aug_params, src_h), OD_F(od_aug_params, src_w),
         OD_F(od_aug_params, crop_x1), OD_F(od_aug_params, crop_y1), OD_F(od_aug_params, crop_x2),

@@ -136,6 +136,28 @@ def stream_queue_sets(device, n, candidates=6, seed_streams=(), beside=None):
     return chosen
 
 
+def _device_key(device):
+    d = torch.device(device)
+    if d.type == "cuda" and d.index is None:
+        return d.type, (torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    return d.type, d.index
+
+
+def check_refresh(device, arch, trainer, ema):
+    """ValueError for a (detector, trainer) pair ObjectDetector.refresh_from cannot serve -- a trainer on another device or
+    of another architecture ((num_classes, neck_ch, tower) and the layer specs), ema=True without an averaged model.
+    Host-only: runs before anything touches the GPU."""
+    if _device_key(trainer.device) != _device_key(device):
+        raise ValueError(f"refresh_from: the trainer lives on {trainer.device}, the detector on {device}; the refresh is a "
+                         f"launch on one device")
+    theirs = (trainer.num_classes, trainer.neck_ch, trainer.tower)
+    if tuple(arch) != theirs or list(trainer.specs.values()) != W.layer_specs(*arch):
+        raise ValueError(f"refresh_from: the trainer's architecture (classes, neck channels, tower) = {theirs} is not the "
+                         f"detector's {tuple(arch)}")
+    if ema and trainer.ema_decay is None:
+        raise ValueError("refresh_from(ema=True): this trainer keeps no averaged model (ema_decay=None)")
+
+
 class _Pipeline:
     """One batch in flight: its own activation buffers (Net), post-processing buffers and HIP stream."""
 
@@ -181,8 +203,13 @@ class ObjectDetector:
             raise ValueError(f"image_decode must be 'host' or 'device', got {image_decode!r}")
         self.image_decode = image_decode
         self.decode_stats = {"jpeg": 0, "fallback": 0, "array": 0}
+        # after refresh_from() the weights on the device are the trainer's and `params` is STALE: it stays the dict the
+        # detector was built from.  refreshed_from: None, or (id(trainer), ema, trainer.steps_issued) of the last refresh
         self.params = params
-        self.num_classes, _, _ = W.infer_arch(params)
+        self.refreshed_from = None
+        self._refresh_ev = None  # recorded behind the last refresh: a pipeline's stream waits for it before its next batch
+        self.arch = W.infer_arch(params)
+        self.num_classes, _, _ = self.arch
         kw = {} if prior_wh is None else {"prior_wh": prior_wh}
         self.pb = PriorBoxes(self.input_size, self.num_classes, device=self.device, **kw)
         n = int(n_inflight) if n_inflight is not None else int(os.environ.get("OD_INFLIGHT", 3))  # explicit argument wins
@@ -260,6 +287,40 @@ class ObjectDetector:
     def synthetic(cls, batch_size, input_size=(320, 320), seed=2, num_classes=20, **kw):
         """Random-init detector of the VOC architecture (benchmarks / parity tests)."""
         return cls(W.random_init(seed, num_classes), batch_size, input_size, **kw)
+
+    @classmethod
+    def from_trainer(cls, trainer, batch_size=None, ema=False, **kw):
+        """A detector of `trainer`'s architecture, input size, priors and device holding its current weights (ema=True: the
+        averaged model): the host route once (export_params, fold, pack, upload), refresh_from(trainer) from then on."""
+        kw.setdefault("device", trainer.device)
+        kw.setdefault("prior_wh", trainer.pb.prior_wh)
+        od = cls(trainer.export_params(ema=ema), trainer.B if batch_size is None else batch_size,
+                 (trainer.H0, trainer.W0), **kw)
+        od.refreshed_from = (id(trainer), bool(ema), trainer.steps_issued)
+        return od
+
+    def refresh_from(self, trainer, ema=False):
+        """Rewrite this detector's weights on the device from a live Trainer's flat buffers -- trainer.params / run_stats, or
+        with ema=True the averaged model trainer.ema / ema_run_stats -- in one launch (od_net_refresh): the bits of
+        ObjectDetector(trainer.export_params(ema), ...) without the host round trip.  In place, so every pipeline, plan and
+        captured graph of the detector runs the new weights.  ValueError (before anything touches the GPU) for a trainer
+        on another device or of another architecture, and for ema=True without an averaged model.
+
+        Ordering, with no host synchronisation: the launch goes on the CURRENT stream, where the trainer's step was issued;
+        it first waits for the `done` event of every pipeline (no batch in flight reads half-written weights), and every
+        pipeline's stream waits for an event recorded behind it before its next batch.  self.params is left alone and is
+        stale afterwards; self.refreshed_from records (id(trainer), ema, trainer.steps_issued)."""
+        check_refresh(self.device, self.arch, trainer, ema)
+        cur = torch.cuda.current_stream(self.device)
+        for p in self._pipes:
+            cur.wait_event(p.done)
+        self.net.refresh(trainer, ema)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        for p in self._pipes:
+            p.stream.wait_event(ev)
+        self._refresh_ev = ev  # _pick_streams: streams chosen later wait for it too
+        self.refreshed_from = (id(trainer), bool(ema), trainer.steps_issued)
 
     # -- inference --------------------------------------------------------------------------------------------
     def predict_batch_device(self, x_u8: torch.Tensor, conf_threshold=DEFAULT_CONF_THRESHOLD, graph=False):
@@ -340,6 +401,8 @@ class ObjectDetector:
         self._calibrated = True
         sts = stream_queue_sets(self.device, len(self._pipes), seed_streams=[p.stream for p in self._pipes])
         for p, st in zip(self._pipes, sts):
+            if self._refresh_ev is not None:  # the stream it replaces was ordered behind the last refresh_from
+                st.wait_event(self._refresh_ev)
             p.stream = st
         self._next = 0
 

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -73,6 +74,46 @@ def pack_layer(w_ohwi: np.ndarray, scale, bias, first=False):
     return wp, pad_vec(np.asarray(scale, np.float32), wp.shape[0]), pad_vec(np.asarray(bias, np.float32), wp.shape[0])
 
 
+def refresh_layers(trainer, dev):
+    """The od_refresh_layer entries (_lib.RefreshLayer) that rewrite the inference tensors `dev` -- a Net's _dev: {layer or
+    layer + "#split": (f16 pack [Cout_pad, Kpad], f32 scale [Cout_pad], f32 bias [Cout_pad])} -- from `trainer`'s flat
+    buffers: one entry per layer of trainer.specs in order (offsets from trainer.seg and trainer._run_off), then one per
+    "#split" pack (cin_repeat = 2, pack only: it shares scale and bias with its layer).  Host-only: reads shapes and
+    pointers, touches no device.  ValueError when `dev` is not the tensor set of the trainer's architecture."""
+    names = list(trainer.specs)
+    splits = [k for k in dev if k.endswith("#split")]
+    extra = set(dev) - set(names) - set(splits)
+    if extra or any(n not in dev for n in names) or any(k[:-len("#split")] not in trainer.specs for k in splits):
+        raise ValueError("refresh: the network's layers are not the trainer's (another architecture)")
+    out = []
+    for key in names + splits:
+        name, rep = (key, 1) if key in trainer.specs else (key[:-len("#split")], 2)
+        _n, cin, cout, k, _s, bn = trainer.specs[name]
+        wp, scale, bias = dev[key]
+        first = name == "b.conv0"
+        cout_pad, kpad = int(wp.shape[0]), int(wp.shape[1])
+        want = (cout, 32) if first else _lib.conv_weight_dims(cout, cin * rep, k)
+        if ((cout_pad, kpad) != want or tuple(scale.shape) != (cout_pad,) or tuple(bias.shape) != (cout_pad,)
+                or (first and rep != 1)):
+            raise ValueError(f"refresh: {key}: a pack of shape {tuple(wp.shape)} cannot hold the trainer's "
+                             f"[{cout}, {k * k * cin * rep}] weights (their pack is {want})")
+        L = _lib.RefreshLayer()
+        L.w_offset = trainer.seg[(name, "w")][0]
+        if bn:
+            L.gamma_offset, L.beta_offset = trainer.seg[(name, "gamma")][0], trainer.seg[(name, "beta")][0]
+            L.mean_offset = trainer._run_off[name]
+            L.var_offset = trainer._run_off[name] + desc.pad_to(cout, 4)
+        else:
+            L.beta_offset = trainer.seg[(name, "bias")][0]
+        L.w_dst = wp.data_ptr()
+        if rep == 1:
+            L.scale_dst, L.bias_dst = scale.data_ptr(), bias.data_ptr()
+        L.Cout, L.Cin, L.ksize, L.Cout_pad, L.Kpad = cout, cin, k, cout_pad, kpad
+        L.cin_repeat, L.first, L.has_bn = rep, int(first), int(bool(bn))
+        out.append(L)
+    return out
+
+
 # the cheapest plan that keeps EVERY logit within 1e-3 x scale of the fp32 oracle at 32 x 320^2 / 16 x 640^2 with margin
 # (profiles/r03/logit_error_mixed_plans_cpu.txt: 22 % of the default plan's error variance; the stage-3 stream would cost
 # another 0.29 ms per batch for 6 points of variance that splitting the two small lateral layers buys for nothing)
@@ -127,6 +168,7 @@ class Net:
         self._splitk_descs = []
         self._keep = []  # device tensors referenced by raw pointers in the plan
         self._dev = {}
+        self._refresh_table = None  # (weak reference to the trainer, device table of od_refresh_layer, entries): refresh_table
         if share_weights_with is not None:  # another pipeline of the same detector: the packed weights are read-only
             self._dev = share_weights_with._dev
         for name, cin, cout, k, _s, _bn in ([] if share_weights_with is not None else
@@ -436,6 +478,25 @@ class Net:
         else:
             _lib.check(self.lib.od_plan_run(self.plan, _stream_ptr()), "od_plan_run")
         return self.pred
+
+    def refresh_table(self, trainer):
+        """(device table of od_refresh_layer, entry count) that rewrites this network's weights from `trainer`'s buffers:
+        built on the first call for a trainer (refresh_layers) and kept on the device; another trainer replaces it."""
+        if self._refresh_table is not None and self._refresh_table[0]() is trainer:
+            return self._refresh_table[1:]
+        entries = refresh_layers(trainer, self._dev)
+        table = torch.frombuffer(bytearray(b"".join(bytes(e) for e in entries)), dtype=torch.uint8).to(self.device)
+        self._refresh_table = (weakref.ref(trainer), table, len(entries))
+        return table, len(entries)
+
+    def refresh(self, trainer, ema=False):
+        """One od_net_refresh launch on the current stream: every pack, scale and bias of self._dev (shared by the nets
+        built with share_weights_with=self) from trainer.params / run_stats, or trainer.ema / ema_run_stats.  In place:
+        plans and captured graphs stay valid.  Ordering against batches in flight is the caller's (ObjectDetector.refresh_from)."""
+        table, n = self.refresh_table(trainer)
+        flat, stats = (trainer.ema, trainer.ema_run_stats) if ema else (trainer.params, trainer.run_stats)
+        _lib.check(self.lib.od_net_refresh(self.ctx.handle, flat.data_ptr(), stats.data_ptr(), table.data_ptr(), n,
+                                           W.BN_EPS, _stream_ptr()), "od_net_refresh")
 
     def time_ops(self):
         """Per-op device time (ms) via hipEvents on the launch stream + kernel names: for bench.py's roofline."""

@@ -249,6 +249,7 @@ class Trainer:
         self.ema = self.params.clone() if self.ema_decay is not None else None
         self.ema_run_stats = self.run_stats.clone() if self.ema_decay is not None else None
         self.ema_updates = 0
+        self.steps_issued = 0  # sgd() calls of this object, skipped steps included: what ObjectDetector.refreshed_from records
         # the new optimizer path's buffers (none on the default path): AdamW's second moment, the device od_optim_state
         # (int32 step, then seven f32: _lib.OptimState), the per-workgroup f64 partials of od_grad_stats
         self.mom2 = torch.zeros_like(self.params) if self.optimizer == "adamw" else None
@@ -771,6 +772,7 @@ class Trainer:
                        "od_ema_update")
             self.ema_updates += 1
         self._repack()  # (a skipped step re-packs unchanged masters: harmless, and keeps the launch sequence fixed)
+        self.steps_issued += 1
         host = self._flag_pool.pop() if self._flag_pool else torch.zeros(1, dtype=torch.int32).pin_memory()
         host.copy_(self.nonfinite, non_blocking=True)
         ev = torch.cuda.Event()
@@ -823,7 +825,8 @@ class Trainer:
         self.sgd()
         return self.losses
 
-    def fit(self, batches, steps, lr_schedule=None, log_every=0, log=print, start_step=0):
+    def fit(self, batches, steps, lr_schedule=None, log_every=0, log=print, start_step=0, validate_every=None,
+            validator=None):
         """Run `steps` training steps from an iterator of (x_u8 [B,H,W,3] device tensor, y_target [B,P,C] device tensor or
         list of annotations) -- what od_gen.Generator(on_device=True).flow(...) yields (the reference's unseen `fit`:
         generator -> encode_truth -> losses, check_assign.py:21-22).  lr_schedule(step) -> learning rate.  Returns the
@@ -831,7 +834,16 @@ class Trainer:
         end, and the loop waits for nothing but the flag copy of the step LAG steps back (_poll_nonfinite), so the host
         runs two steps ahead.  start_step: a continued run (load_state_dict) -- the schedule is asked for start_step + i,
         and the history covers the `steps` steps run here.  The flags of the last LAG steps stay pending when fit()
-        returns: a run in several fit() calls is the run in one, and _poll_nonfinite(wait=True) ends a run."""
+        returns: a run in several fit() calls is the run in one, and _poll_nonfinite(wait=True) ends a run.
+        validate_every=N with validator=v (validate.Validator, or any callable (trainer, step) -> dict or str): v is called
+        behind every step whose number start_step + i + 1 is a multiple of N and what it returns goes to `log`.  It reads
+        the weights on the device (ObjectDetector.refresh_from) and writes nothing the training reads: the run's weights
+        and losses are those of the run without it.  Both or neither (ValueError); the defaults launch nothing."""
+        if (validate_every is None) != (validator is None):
+            raise ValueError("fit: validate_every and validator go together (got "
+                             f"validate_every={validate_every!r}, validator={'None' if validator is None else 'a validator'})")
+        if validate_every is not None and (int(validate_every) != validate_every or validate_every < 1):
+            raise ValueError(f"fit: validate_every must be a positive step count, got {validate_every!r}")
         hist = torch.zeros((steps, 4), dtype=torch.float32, device=self.device)
         for i, (xb, yb) in zip(range(steps), batches):
             if lr_schedule is not None:
@@ -851,6 +863,11 @@ class Trainer:
                 log(f"step {start_step + i + 1}/{start_step + steps} lr {self.lr:.4g} loss {l[3]:.4f} (obj {l[0]:.4f} cls {l[1]:.4f} box {l[2]:.4f}) "
                     f"loss_scale {self.loss_scale:g} skipped {self.skipped_steps}"
                     + (f" grad_norm {float(self.last_grad_norm.item()):.4g}" if self._optim_path else ""))
+            if validate_every is not None and (start_step + i + 1) % validate_every == 0:
+                from .tk.dl import is_main_process
+                res = validator(self, start_step + i + 1)
+                if res is not None and is_main_process():  # every rank validates its shard; one of them reports
+                    log(res if isinstance(res, str) else validation_line(res))
         return hist.cpu().numpy()
 
     def export_params(self, ema=False):
@@ -959,6 +976,13 @@ class Trainer:
             self.optim_state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
         self._repack()
         self._sgd_key = None
+
+
+def validation_line(entry):
+    """The log line of one validation record: its step first, then every scalar of the dict in order."""
+    rest = " ".join(f"{k} {v:.4f}" if isinstance(v, float) else f"{k} {v}" for k, v in entry.items()
+                    if k != "step" and isinstance(v, (int, float, str, bool)))
+    return f"validation at step {entry.get('step', '?')}: {rest}"
 
 
 # "optim_state" of a state_dict: what od_optim_prepare carries from step to step

@@ -52,10 +52,9 @@ def add_slice_arguments(p):
                    help="under --slices: leave the whole-image tile out (objects larger than the overlap can then be lost)")
 
 
-def make_detector(tk, args, batch_size, input_size=(320, 320), device_decode=False, **kw):
-    """device_decode: JPEG decode and resize of predict()'s inputs on the GPU (image_decode="device")."""
-    OD = tk.dl.od.ObjectDetector
-    kw["image_decode"] = "device" if device_decode else "host"
+def detector_options(args):
+    """The ObjectDetector keywords of --tta / --nms / --slices (add_*_arguments above); an absent option adds nothing."""
+    kw = {}
     if getattr(args, "tta", None) is not None:
         kw["tta"], kw["tta_vote_iou"] = tuple(args.tta), args.vote_iou
     if getattr(args, "slices", None) is not None:
@@ -63,6 +62,14 @@ def make_detector(tk, args, batch_size, input_size=(320, 320), device_decode=Fal
         kw["slice_full_view"] = not args.no_slice_full_view
     if getattr(args, "nms", "hard") != "hard":
         kw["nms"], kw["soft_sigma"], kw["soft_min_conf"] = args.nms, args.soft_sigma, args.soft_min_conf
+    return kw
+
+
+def make_detector(tk, args, batch_size, input_size=(320, 320), device_decode=False, **kw):
+    """device_decode: JPEG decode and resize of predict()'s inputs on the GPU (image_decode="device")."""
+    OD = tk.dl.od.ObjectDetector
+    kw["image_decode"] = "device" if device_decode else "host"
+    kw.update(detector_options(args))
     if args.synthetic:
         return OD.synthetic(batch_size, input_size, **kw)
     return OD.load_voc(batch_size=batch_size, input_size=input_size, weights=args.weights, **kw)

@@ -107,12 +107,53 @@ def build_parser():
                    help="continue from a state file at the step it recorded, up to --steps in total.  The generator is "
                         "seeded from (seed, rank, that step), so the batches that follow are NOT those an uninterrupted run "
                         "would have drawn")
+    p.add_argument("--val-every", default=0, type=int, metavar="N",
+                   help="validate every N steps during the run: a detector refreshed on the GPU from the live weights (the "
+                        "average under --ema) predicts the validation images, the mAP is logged (needs --val-shapes or --val-set)")
+    p.add_argument("--val-shapes", default=0, type=int, metavar="M",
+                   help="--val-every: M generated images, drawn with another seed than the --shapes training set")
+    p.add_argument("--val-set", default=None, metavar="SET",
+                   help="--val-every: this image set of the VOC directory (e.g. test, val)")
+    p.add_argument("--val-batch-size", default=None, type=int, help="batch size of the validation detector (default --batch-size)")
+    p.add_argument("--val-coco", action="store_true", help="--val-every: also log the twelve COCO AP / AR numbers")
+    p.add_argument("--keep-best", action="store_true",
+                   help="--val-every: write the weights of the best validation so far (by VOC mAP) to <result-dir>/best.npz")
+    # the validation detector's options (absent = off, as in the evaluation scripts)
+    _common.add_tta_arguments(p)
+    _common.add_nms_arguments(p)
+    _common.add_slice_arguments(p)
     return p
+
+
+def check_validation_args(args):
+    """--val-every needs validation data; said right after parsing, before any data is read or a trainer built."""
+    if args.val_every > 0 and not args.val_shapes and (args.val_set is None or args.vocdevkit_dir is None):
+        raise SystemExit("--val-every needs validation data: --val-shapes M, or --val-set SET with --vocdevkit-dir")
+
+
+def make_validator(args, tr, class_names=None):
+    """--val-every: the Validator of the run (held-out data, a detector built once from the trainer), or None.  Under
+    --resume an existing <result-dir>/best.npz keeps its place until a validation scores above the value it recorded."""
+    if args.val_every <= 0:
+        return None
+    from object_detector_amd.detector import ObjectDetector
+    from object_detector_amd.validate import Validator
+    if args.val_shapes:
+        Xv, yv = _common.shapes_dataset(args.val_shapes, seed=args.seed + 1000)  # held out: another seed
+    else:
+        Xv, yv = tk.data.voc.load_set(args.vocdevkit_dir, args.year, args.val_set)
+    od = ObjectDetector.from_trainer(tr, batch_size=args.val_batch_size, **_common.detector_options(args))
+    v = Validator(od, Xv, yv, coco=args.val_coco, class_names=class_names,
+                  keep_best=args.result_dir / "best.npz" if args.keep_best else None)
+    if args.resume is not None and v.resume_best():
+        tk.log.get(__name__).info(f"{v.keep_best}: {v.metric} {v.best_value:.4f} of step {v.best_step} stays the best so far")
+    return v
 
 
 def _main():
     tk.better_exceptions()
     args = build_parser().parse_args()
+    check_validation_args(args)
     with tk.dl.session():
         tk.log.init(args.result_dir / "train.log")
         _run(args)
@@ -207,6 +248,8 @@ def _run(args):
         flow_seed = int(np.random.SeedSequence([args.seed, rank, start]).generate_state(1)[0] >> 1)
         log.info(f"resumed from {args.resume}: starting at step {start}, loss scale {tr.loss_scale:g}, "
                  f"ema_updates {tr.ema_updates}")
+    validator = make_validator(args, tr, class_names)
+    val_kw = {} if validator is None else {"validate_every": args.val_every, "validator": validator}
     positives = {"sum": torch.zeros((), dtype=torch.int64, device=dev), "images": 0}
 
     def encode_truth(anns):  # tr.pb.encode_truth_device, and the positives it made are counted (on the device: no sync)
@@ -247,7 +290,8 @@ def _run(args):
     hists, done = [], start
     while done < args.steps:  # one fit() for the whole run, or one per --save-state-every steps
         k = args.steps - done if args.save_state_every <= 0 else min(args.save_state_every, args.steps - done)
-        hists.append(tr.fit(feed, k, lr_schedule=schedule, log_every=args.log_every, log=log.info, start_step=done))
+        hists.append(tr.fit(feed, k, lr_schedule=schedule, log_every=args.log_every, log=log.info, start_step=done,
+                            **val_kw))
         count_last_step()
         done += k
         if args.save_state_every > 0 and tk.dl.is_main_process():
@@ -273,6 +317,10 @@ def _run(args):
              f"over {positives['images']} encoded images")
     if tr.ema_decay is not None:
         log.info(f"weight average: decay {tr.ema_decay:g}, ema_updates {tr.ema_updates}")
+    if validator is not None and validator.history:
+        log.info(f"validation: best {validator.metric} {validator.best_value:.4f} at step {validator.best_step} of "
+                 f"{len(validator.history)} validations"
+                 + (f", weights in {validator.keep_best}" if validator.keep_best is not None else ""))
     if tk.dl.is_main_process():
         out = args.out or (args.result_dir / "trained.npz")
         out.parent.mkdir(parents=True, exist_ok=True)
