@@ -16,7 +16,7 @@
 //           nms.hip and detect_wide.hip.  od_detect_refine_sort is the same kernel without the last step
 // Same total order, same exact selection, same kept indices as the three-call path (tests compare them bit for bit).
 // od_detect_candidates is the same call with od_detect_refine_sort for a tail (boxes, sorted keys, counts): one view of
-// od_tta_merge (tta.hip).
+// od_tta_merge (merge.hip).
 // Compiled with -ffp-contract=off like post.hip / topk.hip / nms.hip.  NC <= 76 (256 whole rows in LDS); larger class counts
 // take the streamed kernels of detect_wide.hip through the same entry points, and od_nms's suppression launch after them.
 #include <string.h>
@@ -370,7 +370,8 @@ int detect_launch(od_ctx* ctx, const char* who, const float* pred, const float* 
                   void* workspace, size_t workspace_bytes, void* nms_workspace, size_t nms_workspace_bytes, const NmsArgs* nms,
                   hipStream_t s) {
   OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "%s: NC = %d outside the supported class counts 1..%d", who, NC, OD_MAX_NC);
-  OD_REQUIRE(B > 0 && B <= 65535 && P > 0 && P % 2 == 0 && K > 0 && K <= 1024, "%s: bad dims (P even, K <= 1024)", who);
+  OD_REQUIRE(B > 0 && B <= 65535 && P > 0 && P % 2 == 0 && K > 0 && K <= OD_MERGE_MAX_K,
+             "%s: bad dims (P even, K <= %d)", who, OD_MERGE_MAX_K);
   OD_REQUIRE((long long)P * NC < (1LL << 31), "%s: P * NC must fit 31 bits", who);
   OD_REQUIRE(conf_threshold >= 0.f, "%s: conf_threshold must be >= 0 (scores are probabilities)", who);
   const DetLayout l = det_layout(B, P, NC);

@@ -1,4 +1,5 @@
-// Shared by post.hip (K5/K6), topk.hip (K7), nms.hip (K8), detect.hip and detect_wide.hip (the fused product path) and tta.hip:
+// Shared by post.hip (K5/K6), topk.hip (K7), nms.hip (K8), soft_nms.hip, detect.hip and detect_wide.hip (the fused product
+// path), merge.hip (the merged candidate tables of TTA and sliced inference) and slice.hip:
 // the confidence arithmetic and the histogram searches here; the key format, the radix refine, the sort / gather and the IoU
 // predicate in topk_common.h (included at the end).  Every TU that includes this is compiled with -ffp-contract=off, so the
 // same source is the same f32 op sequence everywhere (and the one of oracle/postprocess.py): confidences are bit-identical
@@ -37,6 +38,7 @@ __device__ __forceinline__ void od_row_conf(const float* row, int NC, float* out
 // confidences are bit-identical to od_row_conf's (and to oracle/postprocess.confidence).
 constexpr int OD_MAX_LDS_NC = 76;  // the largest NC whose [256][NC+6] rows (+ histogram / output) fit the LDS kernels
 constexpr int OD_MAX_NC = 1024;
+constexpr int OD_MERGE_MAX_K = 1024;  // the longest candidate list: one thread per entry in the one-workgroup-per-image kernels
 constexpr int OD_WIDE_CW = 32;              // class columns per LDS chunk
 constexpr int OD_WIDE_LD = OD_WIDE_CW + 1;  // tile row pitch: a thread walking its own row hits a different bank per lane
 
@@ -229,26 +231,11 @@ int od_nms_greedy_launch(void* nms_workspace, const int32_t* counts, int B, int 
                          int32_t* keep_flat, int32_t* keep_count, hipStream_t stream);
 // nms.hip: where od_nms keeps the sorted keys / gathered boxes / classes inside its workspace (KP = next power of two >= K)
 void od_nms_sorted_buffers(void* nms_workspace, int B, int K, unsigned long long** skeys, f32x4** sbox, int** scls, int* KP);
-// tta.hip: the workspace of a merged candidate table (od_tta_merge, od_slice_merge) -- od_nms's workspace, the merged count
-// [B], the (list, flat) source of every merged rank [B,KP,2] and the scan's kept list [B,K] -- and what follows the rank
-// kernel that fills it: od_nms_greedy_k, then the vote-and-gather kernel
-struct OdMergeWs {
-  void* nms;
-  int* mcount;
-  int* msrc;
-  int* keepf;
-};
-size_t od_merge_workspace_bytes(int B, int K);
-OdMergeWs od_merge_workspace(void* workspace, int B, int K);
-// soft non-null: the soft scan (cfg->iou_threshold / strict / max_det in place of the three scalars) and its rescored confidences
-int od_merge_nms_vote_launch(const OdMergeWs& w, int B, int NC, int K, float iou_threshold, int strict, int max_det,
-                             float vote_iou, float* out, int32_t* src, int32_t* keep_count, hipStream_t s,
-                             const od_soft_nms_cfg* soft = nullptr);
 // nms.hip: od_nms's sort launch (keys -> the rank-ordered keys / boxes / classes of the workspace)
 int od_nms_sort_launch(void* nms_workspace, const float* boxes, const unsigned long long* keys, const int32_t* counts, int B, int P,
                        int NC, int K, hipStream_t s);
 // nms.hip: the part of the NMS workspace behind the rank-ordered buffers, >= B * KP * 8 bytes that no scan reads or writes:
-// where the soft merges keep the kept rows' rescored confidences between the scan and the vote-and-gather kernel
+// where the soft merges (merge.hip) keep the kept rows' rescored confidences between the scan and the vote-and-gather kernel
 float* od_nms_scratch(void* nms_workspace, int B, int K);
 // soft_nms.hip: the argument checks every soft entry shares (OD_OK or OD_ERR_*, error text set), and the soft scan's launch on
 // the rank-ordered buffers of the NMS workspace (det may be null)

@@ -1,6 +1,7 @@
-// Sliced inference: tiles of a full-resolution image cut and resized into the network batch (od_tiles_resize), and the merge
-// of the per-tile candidate lists of every image into ONE NMS + box voting (od_slice_merge).  DESIGN.md "Sliced inference"
-// freezes the semantics; tests/slice_ref.py is their numpy restatement and tests/test_gpu_slice_*.py compare bit for bit.
+// Sliced inference: tiles of a full-resolution image cut and resized into the network batch (od_tiles_resize).  The merge of
+// the per-tile candidate lists of every image into ONE NMS + box voting (od_slice_merge) is merge.hip's, with the batch rows as
+// its list source.  DESIGN.md "Sliced inference" freezes the semantics; tests/slice_ref.py is their numpy restatement and
+// tests/test_gpu_slice_tiles.py compares bit for bit.
 //
 // od_tiles_resize: Pillow's crop + resize(BILINEAR) of one rectangle per network row, the two passes of resample_common.h in
 // Image.resize's order, each rounded to 8 bits; a pass whose length does not change is skipped.  HBM-bound: a pass reads
@@ -8,16 +9,6 @@
 //   od_tiles_pass1_k   rectangle -> tmp [th, W] (horizontal), or -> tmp [H, tw] when the tile takes the vertical pass first
 //   od_tiles_pass2_k   tmp (or the rectangle itself, when pass 1 was skipped) -> row n of the output
 // Every source read is inside the rectangle: a tap row is clamped to the pass's source length, whatever the table holds.
-//
-// od_slice_merge is od_tta_merge with batch rows as the "views": three launches,
-//   rank  (od_slice_rank)  one workgroup of 1024 threads per image, thread r owns entry r of every tile's list.  The
-//         interior-edge rule drops candidates cut at a seam; the survivors of each list are compacted in order (ballot +
-//         prefix over the 16 waves), so the lists stay sorted and a survivor's merged rank (conf bits desc, tile asc, flat
-//         asc) is its compacted position plus a binary-searched count per other list -- a dropped entry is in no list and
-//         cannot disturb a rank.  The first Km = min(K, survivors) are written as od_nms_sort leaves a table behind.
-//   od_nms_greedy_k, then od_tta_vote_gather (tta.hip), unchanged, through od_merge_nms_vote_launch
-//   (od_slice_merge_soft: the soft scan of soft_nms.hip in place of od_nms_greedy_k).
-// Compiled with -ffp-contract=off: the map to image coordinates is one rounding per op, as numpy's.
 #include "post_common.h"
 #include "resample_common.h"
 
@@ -116,104 +107,6 @@ bool tile_rect_ok(const od_tile_desc& d) {
 
 int grid_x(int64_t n) { return (int)std::min<int64_t>(std::max<int64_t>((n + 255) / 256, 1), 512); }
 
-// ---- od_slice_merge ---------------------------------------------------------------------------------------------------
-constexpr int SL_MAX_T = 16;
-constexpr int SL_MAX_K = 1024;
-constexpr int SL_LEFT = 1, SL_TOP = 2, SL_RIGHT = 4, SL_BOTTOM = 8;  // interior sides of a tile (slicing.edges)
-
-// grid G, 1024 threads: thread r owns entry r of every tile's list (K <= 1024).  What a thread knows about its 16 entries
-// lives in LDS (one byte each: the survivors of its wave before it, or SL_DROPPED), not in registers: the loops over the
-// tiles stay rolled, and the keys are read again where they are needed (they sit in L2).
-constexpr unsigned char SL_DROPPED = 0xFF;
-
-__global__ __launch_bounds__(1024) void od_slice_rank(const u64* __restrict__ keys, const int* __restrict__ counts,
-                                                      const float* __restrict__ boxes, const float* __restrict__ tiles,
-                                                      const int* __restrict__ edges, int T, int P, int NC, int K, int KP,
-                                                      float edge_lo, float edge_hi, u64* __restrict__ skeys,
-                                                      f32x4* __restrict__ sbox, int* __restrict__ scls,
-                                                      int* __restrict__ msrc, int* __restrict__ mcount) {
-  __shared__ unsigned lconf[SL_MAX_T * SL_MAX_K];      // conf bits of every compacted list, descending
-  __shared__ unsigned char lpre[SL_MAX_T * SL_MAX_K];  // per entry: survivors of its wave before it, or SL_DROPPED
-  __shared__ int wtot[SL_MAX_T * 16];                  // survivors per (tile, wave)
-  __shared__ int wpre[SL_MAX_T * 16];                  // survivors of the tile in the waves before this one
-  __shared__ int lcnt[SL_MAX_T];
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const bool rule = edge_lo >= 0.f;
-  for (int t = 0; t < T; ++t) {
-    const long long row = (long long)g * T + t;
-    const int cnt = min(max(counts[row], 0), K);
-    bool keep = tid < cnt;
-    const int e = rule ? edges[row] : 0;
-    if (keep && e) {  // cut at a seam: the box touches an interior side of its tile
-      const unsigned p = min(od_key_flat(keys[row * K + tid]) / (unsigned)NC, (unsigned)(P - 1));
-      const f32x4 bx = *(const f32x4*)(boxes + (row * P + p) * 4);
-      keep = !(((e & SL_LEFT) && bx[0] <= edge_lo) || ((e & SL_TOP) && bx[1] <= edge_lo) ||
-               ((e & SL_RIGHT) && bx[2] >= edge_hi) || ((e & SL_BOTTOM) && bx[3] >= edge_hi));
-    }
-    const u64 m = __ballot(keep);
-    lpre[t * SL_MAX_K + tid] = keep ? (unsigned char)__popcll(m & ((1ull << lane) - 1ull)) : SL_DROPPED;
-    if (lane == 0) wtot[t * 16 + wv] = __popcll(m);
-  }
-  __syncthreads();
-  if (tid < T * 16) {  // (tile, wave) = (tid / 16, tid % 16)
-    const int base = tid & ~15;
-    int pre = 0;
-    for (int w = 0; w < (tid & 15); ++w) pre += wtot[base + w];
-    wpre[tid] = pre;
-    if ((tid & 15) == 15) lcnt[tid >> 4] = pre + wtot[tid];
-  }
-  __syncthreads();
-  for (int t = 0; t < T; ++t) {  // the compacted lists: order kept, so still sorted
-    const unsigned char v = lpre[t * SL_MAX_K + tid];
-    if (v != SL_DROPPED)
-      lconf[t * SL_MAX_K + wpre[t * 16 + wv] + v] = od_key_score_bits(keys[((long long)g * T + t) * K + tid]);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int total = 0;
-    for (int t = 0; t < T; ++t) total += lcnt[t];
-    mcount[g] = min(K, total);
-  }
-  for (int t = 0; t < T; ++t) {
-    const unsigned char v = lpre[t * SL_MAX_K + tid];
-    if (v == SL_DROPPED) continue;
-    const int pos = wpre[t * 16 + wv] + v;  // position in the compacted list
-    const unsigned cb = lconf[t * SL_MAX_K + pos];
-    int rank = pos;
-    for (int u = 0; u < T; ++u) {
-      if (u == t) continue;
-      // entries of list u that precede (cb, t): conf > cb, and conf == cb too when u < t
-      const unsigned* lu = lconf + u * SL_MAX_K;
-      int lo = 0, hi = lcnt[u];
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        const unsigned x = lu[mid];
-        if (u < t ? x >= cb : x > cb) lo = mid + 1; else hi = mid;
-      }
-      rank += lo;
-    }
-    if (rank >= K) continue;
-    const long long row = (long long)g * T + t;
-    const unsigned flat = od_key_flat(keys[row * K + tid]);
-    unsigned p = flat / (unsigned)NC;
-    const unsigned c = flat - p * (unsigned)NC;
-    p = min(p, (unsigned)(P - 1));  // a malformed key must not read outside the row's box table
-    const f32x4 bx = *(const f32x4*)(boxes + (row * P + p) * 4);
-    const f32x4 a = *(const f32x4*)(tiles + row * 4);  // (ox, oy, sx, sy)
-    f32x4 m;
-    m[0] = fminf(fmaxf(a[0] + a[2] * bx[0], 0.f), 1.f);
-    m[1] = fminf(fmaxf(a[1] + a[3] * bx[1], 0.f), 1.f);
-    m[2] = fminf(fmaxf(a[0] + a[2] * bx[2], 0.f), 1.f);
-    m[3] = fminf(fmaxf(a[1] + a[3] * bx[3], 0.f), 1.f);
-    const long long o = (long long)g * KP + rank;
-    skeys[o] = od_make_key(cb, (unsigned)(rank * NC + (int)c));
-    sbox[o] = m;
-    scls[o] = (int)c;
-    msrc[o * 2] = t;
-    msrc[o * 2 + 1] = (int)flat;
-  }
-}
-
 }  // namespace
 
 extern "C" int od_tiles_workspace_plan(od_tile_desc* descs_host, int N, int H, int W, long long* workspace_bytes) {
@@ -264,55 +157,4 @@ extern "C" int od_tiles_resize(od_ctx* ctx, const od_tile_desc* descs_host, cons
   hipLaunchKernelGGL(od_tiles_pass2_k, dim3(grid_x((int64_t)H * W), N), dim3(256), 0, s, blob, descs, ws, out, H, W);
   OD_CHECK_LAUNCH();
   return OD_OK;
-}
-
-extern "C" size_t od_slice_merge_workspace_bytes(int G, int T, int K) {
-  if (G <= 0 || T < 1 || T > SL_MAX_T || K <= 0 || K > SL_MAX_K) return 0;
-  return od_merge_workspace_bytes(G, K);  // the merged table holds K candidates however many tiles feed it
-}
-
-// od_slice_merge (soft null) and od_slice_merge_soft: the rank kernel, then the greedy or the soft scan, then vote-and-gather
-static int slice_merge(const char* who, od_ctx* ctx, const uint64_t* keys, const int32_t* counts, const float* boxes,
-                       const float* tiles, const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo, float edge_hi,
-                       float iou_threshold, int strict, int max_det, const od_soft_nms_cfg* soft, float vote_iou, float* out,
-                       int32_t* src, int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream) {
-  OD_REQUIRE(ctx && keys && counts && boxes && tiles && edges && out && keep_count && workspace, "%s: null argument", who);
-  OD_REQUIRE(T >= 1 && T <= SL_MAX_T, "%s: T = %d outside 1..%d", who, T, SL_MAX_T);
-  OD_REQUIRE(NC >= 1 && NC <= OD_MAX_NC, "%s: NC = %d outside the supported class counts 1..%d", who, NC, OD_MAX_NC);
-  OD_REQUIRE(G > 0 && G <= 65535 && K > 0 && K <= SL_MAX_K && max_det > 0, "%s: bad dims (K <= 1024)", who);
-  OD_REQUIRE(P > 0 && (long long)P * NC < (1LL << 31), "%s: P * NC must fit 31 bits", who);
-  const size_t need = od_merge_workspace_bytes(G, K);
-  if (workspace_bytes < need) {
-    od_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
-    return OD_ERR_WORKSPACE;
-  }
-  const OdMergeWs w = od_merge_workspace(workspace, G, K);
-  u64* skeys;
-  f32x4* sbox;
-  int* scls;
-  int KP;
-  od_nms_sorted_buffers(w.nms, G, K, &skeys, &sbox, &scls, &KP);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(od_slice_rank, dim3(G), dim3(1024), 0, s, (const u64*)keys, counts, boxes, tiles, edges, T, P, NC, K, KP,
-                     edge_lo, edge_hi, skeys, sbox, scls, w.msrc, w.mcount);
-  OD_CHECK_LAUNCH();
-  return od_merge_nms_vote_launch(w, G, NC, K, iou_threshold, strict, max_det, vote_iou, out, src, keep_count, s, soft);
-}
-
-extern "C" int od_slice_merge(od_ctx* ctx, const uint64_t* keys, const int32_t* counts, const float* boxes, const float* tiles,
-                              const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo, float edge_hi,
-                              float iou_threshold, int strict, int max_det, float vote_iou, float* out, int32_t* src,
-                              int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream) {
-  return slice_merge("od_slice_merge", ctx, keys, counts, boxes, tiles, edges, G, T, P, NC, K, edge_lo, edge_hi, iou_threshold,
-                     strict, max_det, nullptr, vote_iou, out, src, keep_count, workspace, workspace_bytes, stream);
-}
-
-extern "C" int od_slice_merge_soft(od_ctx* ctx, const uint64_t* keys, const int32_t* counts, const float* boxes,
-                                   const float* tiles, const int32_t* edges, int G, int T, int P, int NC, int K, float edge_lo,
-                                   float edge_hi, const od_soft_nms_cfg* cfg, float vote_iou, float* out, int32_t* src,
-                                   int32_t* keep_count, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = od_soft_cfg_check("od_slice_merge_soft", cfg, K)) return rc;
-  return slice_merge("od_slice_merge_soft", ctx, keys, counts, boxes, tiles, edges, G, T, P, NC, K, edge_lo, edge_hi,
-                     cfg->iou_threshold, cfg->strict, cfg->max_det, cfg, vote_iou, out, src, keep_count, workspace,
-                     workspace_bytes, stream);
 }

@@ -3,13 +3,13 @@
 // compares the two bit for bit.
 //
 // od_soft_scan_k: one workgroup per image on the rank-ordered keys / boxes / classes a sort (od_nms_sort), refine
-// (od_detect_refine_sort and its streamed form) or merge-rank kernel (od_tta_merge_rank, od_slice_rank) left in the NMS
+// (od_detect_refine_sort and its streamed form) or merge-rank kernel (od_merge_rank, merge.hip) left in the NMS
 // workspace: the candidates go to LDS, then od_soft_nms_scan (topk_common.h) -- every thread keeps its candidate's box, class
 // and running score in registers; a round is one 64-bit argmax (DPP steps in the wave + one LDS slot per wave, one barrier) and
 // one rescoring pass against the winner.  Latency-bound: up to max_det rounds, each a few hundred cycles.
 //   od_soft_nms      = od_nms's sort launch + the scan
 //   od_detect_soft   = od_detect_candidates' launches + the scan
-//   od_tta_merge_soft / od_slice_merge_soft (tta.hip, slice.hip) = their rank kernel + the scan + the vote-and-gather kernel
+//   od_tta_merge_soft / od_slice_merge_soft (merge.hip) = the rank kernel + the scan + the vote-and-gather kernel
 // Compiled with -ffp-contract=off: the IoU terms, the decay and od_exp_neg are one rounding per op, as numpy's.
 #include "post_common.h"
 
@@ -48,7 +48,7 @@ int od_soft_cfg_check(const char* who, const od_soft_nms_cfg* cfg, int K) {
   OD_REQUIRE(cfg->method >= 0 && cfg->method <= 2, "%s: method = %d outside 0 (hard), 1 (linear), 2 (gaussian)", who, cfg->method);
   OD_REQUIRE(cfg->method != 2 || cfg->sigma > 0.f, "%s: the gaussian method needs sigma > 0", who);
   OD_REQUIRE(cfg->min_conf >= 1e-6f, "%s: min_conf must be >= 1e-6", who);
-  OD_REQUIRE(K > 0 && K <= 1024, "%s: bad dims (K <= 1024)", who);
+  OD_REQUIRE(K > 0 && K <= OD_MERGE_MAX_K, "%s: bad dims (K <= %d)", who, OD_MERGE_MAX_K);
   OD_REQUIRE(cfg->max_det > 0, "%s: max_det must be > 0", who);
   return OD_OK;
 }

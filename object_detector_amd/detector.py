@@ -10,8 +10,10 @@ results are gathered on the host.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import pathlib
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -24,6 +26,8 @@ from .postprocess import SOFT_SIGMA, Postprocessor, check_nms_args
 from .tta import VOTE_IOU, TtaPostprocessor, normalize_views
 
 DEFAULT_CONF_THRESHOLD = 0.01  # [BUILD-DEFINED]: mAP needs the low-confidence tail (voc_evaluate.py:27 passes 0.6)
+PREFETCH_AHEAD = 2  # predict(): batches whose host work is started before the current one is submitted
+N_STAGING = PREFETCH_AHEAD + 2  # a staging buffer is busy from the start of its decode until its upload has completed
 VOC_WEIGHTS_ENV = "OD_VOC_WEIGHTS"
 
 
@@ -235,6 +239,7 @@ class ObjectDetector:
             self._pipes.append(_Pipeline(net, post, torch.cuda.Stream(device=self.device), self._make_tta(post),
                                          self._make_slc(net, post)))
         self._next = 0
+        self._hbufs = None  # predict()'s pinned staging: N_STAGING x [buffer, event of its last upload], made on first use
         self._calibrated = len(self._pipes) < 2 or os.environ.get("OD_INFLIGHT_CALIBRATE", "1") == "0"
 
     def _nms_kw(self):
@@ -349,48 +354,53 @@ class ObjectDetector:
         self._no_batch_entry_with_slices("submit", graph)
         if self.tta is not None:
             self._no_graph_with_tta(graph)
+        with self._next_pipeline() as (ticket, p):  # x_u8 was produced on the caller's stream
+            self._forward_post(p, x_u8, conf_threshold, graph, gather)
+        x_u8.record_stream(p.stream)
+        return ticket
+
+    @contextlib.contextmanager
+    def _next_pipeline(self):
+        """What every submit shares: the streams are calibrated on first use, the next pipeline is taken, its stream waits
+        for the caller's and is the current one inside the block, and `done` is recorded behind what the block queued.
+        -> (ticket, pipeline)"""
         if not self._calibrated:
             self._pick_streams()
         i = self._next
         self._next = (i + 1) % len(self._pipes)
         p = self._pipes[i]
-        p.stream.wait_stream(torch.cuda.current_stream(self.device))  # x_u8 was produced on the caller's stream
+        p.stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(p.stream):
-            if p.tta is not None:
-                p.tta.run(p.net, x_u8, conf_threshold)
-            else:
-                pred = p.net.forward(x_u8, graph=graph)
-                p.post.run(pred, conf_threshold)
-                if gather:
-                    p.post.gather()  # kept detections -> one record block -> pinned host memory, still on this stream
+            yield i, p
             p.done.record()
-        x_u8.record_stream(p.stream)
-        return i
+
+    @staticmethod
+    def _forward_post(p, x_u8, conf_threshold, graph=False, gather=True):
+        """The network and the post-processing of one unsliced batch on the current stream (x_u8 None: p.net.input)."""
+        if p.tta is not None:
+            p.tta.run(p.net, x_u8, conf_threshold)  # x_u8 None: the mirror is taken from the decoded input
+        else:
+            pred = p.net.forward(x_u8, graph=graph)
+            p.post.run(pred, conf_threshold)
+            if gather:
+                p.post.gather()  # kept detections -> one record block -> pinned host memory, still on this stream
+
+    def _decoder(self, p):
+        """The pipeline's devdecode.BatchDecoder, made on first use."""
+        if p.decoder is None:
+            from .devdecode import BatchDecoder
+            p.decoder = BatchDecoder(self.device)
+        return p.decoder
 
     def _submit_images(self, items, conf_threshold=DEFAULT_CONF_THRESHOLD) -> int:
         """submit() for image_decode="device": the upload and the decode / resize kernels of `items` (devdecode.prepare
         results) write the next pipeline's Net.input on its stream, and the network runs on that input without a copy."""
-        if not self._calibrated:
-            self._pick_streams()
-        i = self._next
-        self._next = (i + 1) % len(self._pipes)
-        p = self._pipes[i]
-        if p.decoder is None:
-            from .devdecode import BatchDecoder
-            p.decoder = BatchDecoder(self.device)
-        p.stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(p.stream):
-            p.decoder.run(items, p.net.input)
-            if p.tta is not None:
-                p.tta.run(p.net, None, conf_threshold)  # the mirror is taken from the decoded input
-            else:
-                pred = p.net.forward(None)
-                p.post.run(pred, conf_threshold)
-                p.post.gather()
-            p.done.record()
+        with self._next_pipeline() as (ticket, p):
+            self._decoder(p).run(items, p.net.input)
+            self._forward_post(p, None, conf_threshold)
         for it in items:
             self.decode_stats[it[0]] += 1
-        return i
+        return ticket
 
     def _pick_streams(self):
         """One stream per pipeline, on DIFFERENT hardware queues.  HIP deals streams onto a few hardware queues (4 by
@@ -473,16 +483,62 @@ class ObjectDetector:
         route = self.image_decode if image_decode is None else image_decode
         if route not in ("host", "device"):
             raise ValueError(f"image_decode must be 'host' or 'device', got {route!r}")
-        if self.slices is not None:
-            return self._predict_sliced(X, conf_threshold, route)
         rank, world = dist_info(self.use_multi_gpu)
         mine = shard_indices(len(X), rank, world)
+        run = self._predict_plain if self.slices is None else self._predict_sliced
+        results = gather_results(run(X, mine, conf_threshold, route), world)
+        return [results[i] for i in range(len(X))]
+
+    def _run_batches(self, batches, start, finish, drain):
+        """The look-ahead loop of predict(): start(bi) begins the host work of batch bi and returns its futures -- issued
+        PREFETCH_AHEAD batches early, so decode + upload of the next batches overlaps the device work of this one --,
+        finish(bi, results) submits the batch and returns what drain(image indices, that) reads its results with.  A
+        pipeline's results are drained before it is reused, the rest at the end."""
+        pending = []  # (image indices, what finish returned), oldest first
+        futs = {bi: start(bi) for bi in range(min(PREFETCH_AHEAD + 1, len(batches)))}
+        for bi, idx in enumerate(batches):
+            if bi + PREFETCH_AHEAD + 1 < len(batches):
+                futs[bi + PREFETCH_AHEAD + 1] = start(bi + PREFETCH_AHEAD + 1)
+            res = [f.result() for f in futs.pop(bi)]
+            if len(pending) == len(self._pipes):  # the pipeline about to be reused still holds unread results
+                drain(*pending.pop(0))
+            pending.append((idx, finish(bi, res)))
+        for entry in pending:
+            drain(*entry)
+
+    @staticmethod
+    def _decode_threads():
+        """predict()'s pool of decode threads: OD_DECODE_THREADS, or up to 8."""
+        nthreads = int(os.environ.get("OD_DECODE_THREADS", "0")) or min(8, os.cpu_count() or 1)
+        return ThreadPoolExecutor(max_workers=max(1, nthreads))
+
+    def _stage(self, bi):
+        """Pinned staging buffer of batch bi as a numpy array uint8 [B,H,W,3], free to be written."""
+        if self._hbufs is None:
+            shape = (self.batch_size,) + tuple(self.input_size) + (3,)
+            self._hbufs = [[torch.zeros(shape, dtype=torch.uint8).pin_memory(), None] for _ in range(N_STAGING)]
+        hb = self._hbufs[bi % N_STAGING]
+        if hb[1] is not None:
+            hb[1].synchronize()  # the upload that last read this pinned buffer
+            hb[1] = None
+        return hb[0].numpy()
+
+    def _upload_stage(self, bi):
+        """Queue the upload of batch bi's staging buffer on the current stream -> the device tensor."""
+        hb = self._hbufs[bi % N_STAGING]
+        x = hb[0].to(self.device, non_blocking=True)
+        hb[1] = torch.cuda.Event()
+        hb[1].record(torch.cuda.current_stream(self.device))
+        return x
+
+    def _predict_plain(self, X, mine, conf_threshold, route):
+        """predict() without slices for the images `mine` of this rank -> {index: prediction}."""
         results = {}
         B = self.batch_size
-        pending = []  # (ticket, image indices, scales): decode + upload of batch k+1.. overlaps the device work of batch k
+        batches = [mine[s:s + B] for s in range(0, len(mine), B)]
 
-        def drain(entry):
-            ticket, idx, scales = entry
+        def drain(idx, submitted):
+            ticket, scales = submitted
             self.collect(ticket)
             for i, pr in zip(idx, self._collect(len(idx), scales, self._pipes[ticket].post)):
                 results[i] = pr
@@ -493,17 +549,11 @@ class ObjectDetector:
         # staging buffers that are uploaded asynchronously.  OD_DECODE_PROCS=N: N spawned worker PROCESSES (numpy + PIL
         # only, never the GPU) writing into one shared-memory staging block -- scales with the cores (measured 9.5 k
         # decodes/s on 16); opt-in because spawn re-imports the caller's __main__ (needs the usual __main__ guard).
-        batches = [mine[s:s + B] for s in range(0, len(mine), B)]
-        ahead = 2
-        nb = ahead + 2  # a staging buffer is busy from the start of its decode until its upload has completed
         nprocs = int(os.environ.get("OD_DECODE_PROCS", "0"))
-        img_bytes = self.input_size[0] * self.input_size[1] * 3
+        own_pool = None
         if route == "device":  # pool threads read files and parse headers; the device decodes and resizes
-            from concurrent.futures import ThreadPoolExecutor
-
             from .devdecode import prepare
-            nthreads = int(os.environ.get("OD_DECODE_THREADS", "0")) or min(8, os.cpu_count() or 1)
-            own_pool = pool = ThreadPoolExecutor(max_workers=max(1, nthreads))
+            own_pool = pool = self._decode_threads()
 
             def start(bi):
                 return [pool.submit(prepare, X[i], tuple(self.input_size), self.keep_aspect) for i in batches[bi]]
@@ -511,6 +561,8 @@ class ObjectDetector:
             def finish(bi, items):
                 return self._submit_images(items, conf_threshold), [it[3] for it in items]
         elif nprocs > 0:
+            nb = N_STAGING
+            img_bytes = self.input_size[0] * self.input_size[1] * 3
             pool, shm = self._decode_procs(nprocs, nb * B * img_bytes)
             stage = np.ndarray((nb, B) + tuple(self.input_size) + (3,), np.uint8, buffer=shm.buf)
 
@@ -532,19 +584,10 @@ class ObjectDetector:
                     out += [_Chunk(fut, j) for j in range(len(part))]
                 return out
 
-            def upload(bi):
-                return torch.from_numpy(stage[bi % nb]).to(self.device)
-            own_pool = None
-
             def finish(bi, scales):
-                return self.submit(upload(bi), conf_threshold, gather=True), scales
+                return self.submit(torch.from_numpy(stage[bi % nb]).to(self.device), conf_threshold, gather=True), scales
         else:
-            from concurrent.futures import ThreadPoolExecutor
-            nthreads = int(os.environ.get("OD_DECODE_THREADS", "0")) or min(8, os.cpu_count() or 1)
-            if getattr(self, "_hbufs", None) is None:
-                self._hbufs = [[torch.zeros((B,) + tuple(self.input_size) + (3,), dtype=torch.uint8).pin_memory(), None]
-                               for _ in range(nb)]
-            own_pool = pool = ThreadPoolExecutor(max_workers=max(1, nthreads))
+            own_pool = pool = self._decode_threads()
 
             def load_into(x, dst):  # worker thread: decode + resize, then the (slow, uncached) write into pinned memory
                 img, sc = load_image(x, self.input_size, self.keep_aspect, True)
@@ -552,39 +595,17 @@ class ObjectDetector:
                 return sc
 
             def start(bi):
-                hb = self._hbufs[bi % nb]
-                if hb[1] is not None:
-                    hb[1].synchronize()  # the upload that last read this pinned buffer
-                    hb[1] = None
-                host = hb[0].numpy()
+                host = self._stage(bi)
                 return [pool.submit(load_into, X[i], host[j]) for j, i in enumerate(batches[bi])]
 
-            def upload(bi):
-                hb = self._hbufs[bi % nb]
-                x = hb[0].to(self.device, non_blocking=True)
-                hb[1] = torch.cuda.Event()
-                hb[1].record(torch.cuda.current_stream(self.device))
-                return x
-
             def finish(bi, scales):
-                return self.submit(upload(bi), conf_threshold, gather=True), scales
+                return self.submit(self._upload_stage(bi), conf_threshold, gather=True), scales
         try:
-            futs = {bi: start(bi) for bi in range(min(ahead + 1, len(batches)))}
-            for bi, idx in enumerate(batches):
-                if bi + ahead + 1 < len(batches):
-                    futs[bi + ahead + 1] = start(bi + ahead + 1)
-                res = [f.result() for f in futs.pop(bi)]
-                if len(pending) == len(self._pipes):  # the pipeline about to be reused still holds unread results
-                    drain(pending.pop(0))
-                ticket, scales = finish(bi, res)
-                pending.append((ticket, idx, scales))
+            self._run_batches(batches, start, finish, drain)
         finally:
             if own_pool is not None:
                 own_pool.shutdown(wait=True)
-        for entry in pending:
-            drain(entry)
-        results = gather_results(results, world)
-        return [results[i] for i in range(len(X))]
+        return results
 
     # -- sliced inference -------------------------------------------------------------------------------------------
     def _submit_sliced(self, conf_threshold, x_u8=None, sizes=None, images=None, cut_only=False) -> int:
@@ -592,55 +613,37 @@ class ObjectDetector:
         Host route: x_u8 uint8 [B,H,W,3] holds the tiles (row g*T + t = tile t of image g), sizes the images' (w, h).
         Device route: images = the uint8 [h,w,3] arrays; one upload, then od_tiles_resize writes the pipeline's Net.input.
         cut_only: the images are the ones the pipeline's decoder uploaded last (scripts/bench_slices.py)."""
-        if not self._calibrated:
-            self._pick_streams()
-        i = self._next
-        self._next = (i + 1) % len(self._pipes)
-        p = self._pipes[i]
-        p.stream.wait_stream(torch.cuda.current_stream(self.device))  # x_u8 was produced on the caller's stream
-        with torch.cuda.stream(p.stream):
+        with self._next_pipeline() as (ticket, p):  # x_u8 was produced on the caller's stream
             if images is not None:
-                if p.decoder is None:
-                    from .devdecode import BatchDecoder
-                    p.decoder = BatchDecoder(self.device)
                 if cut_only:
-                    p.decoder.cut_tiles(p.net.input)
+                    self._decoder(p).cut_tiles(p.net.input)
                 else:
-                    sizes = p.decoder.run_tiles(images, self.slices, p.net.input)
+                    sizes = self._decoder(p).run_tiles(images, self.slices, p.net.input)
             p.slc.run(p.net, x_u8, sizes, conf_threshold)
-            p.done.record()
         if x_u8 is not None:
             x_u8.record_stream(p.stream)
-        return i
+        return ticket
 
-    def _predict_sliced(self, X, conf_threshold, route):
-        """predict() with slices: G = batch_size // T images per network batch.  Same shape as the plain route: images are
-        sharded by index over the ranks, pool threads prepare the next batches while this one runs, a pipeline's results are
-        read before it is reused.  Host route: the threads crop and resize every tile with PIL into pinned staging.  Device
-        route: the threads decode every image ONCE at its own size (files count as "fallback" in decode_stats -- the device
-        JPEG decoder does not feed the tile cutter), the device cuts the tiles.  The pool is always threads (OD_DECODE_PROCS
-        is for the plain route)."""
-        from concurrent.futures import ThreadPoolExecutor
+    def _predict_sliced(self, X, mine, conf_threshold, route):
+        """predict() with slices for the images `mine` of this rank -> {index: prediction}: G = batch_size // T images per
+        network batch.  Same shape as the plain route: pool threads prepare the next batches while this one runs, a
+        pipeline's results are read before it is reused.  Host route: the threads crop and resize every tile with PIL into
+        pinned staging.  Device route: the threads decode every image ONCE at its own size (files count as "fallback" in
+        decode_stats -- the device JPEG decoder does not feed the tile cutter), the device cuts the tiles.  The pool is
+        always threads (OD_DECODE_PROCS is for the plain route)."""
         grid = self.slices
-        T, B = grid.T, self.batch_size
-        G = B // T
-        rank, world = dist_info(self.use_multi_gpu)
-        mine = shard_indices(len(X), rank, world)
+        T = grid.T
+        G = self.batch_size // T
         batches = [mine[s:s + G] for s in range(0, len(mine), G)]
         results = {}
-        pending = []  # (ticket, image indices)
 
-        def drain(entry):
-            ticket, idx = entry
+        def drain(idx, ticket):
             p = self._pipes[ticket]
             p.done.synchronize()
             for i, (k, confs, bxs) in zip(idx, p.slc.detections_host(len(idx))):
                 results[i] = ObjectsPrediction(k, confs, bxs, None)  # word 0 of a merged record is the class
 
-        ahead = 2
-        nb = ahead + 2  # a staging buffer is busy from the start of its decode until its upload has completed
-        nthreads = int(os.environ.get("OD_DECODE_THREADS", "0")) or min(8, os.cpu_count() or 1)
-        pool = ThreadPoolExecutor(max_workers=max(1, nthreads))
+        pool = self._decode_threads()
         if route == "device":
             def start(bi):
                 return [pool.submit(slicing.load_native, X[i]) for i in batches[bi]]
@@ -651,39 +654,17 @@ class ObjectDetector:
                     self.decode_stats["fallback" if it[1] else "array"] += 1
                 return ticket
         else:
-            if getattr(self, "_hbufs", None) is None:
-                self._hbufs = [[torch.zeros((B,) + tuple(self.input_size) + (3,), dtype=torch.uint8).pin_memory(), None]
-                               for _ in range(nb)]
-
             def load_into(x, dst):  # worker thread: decode, then crop + resize every tile into pinned memory
                 return slicing.host_tiles(slicing.load_native(x)[0], grid, self.input_size, dst)
 
             def start(bi):
-                hb = self._hbufs[bi % nb]
-                if hb[1] is not None:
-                    hb[1].synchronize()  # the upload that last read this pinned buffer
-                    hb[1] = None
-                host = hb[0].numpy()
+                host = self._stage(bi)
                 return [pool.submit(load_into, X[i], host[j * T:(j + 1) * T]) for j, i in enumerate(batches[bi])]
 
             def finish(bi, sizes):
-                hb = self._hbufs[bi % nb]
-                x = hb[0].to(self.device, non_blocking=True)
-                hb[1] = torch.cuda.Event()
-                hb[1].record(torch.cuda.current_stream(self.device))
-                return self._submit_sliced(conf_threshold, x_u8=x, sizes=sizes)
+                return self._submit_sliced(conf_threshold, x_u8=self._upload_stage(bi), sizes=sizes)
         try:
-            futs = {bi: start(bi) for bi in range(min(ahead + 1, len(batches)))}
-            for bi, idx in enumerate(batches):
-                if bi + ahead + 1 < len(batches):
-                    futs[bi + ahead + 1] = start(bi + ahead + 1)
-                res = [f.result() for f in futs.pop(bi)]
-                if len(pending) == len(self._pipes):  # the pipeline about to be reused still holds unread results
-                    drain(pending.pop(0))
-                pending.append((finish(bi, res), idx))
+            self._run_batches(batches, start, finish, drain)
         finally:
             pool.shutdown(wait=True)
-        for entry in pending:
-            drain(entry)
-        results = gather_results(results, world)
-        return [results[i] for i in range(len(X))]
+        return results

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -37,6 +38,18 @@ def check_nms_args(nms="hard", soft_sigma=SOFT_SIGMA, soft_min_conf=None):
         if not soft_min_conf >= SOFT_MIN_CONF_FLOOR:
             raise ValueError(f"soft_min_conf must be >= {SOFT_MIN_CONF_FLOOR}, got {soft_min_conf!r}")
     return nms, sigma, soft_min_conf
+
+
+def records_host(block, n_valid):
+    """A pinned record block [B, 1 + 6*max_det] (word 0 = the keep count, row r = {word0 (int bits), conf, x1, y1, x2, y2})
+    -> [(word0 i32 [n], conf f32 [n], boxes f32 [n,4])] for its first n_valid images."""
+    a = block.numpy()
+    out = []
+    for b in range(n_valid):
+        n = int(a[b, :1].view(np.int32)[0])
+        rows = a[b, 1:1 + 6 * n].reshape(n, 6)
+        out.append((rows[:, 0].copy().view(np.int32), rows[:, 1].copy(), rows[:, 2:6].copy()))
+    return out
 
 
 class Postprocessor:
@@ -160,14 +173,18 @@ class Postprocessor:
 
     def detections_host(self, n_valid):
         """-> [(flat i32 [n], conf f32 [n], boxes f32 [n,4])] for the first n_valid images, from the pinned block."""
-        import numpy as np
-        a = self.det_host.numpy()
-        out = []
-        for b in range(n_valid):
-            n = int(a[b, :1].view(np.int32)[0])
-            rows = a[b, 1:1 + 6 * n].reshape(n, 6)
-            out.append((rows[:, 0].copy().view(np.int32), rows[:, 1].copy(), rows[:, 2:6].copy()))
-        return out
+        return records_host(self.det_host, n_valid)
+
+    def candidates(self, pred: torch.Tensor, conf_threshold: float, boxes, keys, counts):
+        """pred [B,P,C] -> boxes [B,P,4] / sorted keys [B,K] / counts [B] in the caller's buffers (od_detect_candidates:
+        od_detect without the NMS, clip = 1): what the merges of tta.py and slicing.py take one list per view / row from."""
+        assert pred.dtype == torch.float32 and pred.is_contiguous() and tuple(pred.shape) == (self.B, self.P, self.NC + 6)
+        self._conf_threshold = float(conf_threshold)
+        _lib.check(self.lib.od_detect_candidates(self.ctx.handle, pred.data_ptr(), self.priors.data_ptr(), self.B, self.P,
+                                                 self.NC, self.loc_scale, 1, float(conf_threshold), self.K, boxes.data_ptr(),
+                                                 None, keys.data_ptr(), counts.data_ptr(), self.ws_det.data_ptr(),
+                                                 self.ws_det_bytes, self.ws_nms.data_ptr(), self.ws_nms_bytes, _stream_ptr()),
+                   "od_detect_candidates")
 
     def run(self, pred: torch.Tensor, conf_threshold: float):
         """pred [B,P,C] -> (keep_flat i32 [B,max_det] (-1 padded), keep_count i32 [B]); boxes / keys stay on device.

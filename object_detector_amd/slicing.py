@@ -2,15 +2,20 @@
 of the network batch, and the candidate lists of an image's tiles are merged in ONE NMS + box voting on the device.
 
 [BUILD-DEFINED] (the reference has no slicing; DESIGN.md "Sliced inference" freezes the semantics).  This module is the single
-definition of the geometry: both image routes of `ObjectDetector.predict` and the tests call it.  It imports numpy and the
-stdlib only; SlicePostprocessor (the device side, beside the pipeline's Postprocessor as TtaPostprocessor is) imports torch
-when it is constructed.
+definition of the geometry: both image routes of `ObjectDetector.predict` and the tests call it.  SlicePostprocessor is the
+device side, beside the pipeline's Postprocessor as TtaPostprocessor is.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 
 import numpy as np
+import torch
+
+from . import _lib
+from .net import _stream_ptr
+from .postprocess import records_host
 
 MAX_TILES = 16
 VOTE_IOU = 0.5  # [BUILD-DEFINED] box-voting overlap (tta.VOTE_IOU)
@@ -126,7 +131,6 @@ class SlicePostprocessor:
     arrays, the merge workspace, and the record block of the G = B // T images of a batch with its pinned mirror."""
 
     def __init__(self, post, grid, vote_iou=VOTE_IOU):
-        import torch
         self.post, self.lib, self.ctx, self.grid = post, post.lib, post.ctx, grid
         self.vote_iou = float(vote_iou)
         B, P, K = post.B, post.P, post.K
@@ -146,7 +150,7 @@ class SlicePostprocessor:
         self.edges = self.geom[n * 4:]
         self._geom_copied = None
         self._geom_sizes = None  # the image sizes the device arrays were last made for
-        self.src =torch.empty((G, post.max_det, 2), dtype=torch.int32, device=dev)
+        self.src = torch.empty((G, post.max_det, 2), dtype=torch.int32, device=dev)
         self.keep_count = torch.empty((G,), dtype=torch.int32, device=dev)
         self.det = torch.empty((G, 1 + 6 * post.max_det), dtype=torch.float32, device=dev)
         self.det_host = torch.empty((G, 1 + 6 * post.max_det), dtype=torch.float32).pin_memory()
@@ -155,7 +159,6 @@ class SlicePostprocessor:
 
     def set_geometry(self, sizes):
         """(w, h) of the batch's images (at most G) -> the tiles / edges device arrays, queued on the current stream."""
-        import torch
         sizes = [(int(w), int(h)) for w, h in sizes]
         assert len(sizes) <= self.G
         if sizes == self._geom_sizes:  # frames of one size: the arrays on the device are already these
@@ -175,41 +178,22 @@ class SlicePostprocessor:
         self._geom_copied.record()
 
     def candidates(self, pred, conf_threshold):
-        """pred of the whole batch -> boxes / sorted keys / counts of every row (od_detect_candidates, clip = 1)."""
-        import torch
-        from . import _lib
-        from .net import _stream_ptr
-        p = self.post
-        assert pred.dtype == torch.float32 and pred.is_contiguous() and tuple(pred.shape) == (p.B, p.P, p.NC + 6)
-        p._conf_threshold = float(conf_threshold)
-        _lib.check(self.lib.od_detect_candidates(self.ctx.handle, pred.data_ptr(), p.priors.data_ptr(), p.B, p.P, p.NC,
-                                                 p.loc_scale, 1, float(conf_threshold), p.K, self.boxes.data_ptr(), None,
-                                                 self.keys.data_ptr(), self.counts.data_ptr(), p.ws_det.data_ptr(),
-                                                 p.ws_det_bytes, p.ws_nms.data_ptr(), p.ws_nms_bytes, _stream_ptr()),
-                   "od_detect_candidates")
+        """pred of the whole batch -> boxes / sorted keys / counts of every row (Postprocessor.candidates)."""
+        self.post.candidates(pred, conf_threshold, self.boxes, self.keys, self.counts)
 
     def merge(self):
         """The rows' candidates -> self.det (record block of G images, word 0 of a row = class), self.src, self.keep_count;
         queues the single device->host copy of the block.  Rows from G*T on are never read."""
-        from . import _lib
-        from .net import _stream_ptr
         p = self.post
         lo, hi = self.grid.edge_lo_hi
-        if p.soft:  # the soft scan in place of the greedy one; the report carries the rescored confidences
-            import ctypes as C
-            cfg = p.soft_cfg()
-            _lib.check(self.lib.od_slice_merge_soft(self.ctx.handle, self.keys.data_ptr(), self.counts.data_ptr(),
-                                                    self.boxes.data_ptr(), self.tiles.data_ptr(), self.edges.data_ptr(), self.G,
-                                                    self.T, p.P, p.NC, p.K, lo, hi, C.byref(cfg), self.vote_iou,
-                                                    self.det.data_ptr(), self.src.data_ptr(), self.keep_count.data_ptr(),
-                                                    self.ws.data_ptr(), self.ws_bytes, _stream_ptr()), "od_slice_merge_soft")
-            self.det_host.copy_(self.det, non_blocking=True)
-            return self.det, self.keep_count
-        _lib.check(self.lib.od_slice_merge(self.ctx.handle, self.keys.data_ptr(), self.counts.data_ptr(), self.boxes.data_ptr(),
-                                           self.tiles.data_ptr(), self.edges.data_ptr(), self.G, self.T, p.P, p.NC, p.K, lo, hi,
-                                           p.iou_threshold, p.strict, p.max_det, self.vote_iou, self.det.data_ptr(),
-                                           self.src.data_ptr(), self.keep_count.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
-                                           _stream_ptr()), "od_slice_merge")
+        # the soft scan in place of the greedy one (the report carries the rescored confidences): the two ABIs differ in
+        # this argument group alone
+        entry, nms = ("od_slice_merge_soft", (C.byref(p.soft_cfg()),)) if p.soft else \
+            ("od_slice_merge", (p.iou_threshold, p.strict, p.max_det))
+        _lib.check(getattr(self.lib, entry)(self.ctx.handle, self.keys.data_ptr(), self.counts.data_ptr(), self.boxes.data_ptr(),
+                                            self.tiles.data_ptr(), self.edges.data_ptr(), self.G, self.T, p.P, p.NC, p.K, lo, hi,
+                                            *nms, self.vote_iou, self.det.data_ptr(), self.src.data_ptr(),
+                                            self.keep_count.data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream_ptr()), entry)
         self.det_host.copy_(self.det, non_blocking=True)
         return self.det, self.keep_count
 
@@ -222,10 +206,4 @@ class SlicePostprocessor:
 
     def detections_host(self, n_valid):
         """-> [(class i32 [n], conf f32 [n], boxes f32 [n,4])] for the first n_valid images, from the pinned block."""
-        a = self.det_host.numpy()
-        out = []
-        for g in range(n_valid):
-            n = int(a[g, :1].view(np.int32)[0])
-            rows = a[g, 1:1 + 6 * n].reshape(n, 6)
-            out.append((rows[:, 0].copy().view(np.int32), rows[:, 1].copy(), rows[:, 2:6].copy()))
-        return out
+        return records_host(self.det_host, n_valid)

@@ -69,32 +69,20 @@ class TtaPostprocessor:
         return self.mirrored
 
     def candidates(self, view: int, pred: torch.Tensor, conf_threshold: float):
-        """pred of view `view` -> its boxes / sorted keys / counts (od_detect_candidates: od_detect without the NMS)."""
-        p = self.post
-        assert pred.dtype == torch.float32 and pred.is_contiguous() and tuple(pred.shape) == (p.B, p.P, p.NC + 6)
-        p._conf_threshold = float(conf_threshold)
-        _lib.check(self.lib.od_detect_candidates(self.ctx.handle, pred.data_ptr(), p.priors.data_ptr(), p.B, p.P, p.NC,
-                                                 p.loc_scale, 1, float(conf_threshold), p.K, self.boxes[view].data_ptr(), None,
-                                                 self.keys[view].data_ptr(), self.counts[view].data_ptr(), p.ws_det.data_ptr(),
-                                                 p.ws_det_bytes, p.ws_nms.data_ptr(), p.ws_nms_bytes, _stream_ptr()),
-                   "od_detect_candidates")
+        """pred of view `view` -> its boxes / sorted keys / counts (Postprocessor.candidates)."""
+        self.post.candidates(pred, conf_threshold, self.boxes[view], self.keys[view], self.counts[view])
 
     def merge(self):
         """All views' candidates -> post.det (record block, word 0 of a row = class), self.src, post.keep_count; queues
         the single device->host copy of the block."""
         p = self.post
-        if p.soft:  # the soft scan in place of the greedy one; the report carries the rescored confidences
-            cfg = p.soft_cfg()
-            _lib.check(self.lib.od_tta_merge_soft(self.ctx.handle, self._desc, self.V, p.B, p.NC, p.K, C.byref(cfg),
-                                                  self.vote_iou, p.det.data_ptr(), self.src.data_ptr(),
-                                                  p.keep_count.data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream_ptr()),
-                       "od_tta_merge_soft")
-            p.det_host.copy_(p.det, non_blocking=True)
-            return p.det, p.keep_count
-        _lib.check(self.lib.od_tta_merge(self.ctx.handle, self._desc, self.V, p.B, p.NC, p.K, p.iou_threshold, p.strict,
-                                         p.max_det, self.vote_iou, p.det.data_ptr(), self.src.data_ptr(),
-                                         p.keep_count.data_ptr(), self.ws.data_ptr(), self.ws_bytes, _stream_ptr()),
-                   "od_tta_merge")
+        # the soft scan in place of the greedy one (the report carries the rescored confidences): the two ABIs differ in
+        # this argument group alone
+        entry, nms = ("od_tta_merge_soft", (C.byref(p.soft_cfg()),)) if p.soft else \
+            ("od_tta_merge", (p.iou_threshold, p.strict, p.max_det))
+        _lib.check(getattr(self.lib, entry)(self.ctx.handle, self._desc, self.V, p.B, p.NC, p.K, *nms, self.vote_iou,
+                                            p.det.data_ptr(), self.src.data_ptr(), p.keep_count.data_ptr(),
+                                            self.ws.data_ptr(), self.ws_bytes, _stream_ptr()), entry)
         p.det_host.copy_(p.det, non_blocking=True)
         return p.det, p.keep_count
 

@@ -111,32 +111,46 @@ def test_slice_merge_equals_reference(cuda, name, strict, vote_iou):
         assert np.array_equal(dev[k].cpu().numpy(), sc[k].view(np.uint8).reshape(-1)), k
 
 
-def test_one_tile_equals_tta_merge_with_one_view(cuda):
-    """T = 1 (one tile = the whole image, no interior side): the record block and keep counts of od_tta_merge with V = 1 on
-    the same lists."""
+@pytest.mark.parametrize("T", [1, 4])
+def test_tiles_equal_tta_merge_with_views(cuda, T):
+    """Tiles that are the whole image (affine row (0, 0, 1, 1), no interior side, the rule disabled) are unflipped views:
+    od_slice_merge on rows g * T + t and od_tta_merge on the same lists passed as V = T views give the same record block,
+    sources and keep counts, word for word.  G = B = 2; K = 200 is no multiple of 64 (a partial wave in the compaction);
+    the boxes lie in [0, 1], where the tiles' clamp changes nothing."""
     _lib, lib, h = _ctx(cuda)
-    sc, _ = _scenario("t1")
-    G, K, P, NC = sc["G"], sc["K"], sc["P"], sc["NC"]
-    dev = _device(cuda, sc)
+    G, K, P, NC = 2, 200, 4200, 20
+    rng = np.random.default_rng(L.seed_of("tiles_as_views", T))
+    keys, boxes = np.zeros((G * T, K), np.uint64), np.zeros((G * T, P, 4), F)
+    counts = np.array([K if r % 3 == 0 else int(rng.integers(1, K)) for r in range(G * T)], np.int32)
+    for r in range(G * T):
+        keys[r], boxes[r] = slice_ref.make_row(rng, K, P, NC, int(counts[r]), quantise=r % 2 == 0)
+    assert boxes.min() >= 0 and boxes.max() <= 1
+    sc = {"G": G, "T": T, "K": K, "P": P, "NC": NC, "keys": keys, "counts": counts, "boxes": boxes, "edge_lo": -1.0,
+          "edge_hi": 2.0, "tiles": np.tile(np.array([0, 0, 1, 1], F), (G * T, 1)), "edges": np.zeros(G * T, np.int32)}
     outs = []
     for which in ("slice", "tta"):
         out = L.Guarded((G, 1 + 6 * MAX_DET), torch.float32, cuda)
         src = L.Guarded((G, MAX_DET, 2), torch.int32, cuda)
         kc = L.Guarded((G,), torch.int32, cuda)
         if which == "slice":
-            nb = lib.od_slice_merge_workspace_bytes(G, 1, K)
+            nb = lib.od_slice_merge_workspace_bytes(G, T, K)
             ws = L.Guarded((nb,), torch.uint8, cuda)
-            _merge(cuda, sc, dev, 0, 0.5, out, src, kc, ws, nb)
+            _merge(cuda, sc, _device(cuda, sc), 0, 0.5, out, src, kc, ws, nb)
         else:
-            nb = lib.od_tta_merge_workspace_bytes(G, 1, K)
+            nb = lib.od_tta_merge_workspace_bytes(G, T, K)
             ws = L.Guarded((nb,), torch.uint8, cuda)
-            desc = (_lib.TtaView * 1)()
-            desc[0] = _lib.TtaView(dev["keys"].data_ptr(), dev["counts"].data_ptr(), dev["boxes"].data_ptr(), P, 0)
-            _lib.check(lib.od_tta_merge(h, desc, 1, G, NC, K, THR, 0, MAX_DET, 0.5, out.t.data_ptr(), src.t.data_ptr(),
+            # view t = rows t, T + t, ...: [B, ...] arrays of their own, as od_tta_view takes them
+            dev = [{k: L.poisoned(np.ascontiguousarray(sc[k][t::T]).view(np.uint8).reshape(-1), cuda)
+                    for k in ("keys", "counts", "boxes")} for t in range(T)]
+            desc = (_lib.TtaView * T)()
+            for t, d in enumerate(dev):
+                desc[t] = _lib.TtaView(d["keys"].data_ptr(), d["counts"].data_ptr(), d["boxes"].data_ptr(), P, 0)
+            _lib.check(lib.od_tta_merge(h, desc, T, G, NC, K, THR, 0, MAX_DET, 0.5, out.t.data_ptr(), src.t.data_ptr(),
                                         kc.t.data_ptr(), ws.t.data_ptr(), nb, _stream()), "od_tta_merge")
             torch.cuda.synchronize()
-        outs.append((out.numpy("out").view(np.uint32), src.numpy("src"), kc.numpy("kc")))
-    assert all(np.array_equal(a, b) for a, b in zip(*outs)) and int(outs[0][2].sum()) > 0
+        ws.check("workspace")
+        outs.append((out.numpy("out").view(np.uint32), src.numpy("src").view(np.uint32), kc.numpy("kc").view(np.uint32)))
+    assert all(np.array_equal(a, b) for a, b in zip(*outs)) and (outs[0][2] > 0).all()
 
 
 def test_slice_merge_rejects_bad_arguments(cuda):

@@ -171,6 +171,9 @@ def _scenario(name, rng):
         B, K, spec = 2, 1024, [(16800, 0, "full"), (16800, 1, "full"), (16800, 0, "full")]
     elif name == "B32":
         B, K, spec = 32, 256, [(16800, 0, "rand"), (16800, 1, "rand")]
+    elif name == "v8":  # the view capacity: P and flip alternate, and the quantised even views tie across views
+        B, K, spec = 1, 1024, [((16800, 4200)[v % 2], v % 2, how)
+                               for v, how in enumerate(("full", "rand", "rand", "small", "empty", "rand", "full", "rand"))]
     else:
         raise AssertionError(name)
     views = []
@@ -190,7 +193,7 @@ def _scenario(name, rng):
 
 
 SCENARIOS = ["v1", "v2_flip", "v2_two_sizes", "v4", "identical_views", "one_empty_view", "all_views_empty", "sum_below_K",
-             "sum_is_VK", "B32"]
+             "sum_is_VK", "B32", "v8"]
 
 
 def _check_merge(out, src, kc, views_np, b, NC, K, thr, strict, max_det, vote_iou, what):
